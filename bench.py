@@ -15,10 +15,13 @@ the reference's batch-global top_db floor is per call, i.e. per rank — SURVEY 
                                                         as a child BEFORE anything touches the GPU and relays its output
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...   (how the driver launches N > 1)
 
-Besides the headline the line carries: `sustained` (the same step timed over >= 2 s, after the burst figure), the two
-rooflines, `train_dp` (cfg 4: data-parallel CTC training steps of Conformer-small with the bucketed RCCL gradient
-all-reduce, its bus bandwidth and the exposed communication time; `--train` makes that leg the headline instead), and at
-N = 1 the CPU baselines.  Prints ONE JSON line on rank 0.
+A plain run sets up, warms up, times the K steps and prints the headline (`--train` makes the cfg-4 data-parallel CTC
+training step of Conformer-small the headline instead).  `--full` adds everything else: `sustained` (the same step timed
+over >= 2 s, after the burst figure), the two rooflines and their probes, cfg 3 and cfg 5, `train_dp` (the training step
+with the bucketed RCCL gradient all-reduce, its bus bandwidth and the exposed communication time), the hybrid and
+bucket-cycling training legs, and at N = 1 the CPU baselines.  `--dump-outputs DIR` writes what the timed path returned in
+its last step as DIR/<name>.npy (float32; the inputs and weights are seeded, so two builds can be compared output for
+output).  Prints ONE JSON line on rank 0.
 """
 import argparse
 import json
@@ -44,6 +47,20 @@ TRAIN_BATCH, TRAIN_FRAMES, TRAIN_VOCAB = 40, 1024, 4233  # conformer.yaml bucket
 
 def synth_batch(seed, n=BATCH):
     return (0.1 * np.random.RandomState(seed).randn(n, SAMPLES)).astype(np.float32)
+
+
+DUMP_BYTES_MAX = 64 << 20
+
+
+def dump_outputs(out_dir, **arrays):
+    """--dump-outputs: each array (a tensor on any device) as out_dir/<name>.npy in float32."""
+    import torch
+
+    arrays = {k: v.detach().to(torch.float32).cpu().numpy() for k, v in arrays.items()}
+    assert sum(a.nbytes for a in arrays.values()) <= DUMP_BYTES_MAX
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 # ======================================================================================================================
@@ -214,10 +231,11 @@ def comm_metrics(res, eng, world, force_collective, steps, timed, barrier):
 
 
 def train_leg(rank, world, dev, dist, steps, warmup, barrier, force_collective=False, digest=False, ctc_weight=1.0,
-              default_stream=False):
+              default_stream=False, full=True, dump_dir=None):
     """cfg 4: `steps` optimizer steps of ConformerCTCTrainStep on a (40, 1024, 80) batch per rank, gradients
-    all-reduced over RCCL in per-block buckets overlapped with the backward pass.  Also times the same all-reduce alone
-    (bus bandwidth) and the step with communication disabled (exposed communication)."""
+    all-reduced over RCCL in per-block buckets overlapped with the backward pass.  With `full`, also times the host side of
+    one step, the same all-reduce alone (bus bandwidth) and the step with communication disabled (exposed communication).
+    `dump_dir`: write the last timed step's loss and a fixed sample of the trained float32 masters there."""
     import torch
 
     from mindaudio_amd.conformer.asr_model import create_asr_model
@@ -256,6 +274,9 @@ def train_leg(rank, world, dev, dist, steps, warmup, barrier, force_collective=F
 
     first = [float(eng.step(*cols)[0]) for _ in range(max(warmup, 1))]
     dt, out = timed(steps)
+    if dump_dir is not None:  # (all masters are 138 MB: a seeded sample of 4 Mi of them)
+        idx = torch.from_numpy(np.random.RandomState(0).randint(0, eng.fp.size, 1 << 22)).to(dev)
+        dump_outputs(dump_dir, loss=out[0].reshape(1), masters_sample=eng.fp.master[idx])
     res = {"utterances_per_s": round(world * TRAIN_BATCH * steps / dt, 1), "ms_per_step": round(dt / steps * 1e3, 3),
            "steps": steps, "global_batch": TRAIN_BATCH * world, "frames": TRAIN_FRAMES, "vocab": TRAIN_VOCAB,
            "workload": "Conformer-small (12 blocks) %s training step: forward + backward + bucketed gradient "
@@ -268,24 +289,25 @@ def train_leg(rank, world, dev, dist, steps, warmup, barrier, force_collective=F
     tf = world * flops / (dt / steps) / 1e12
     res["roofline"] = {"bound": "mfma", "algorithmic_flops_per_step": int(world * flops), "achieved": round(tf, 1),
                        "peak": MFMA_BF16_PEAK_TF * world, "unit": "TFLOP/s", "frac": round(tf / (MFMA_BF16_PEAK_TF * world), 4)}
-    # host side of one step: the time to ENQUEUE it (Python + ctypes + launches) with the GPU kept busy, so that no call waits for
-    # the device; the step is GPU-bound while this stays below ms_per_step (8 ranks share one host)
-    enq = []
-    for _ in range(3):  # (median of three: the CPU baseline's child process may be busy on the same cores)
-        torch.cuda.synchronize()
-        torch.cuda._sleep(int(1e8))  # ~50 ms of GPU time in front of the step
-        t0 = time.perf_counter()
-        pending = eng.enqueue_step(*cols)
-        enq.append((time.perf_counter() - t0) * 1e3)
-        eng.finish_step(*pending)
-    res["host_enqueue_ms"] = round(sorted(enq)[1], 3)
+    if full:
+        # host side of one step: the time to ENQUEUE it (Python + ctypes + launches) with the GPU kept busy, so that no call waits for
+        # the device; the step is GPU-bound while this stays below ms_per_step (8 ranks share one host)
+        enq = []
+        for _ in range(3):  # (median of three: the CPU baseline's child process may be busy on the same cores)
+            torch.cuda.synchronize()
+            torch.cuda._sleep(int(1e8))  # ~50 ms of GPU time in front of the step
+            t0 = time.perf_counter()
+            pending = eng.enqueue_step(*cols)
+            enq.append((time.perf_counter() - t0) * 1e3)
+            eng.finish_step(*pending)
+        res["host_enqueue_ms"] = round(sorted(enq)[1], 3)
     if force_collective:
         res["force_collective"] = True
     if digest:  # bit pattern of the trained masters (tests/test_rccl_world1_gpu.py compares runs with and without the collective)
         import hashlib
 
         res["masters_sha16"] = hashlib.sha256(eng.fp.master.cpu().numpy().tobytes()).hexdigest()[:16]
-    if world > 1 or force_collective:
+    if full and (world > 1 or force_collective):
         comm_metrics(res, eng, world, force_collective, steps, timed, barrier)
     return res
 
@@ -295,6 +317,11 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: sustained figure, rooflines and probes, cfg3 / cfg5, training legs, CPU baselines "
+                         "(the --no-* switches below thin this out)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the timed path returned in its last step as DIR/<name>.npy (float32, seeded inputs)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-baseline-only", action="store_true", help="(internal) print the cpu_baseline object and exit")
     ap.add_argument("--train", action="store_true", help="headline = the cfg-4 data-parallel training step")
@@ -310,14 +337,14 @@ def main():
     ap.add_argument("--no-bucket-leg", action="store_true", help="skip the train_bucket_cycle object (the hybrid step over the yaml's "
                     "16 buckets, a different bucket every step)")
     ap.add_argument("--step-only", action="store_true",
-                    help="(profiling) only the warm-up + timed steps of the headline: no roofline loops, no cfg3 / cfg5 / training legs, "
-                         "no CPU baseline - the kernel stats of this run are the step's launches and nothing else")
+                    help="(profiling) the plain run even with --full: only the warm-up + timed steps of the headline, so that the "
+                         "kernel stats of this run are the step's launches and nothing else")
     ap.add_argument("--train-default-stream", action="store_true",
                     help="run the data-parallel training leg on torch's default stream instead of a stream of its own (A/B of the "
                          "hardware-queue sharing with RCCL's stream)")
     args = ap.parse_args()
     if args.step_only:
-        args.no_cpu_baseline = args.no_train_leg = args.no_sustained = args.no_cfg3 = args.no_cfg5 = True
+        args.full = False
 
     # ---- N > 1: one process per GPU.  Either we already are a rank (WORLD_SIZE set by torch.distributed.run) or this
     #      process becomes the launcher — decided here, before torch.cuda / any HIP call. ------------------------------
@@ -340,7 +367,7 @@ def main():
         print(json.dumps(cpu_baseline()))
         return
     cpu = None
-    if world == 1 and not args.no_cpu_baseline and not dry:
+    if world == 1 and args.full and not args.no_cpu_baseline and not dry:
         out = subprocess.run([sys.executable, os.path.abspath(__file__), "--cpu-baseline-only"], stdout=subprocess.PIPE, check=True)
         cpu = json.loads([l for l in out.stdout.decode().splitlines() if l.startswith("{")][-1])
 
@@ -405,7 +432,7 @@ def main():
         return dt
 
     t2 = ((FRAMES - 3) // 2 + 1 - 3) // 2 + 1
-    res = {}
+    train = None
     if not args.train:
         torch.manual_seed(777)  # examples/conformer/train.py:56
         enc = ConformerEncoder(80, 256, 4, 2048, 12).eval().to(dev).prepare()
@@ -426,9 +453,11 @@ def main():
         barrier()
         dt = max_over_ranks(time.perf_counter() - t0)
         assert tuple(out.shape) == (BATCH, t2, 256)
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, encoder_out=out)  # (64, 249, 256): 16 MB
 
         sustained = None
-        if not args.no_sustained:
+        if args.full and not args.no_sustained:
             # the same step over >= 2 s: the chip reaches its power limit within ~1 s (DVFS), the K-step figure above is a burst
             n_sus = max(args.steps, int(2.2 / (dt / args.steps)) + 1)
             barrier()
@@ -439,12 +468,47 @@ def main():
             ds = max_over_ranks(time.perf_counter() - t0)
             sustained = {"value": round(world * BATCH * n_sus / ds, 1), "unit": "utterances/s", "steps": n_sus,
                          "seconds": round(ds, 3), "ms_per_step": round(ds / n_sus * 1e3, 4)}
+    else:
+        train = train_leg(rank, world, dev, dist if world > 1 else None, args.steps, args.warmup, barrier, args.force_collective,
+                          args.train_digest, default_stream=args.train_default_stream, full=args.full,
+                          dump_dir=args.dump_outputs if rank == 0 else None)
 
-    if args.step_only:
+    def headline():
+        if args.train:
+            return {
+                "metric": "utterances/s, Conformer-small CTC training step (fwd + bwd + RCCL all-reduce + Adam), 1/2/4/8 MI355X",
+                "value": train["utterances_per_s"], "unit": "utterances/s", "n_gpus": world, "steps": args.steps,
+                "warmup": args.warmup, "ms_per_step": train["ms_per_step"], "higher_is_better": True, "scaling": "weak",
+                "vs_baseline": None, "dtype": "bf16", "data": "synthetic",
+                "config": {"workload": train["workload"], "global_batch": TRAIN_BATCH * world, "frames": TRAIN_FRAMES,
+                           "sharding": "data parallel by utterance, bucketed all-reduce (SUM) of the flat float32 gradient"},
+                "train_dp": {k: v for k, v in train.items() if k not in ("utterances_per_s", "ms_per_step", "workload")},
+            }
+        return {
+            "metric": "utterances/s (16 kHz×10 s) fbanks+Conformer fwd, 1/2/4/8 MI355X",
+            "value": round(world * BATCH * args.steps / dt, 1),
+            "unit": "utterances/s",
+            "n_gpus": world,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": round(dt / args.steps * 1e3, 4),
+            "higher_is_better": True,
+            "scaling": "weak",
+            "vs_baseline": None,
+            "dtype": "bf16",
+            "data": "synthetic",
+            "config": {"workload": "features.fbank (n_fft=512 hop=160 n_mels=80, batch-global top_db) on 64 x (10 s "
+                                   "@16 kHz) synthetic waves per GPU -> Conformer-small encoder forward (12 blocks, "
+                                   "d=256, 4 heads, ff=2048, conv k=15, eval mode) on the (64, 1000, 80) features; "
+                                   "random-init weights",
+                       "global_batch": BATCH * world, "frames": FRAMES,
+                       "sharding": "independent utterance shards per rank, no collective",
+                       "encoder_tflops": round(world * BATCH * args.steps * 23.12e9 / dt / 1e12, 1)},
+        }
+
+    if not args.full:
         if rank == 0:
-            print(json.dumps({"metric": "utterances/s (16 kHz×10 s) fbanks+Conformer fwd, 1/2/4/8 MI355X", "step_only": True,
-                              "value": round(world * BATCH * args.steps / dt, 1), "unit": "utterances/s", "n_gpus": world,
-                              "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 4)}))
+            print(json.dumps(headline()))
         if dist is not None:
             dist.destroy_process_group()
         return
@@ -641,12 +705,11 @@ def main():
             del m5
         del x5
 
-    train = hybrid = bucket_cycle = None
-    if args.train or not args.no_train_leg:
-        train = train_leg(rank, world, dev, dist if world > 1 else None, args.steps if args.train else args.train_steps,
-                          args.warmup if args.train else 2, barrier, args.force_collective, args.train_digest,
-                          default_stream=args.train_default_stream)
-        if not args.train and not args.no_hybrid_leg and world == 1 and not args.force_collective:
+    hybrid = bucket_cycle = None
+    if not args.train and not args.no_train_leg:
+        train = train_leg(rank, world, dev, dist if world > 1 else None, args.train_steps, 2, barrier, args.force_collective,
+                          args.train_digest, default_stream=args.train_default_stream)
+        if not args.no_hybrid_leg and world == 1 and not args.force_collective:
             import gc
 
             gc.collect()  # (an engine is a reference cycle: the first leg's launch tables and tape must not stay allocated - and be
@@ -669,40 +732,9 @@ def main():
                 torch.cuda.empty_cache()
 
     if rank == 0:
-        flops_utt = 23.12e9
-        if args.train:
-            res = {
-                "metric": "utterances/s, Conformer-small CTC training step (fwd + bwd + RCCL all-reduce + Adam), 1/2/4/8 MI355X",
-                "value": train["utterances_per_s"], "unit": "utterances/s", "n_gpus": world, "steps": args.steps,
-                "warmup": args.warmup, "ms_per_step": train["ms_per_step"], "higher_is_better": True, "scaling": "weak",
-                "vs_baseline": None, "dtype": "bf16", "data": "synthetic",
-                "config": {"workload": train["workload"], "global_batch": TRAIN_BATCH * world, "frames": TRAIN_FRAMES,
-                           "sharding": "data parallel by utterance, bucketed all-reduce (SUM) of the flat float32 gradient"},
-            }
-        else:
-            res = {
-                "metric": "utterances/s (16 kHz×10 s) fbanks+Conformer fwd, 1/2/4/8 MI355X",
-                "value": round(world * BATCH * args.steps / dt, 1),
-                "unit": "utterances/s",
-                "n_gpus": world,
-                "steps": args.steps,
-                "warmup": args.warmup,
-                "ms_per_step": round(dt / args.steps * 1e3, 4),
-                "higher_is_better": True,
-                "scaling": "weak",
-                "vs_baseline": None,
-                "dtype": "bf16",
-                "data": "synthetic",
-                "config": {"workload": "features.fbank (n_fft=512 hop=160 n_mels=80, batch-global top_db) on 64 x (10 s "
-                                       "@16 kHz) synthetic waves per GPU -> Conformer-small encoder forward (12 blocks, "
-                                       "d=256, 4 heads, ff=2048, conv k=15, eval mode) on the (64, 1000, 80) features; "
-                                       "random-init weights",
-                           "global_batch": BATCH * world, "frames": FRAMES,
-                           "sharding": "independent utterance shards per rank, no collective",
-                           "encoder_tflops": round(world * BATCH * args.steps * flops_utt / dt / 1e12, 1)},
-            }
-            if sustained is not None:
-                res["sustained"] = sustained
+        res = headline()
+        if not args.train and sustained is not None:
+            res["sustained"] = sustained
         res["roofline"] = {"bound": "mfma", "kernel": "ffn_packed_kernel, pair + qkv form (2 x [w_1 -> Swish -> w_2 + residual] + 4 LayerNorms + linear_q/k/v, "
                                                       "M=%d d=256 hidden=%d)" % (m, hid),
                            "achieved": round(gemm_tf, 1), "peak": MFMA_BF16_PEAK_TF, "unit": "TFLOP/s",
@@ -731,8 +763,6 @@ def main():
                 res["train_dp_hybrid"] = hybrid
             if bucket_cycle is not None:
                 res["train_bucket_cycle"] = bucket_cycle
-        elif train is not None:
-            res["train_dp"] = {k: v for k, v in train.items() if k not in ("utterances_per_s", "ms_per_step", "workload")}
         if cpu is not None:
             res["cpu_baseline"] = cpu
         print(json.dumps(res))

@@ -29,7 +29,7 @@ def _train_line(extra):
     env = dict(os.environ)
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
-           "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "1", "--train", "--steps", "3",
+           "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "1", "--train", "--full", "--steps", "3",
            "--warmup", "1", "--no-cpu-baseline", "--train-digest"] + extra
     res = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
     assert res.returncode == 0, res.stderr.decode()[-3000:]
@@ -72,8 +72,8 @@ def test_rccl_device_kernels_really_run_beside_the_backward_pass(tmp_path):
     env.update(RANK="0", LOCAL_RANK="0", WORLD_SIZE="1", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(_free_port()), TMPDIR=str(tmp_path))
     steps, warmup = 3, 1
     cmd = [prof, "--kernel-trace", "--output-format", "csv", "-d", str(tmp_path / "trace"), "--", sys.executable,
-           os.path.join(ROOT, "bench.py"), "--gpus", "1", "--train", "--steps", str(steps), "--warmup", str(warmup), "--no-cpu-baseline",
-           "--force-collective"]
+           os.path.join(ROOT, "bench.py"), "--gpus", "1", "--train", "--full", "--steps", str(steps), "--warmup", str(warmup),
+           "--no-cpu-baseline", "--force-collective"]
     res = subprocess.run(cmd, env=env, cwd=str(tmp_path), stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=1200)
     assert res.returncode == 0, res.stderr.decode()[-3000:]
     info = rccl_trace_check.analyse(str(tmp_path / "trace"))

@@ -8,5 +8,5 @@ cd $R
 timeout 1500 python -m pytest tests -m gpu -q "$@" > $OUT/pytest.log 2>&1
 echo "pytest rc=$?" >> $OUT/pytest.log
 tail -5 $OUT/pytest.log
-timeout 600 python bench.py --steps 20 --warmup 3 > $OUT/bench.log 2> $OUT/bench.err
+timeout 600 python bench.py --full --steps 20 --warmup 3 > $OUT/bench.log 2> $OUT/bench.err
 echo "bench rc=$?"; tail -c 6000 $OUT/bench.log; tail -5 $OUT/bench.err
