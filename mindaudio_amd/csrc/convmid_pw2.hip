@@ -9,6 +9,7 @@
 // trip fewer per block.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdlib.h>
 
 #include "../../include/mindaudio_amd.h"
 
@@ -677,12 +678,404 @@ __global__ __launch_bounds__(256, 2) void convmodule_kernel(const ConvModParams 
 #endif
 }
 
+// ---- OPROJ form on 64-frame tiles: one 8-wave workgroup per CU (the default for ma_attn_out_convmodule_bf16) --------------------
+// The 32-frame form above runs its projection, LayerNorm and pointwise_conv1 on 64 rows for 32 output frames (1.8x the needed MFMA
+// work) and each of its two workgroups per CU streams the whole weight set (527 KB) from L2.  Here a workgroup emits 64 frames of one
+// utterance and works on the 80 rows t0 - 8 .. t0 + 71 (5 MFMA row tiles; halo 8 >= (k - 1) / 2), and one workgroup of 8 waves runs
+// per CU: 1.25 rows per output frame instead of 2, and half the weight stream per CU.  Each wave owns 32 of the 256 output columns of
+// the out-projection and pointwise_conv2 and 32 value + 32 gate columns of pointwise_conv1 (80 + 160 + 64 MFMAs per wave).
+//   0. ctx tile [80][544 B] + taps + per-channel parameters -> LDS; x' = x + ctx . Wo^T + bo on 5 row tiles; the LayerNorm row sums
+//      are reduced in the 32-frame kernel's order (wave pairs, row swaps, then through LDS: two barriers); a = LN(x') * mask -> the
+//      a-tile over the ctx tile.  The x' rows of the tile's own 64 frames stay in registers: projection row r = frame t0 - 8 + r, so
+//      the epilogue's frame t0 + 16 s + c is row 16 s + c + 8 = lane c ^ 8 of row tile s or s + 1 - one DPP row rotation.
+//   1. pointwise_conv1 + GLU on all 80 rows in two sub-passes (value tile 2 w + sp with its gate tile), y tile [80][528 B].
+//   2. depthwise conv + BN + Swish: 4 frames x 8 channels per thread (512 threads = 64 frames x 256 channels), z tile over the a-tile.
+//   3. z . Wp2^T + bias, x_out = x' + mask * (...).
+// Each phase's first weight fragments are requested before the barrier that ends the phase before it.
+constexpr int kCm64Tile = 64, kCm64Halo = 8, kCm64Rows = kCm64Tile + 2 * kCm64Halo, kCm64Threads = 512;
+struct Cm64Layout {
+  static constexpr int kOffY = kCm64Rows * kCpPitch;                  // 43520: ctx tile, then a-tile, then z tile [64][544 B]
+  static constexpr int kOffW = kOffY + kCm64Rows * kCmYPitch;         // 85760: y tile [80][528 B]
+  static constexpr int kOffPar = kOffW + kCpMaxK * 256 * 4;           // 101120: taps wl[k][c]
+  static constexpr int kLds = kOffPar + 4096;                         // 105216: b1 (512), bn_scale, bn_shift as floats
+  // phase 0 only, inside the not yet written y tile: the LayerNorm exchanges (partial sums [80][4][4] x 16 B, wave totals
+  // [2][80][4] floats), then ln_g, ln_b, bo
+  static constexpr int kOffPart = kOffY;
+  static constexpr int kOffWsum = kOffPart + kCm64Rows * 16 * 16;
+  static constexpr int kOffPar0 = kOffWsum + 2 * kCm64Rows * 4 * 4;
+};
+static_assert(Cm64Layout::kOffPar0 + 3 * 256 * 4 <= Cm64Layout::kOffW, "phase-0 scratch must fit in the y tile");
+static_assert(Cm64Layout::kLds <= 160 * 1024, "LDS");
+
+__device__ __forceinline__ float cp_ror8(float v) {  // lane c of every 16-lane row reads lane c ^ 8 (row_ror:8)
+  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x128, 0xf, 0xf, false));
+}
+
+__global__ __launch_bounds__(kCm64Threads, 1) void convmodule64_kernel(const ConvModParams p) {
+#ifdef MA_CM_PROF
+  unsigned long long cm_ts[16];
+  CM_STAMP(0);
+#endif
+  typedef Cm64Layout L;
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int c = lane & 15, g = lane >> 4;
+  const int b = blockIdx.y, t0 = blockIdx.x * kCm64Tile, tb = t0 - kCm64Halo;  // projection row r is frame tb + r
+  const int KS = p.KS, half = KS / 2;
+  const int64_t row0 = (int64_t)b * p.T;
+  float* wl = reinterpret_cast<float*>(smem + L::kOffW);
+  char* ytile = smem + L::kOffY;
+  const float* par0 = reinterpret_cast<const float*>(smem + L::kOffPar0);
+  const float* par = reinterpret_cast<const float*>(smem + L::kOffPar);
+  const char* abase = smem + c * kCpPitch + g * 16;
+  const int ncol = 32 * wave + 4 * g;  // + 16 jt: this lane's output columns in phases 0 and 3
+
+  // ---- phase 0: x' = x + ctx . Wo^T + bo; a = LN(x') * mask on the 80 frames tb .. tb + 79 -----------------------------------------
+  f32x4 acc[2][5];
+  f32x4 xall[5][2];
+  float mall[5];
+  {
+    // straight-line staging, as convmodule_kernel<true>: every global load of the phase in flight before the first LDS store; rows
+    // outside the utterance are loaded clamped (their LayerNorm rows are masked to zero, their GLU rows zeroed)
+    f32x4 cv[kCm64Rows * 32 / kCm64Threads];
+#pragma unroll
+    for (int it = 0; it < kCm64Rows * 32 / kCm64Threads; ++it) {
+      const int idx = it * kCm64Threads + tid;
+      int t = tb + (idx >> 5);
+      t = t < 0 ? 0 : (t >= p.T ? p.T - 1 : t);
+      cv[it] = *reinterpret_cast<const f32x4*>(p.ctx + (row0 + t) * p.ldc + (idx & 31) * 8);
+    }
+    const int ch = tid & 255, hi = tid >> 8;  // taps k = hi, hi + 2, ... of channel ch; parameter half hi
+    float taps[(kCpMaxK + 1) / 2];
+#pragma unroll
+    for (int i = 0; i < (kCpMaxK + 1) / 2; ++i) {
+      const int k = min(hi + 2 * i, KS - 1);
+      taps[i] = p.dw[ch * KS + k];
+    }
+    float pv[4];
+    if (hi == 0) {
+      pv[0] = p.ln_g[ch]; pv[1] = p.ln_b[ch]; pv[2] = p.bo[ch]; pv[3] = p.b1[ch];
+    } else {
+      pv[0] = p.b1[256 + ch]; pv[1] = p.bn_scale[ch]; pv[2] = p.bn_shift[ch]; pv[3] = 0.f;
+    }
+    bf16x8 wo[2][8];
+    {
+      const uint4* base = p.wop + ((int64_t)(wave * 2) * 8) * 64 + lane;
+#pragma unroll
+      for (int jt = 0; jt < 2; ++jt)
+#pragma unroll
+        for (int ks = 0; ks < 8; ++ks) wo[jt][ks] = *reinterpret_cast<const bf16x8*>(base + (jt * 8 + ks) * 64);
+    }
+    // residual rows and row mask, requested behind Wo so that they fly under the out-projection (unconditional loads: dead rows
+    // read row 0 of the utterance and are zeroed by the select of the LayerNorm step)
+    int64_t mrow[5];
+#pragma unroll
+    for (int s = 0; s < 5; ++s) {
+      const int t = tb + 16 * s + c;
+      mrow[s] = row0 + ((t >= 0 && t < p.T) ? t : 0);
+#pragma unroll
+      for (int jt = 0; jt < 2; ++jt) xall[s][jt] = *reinterpret_cast<const f32x4*>(p.x + mrow[s] * p.ldx + ncol + 16 * jt);
+    }
+    if (p.mask) {  // (one uniform branch around all five loads, not one per row)
+#pragma unroll
+      for (int s = 0; s < 5; ++s) mall[s] = p.mask[mrow[s]];
+    } else {
+#pragma unroll
+      for (int s = 0; s < 5; ++s) mall[s] = 1.0f;
+    }
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int it = 0; it < kCm64Rows * 32 / kCm64Threads; ++it) {
+      const int idx = it * kCm64Threads + tid;
+      *reinterpret_cast<f32x4*>(smem + (idx >> 5) * kCpPitch + (idx & 31) * 16) = cv[it];
+    }
+#pragma unroll
+    for (int i = 0; i < (kCpMaxK + 1) / 2; ++i)
+      if (hi + 2 * i < KS) wl[(hi + 2 * i) * 256 + ch] = taps[i];
+    {
+      float* q0 = reinterpret_cast<float*>(smem + L::kOffPar0);
+      float* q = reinterpret_cast<float*>(smem + L::kOffPar);
+      if (hi == 0) {
+        q0[ch] = pv[0]; q0[256 + ch] = pv[1]; q0[512 + ch] = pv[2]; q[ch] = pv[3];
+      } else {
+        q[256 + ch] = pv[0]; q[512 + ch] = pv[1]; q[768 + ch] = pv[2];
+      }
+    }
+    __syncthreads();
+    CM_STAMP(1);
+#pragma unroll
+    for (int jt = 0; jt < 2; ++jt)
+#pragma unroll
+      for (int s = 0; s < 5; ++s) acc[jt][s] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int ks = 0; ks < 8; ++ks) {
+      bf16x8 af[5];
+#pragma unroll
+      for (int s = 0; s < 5; ++s) af[s] = *reinterpret_cast<const bf16x8*>(abase + s * 16 * kCpPitch + ks * 64);
+#pragma unroll
+      for (int jt = 0; jt < 2; ++jt)
+#pragma unroll
+        for (int s = 0; s < 5; ++s) acc[jt][s] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wo[jt][ks], af[s], acc[jt][s], 0, 0, 0);
+    }
+  }
+  CM_STAMP(2);
+  // pointwise_conv1's first sub-pass of weight fragments: in flight under the LayerNorm exchange
+  bf16x8 wq[2][2][8];  // [sub-pass][value | gate][k-step]
+#define CM64_LOAD_SP(sp)                                                                                           \
+  {                                                                                                              \
+    _Pragma("unroll") for (int vg = 0; vg < 2; ++vg) {                                                           \
+      const uint4* base = p.w1p + ((int64_t)(vg * 16 + wave * 2 + (sp)) * 8) * 64 + lane;                        \
+      _Pragma("unroll") for (int ks = 0; ks < 8; ++ks) wq[sp][vg][ks] = *reinterpret_cast<const bf16x8*>(base + ks * 64); \
+    }                                                                                                            \
+  }
+  CM64_LOAD_SP(0)
+  __builtin_amdgcn_sched_barrier(0);
+  // LayerNorm statistics in exactly the order of convmodule_kernel<true> (and of gemm_packed_ln's epilogue), so that a = LN(x') is
+  // the same bf16 tile: there, lane (c, g) of wave w' sums the column tiles 64 w' + 16 j + 4 g (j = 0..3) in sequence, the lane
+  // groups by two row swaps, the four waves pairwise.  Here those four tiles are jt = 0, 1 of the waves 2 w' and 2 w' + 1: the odd
+  // wave hands its two partial sums per row and lane to the even one through LDS, which completes the sequence and the row swaps;
+  // the wave totals meet in LDS again (two barriers: reduced in another order, a few elements of a round the other way and the
+  // result no longer matches the two-launch path bit for bit).
+  float ps[5][2], pq[5][2], msk[5];
+  {
+    float4 bv[2];
+#pragma unroll
+    for (int jt = 0; jt < 2; ++jt) bv[jt] = *reinterpret_cast<const float4*>(par0 + 512 + ncol + 16 * jt);
+#pragma unroll
+    for (int s = 0; s < 5; ++s) {
+      const int t = tb + 16 * s + c;
+      const bool live = t >= 0 && t < p.T;
+      msk[s] = live ? mall[s] : 0.0f;
+#pragma unroll
+      for (int jt = 0; jt < 2; ++jt) {
+        const f32x4 xl = xall[s][jt];
+        const float4 xv = live ? make_float4(xl[0], xl[1], xl[2], xl[3]) : make_float4(0.f, 0.f, 0.f, 0.f);
+        const float v0 = (acc[jt][s][0] + bv[jt].x) + xv.x, v1 = (acc[jt][s][1] + bv[jt].y) + xv.y;
+        const float v2 = (acc[jt][s][2] + bv[jt].z) + xv.z, v3 = (acc[jt][s][3] + bv[jt].w) + xv.w;
+        acc[jt][s] = f32x4{v0, v1, v2, v3};
+        ps[s][jt] = (v0 + v1) + (v2 + v3);
+        pq[s][jt] = (v0 * v0 + v1 * v1) + (v2 * v2 + v3 * v3);
+      }
+    }
+  }
+  float4* part = reinterpret_cast<float4*>(smem + L::kOffPart);  // [80 rows][4 w'][4 g]: the odd waves' (sum j2, sum j3, sq j2, sq j3)
+  float* wsum = reinterpret_cast<float*>(smem + L::kOffWsum);      // [2][80 rows][4 w']
+  if (wave & 1) {
+#pragma unroll
+    for (int s = 0; s < 5; ++s) part[((16 * s + c) * 4 + (wave >> 1)) * 4 + g] = make_float4(ps[s][0], ps[s][1], pq[s][0], pq[s][1]);
+  }
+  __syncthreads();  // (also: every wave is done reading the ctx tile)
+  if (!(wave & 1)) {
+#pragma unroll
+    for (int s = 0; s < 5; ++s) {
+      const float4 o = part[((16 * s + c) * 4 + (wave >> 1)) * 4 + g];
+      float rs = 0.f, rq = 0.f;
+      rs += ps[s][0]; rs += ps[s][1]; rs += o.x; rs += o.y;
+      rq += pq[s][0]; rq += pq[s][1]; rq += o.z; rq += o.w;
+      const float a = cp_sum_xor32(cp_sum_xor16(rs)), q = cp_sum_xor32(cp_sum_xor16(rq));
+      if (g == 0) {
+        wsum[(16 * s + c) * 4 + (wave >> 1)] = a;
+        wsum[kCm64Rows * 4 + (16 * s + c) * 4 + (wave >> 1)] = q;
+      }
+    }
+  }
+  __syncthreads();
+  CM_STAMP(3);
+#pragma unroll
+  for (int s = 0; s < 5; ++s) {
+    const int r = 16 * s + c;
+    const float4 w4 = *reinterpret_cast<const float4*>(wsum + r * 4), q4 = *reinterpret_cast<const float4*>(wsum + kCm64Rows * 4 + r * 4);
+    const float sum = (w4.x + w4.y) + (w4.z + w4.w);
+    const float sq = (q4.x + q4.y) + (q4.z + q4.w);
+    const float mean = sum * (1.0f / 256.0f);
+    const float var = fmaxf(sq * (1.0f / 256.0f) - mean * mean, 0.0f);
+    const float inv = 1.0f / sqrtf(var + p.ln_eps);
+#pragma unroll
+    for (int jt = 0; jt < 2; ++jt) {
+      const int n = ncol + 16 * jt;
+      const float4 ga = *reinterpret_cast<const float4*>(par0 + n);
+      const float4 be = *reinterpret_cast<const float4*>(par0 + 256 + n);
+      const f32x4 v = acc[jt][s];
+      *reinterpret_cast<uint2*>(smem + r * kCpPitch + n * 2) =
+          make_uint2(cp_pack_bf16(((v[0] - mean) * inv * ga.x + be.x) * msk[s], ((v[1] - mean) * inv * ga.y + be.y) * msk[s]),
+                     cp_pack_bf16(((v[2] - mean) * inv * ga.z + be.z) * msk[s], ((v[3] - mean) * inv * ga.w + be.w) * msk[s]));
+    }
+  }
+  // x' of the own frames t0 + 16 s + c in the epilogue's layout: row 16 s + c + 8 = lane c ^ 8 of row tile s (c < 8) or s + 1
+  f32x4 xo[2][4];
+  {
+    const bool up = c >= 8;  // as a source lane: which row tile the destination lane c ^ 8 needs
+#pragma unroll
+    for (int jt = 0; jt < 2; ++jt)
+#pragma unroll
+      for (int s = 0; s < 4; ++s)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) xo[jt][s][e] = cp_ror8(up ? acc[jt][s][e] : acc[jt][s + 1][e]);
+  }
+  CM64_LOAD_SP(1)  // the second sub-pass's fragments fly under the barrier and the first sub-pass
+  __syncthreads();  // the a-tile is complete; the exchange buffer is free again
+  CM_STAMP(4);
+
+  // ---- phase 1: pointwise_conv1 + GLU on the 80 rows, two sub-passes of (value tile 2 w + sp, gate tile 16 + 2 w + sp) ----------
+#pragma unroll
+  for (int sp = 0; sp < 2; ++sp) {
+    __builtin_amdgcn_sched_barrier(0);  // (without these fences the scheduler interleaves the sub-passes and spills)
+    f32x4 a2[2][5];
+#pragma unroll
+    for (int vg = 0; vg < 2; ++vg)
+#pragma unroll
+      for (int s = 0; s < 5; ++s) a2[vg][s] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int ks = 0; ks < 8; ++ks) {
+      bf16x8 af[5];
+#pragma unroll
+      for (int s = 0; s < 5; ++s) af[s] = *reinterpret_cast<const bf16x8*>(abase + s * 16 * kCpPitch + ks * 64);
+#pragma unroll
+      for (int vg = 0; vg < 2; ++vg)
+#pragma unroll
+        for (int s = 0; s < 5; ++s) a2[vg][s] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wq[sp][vg][ks], af[s], a2[vg][s], 0, 0, 0);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    const int n = ncol + 16 * sp;
+    const float4 bvv = *reinterpret_cast<const float4*>(par + n);
+    const float4 bg = *reinterpret_cast<const float4*>(par + kCpC + n);
+#pragma unroll
+    for (int s = 0; s < 5; ++s) {
+      const int t = tb + 16 * s + c;
+      const bool live = t >= 0 && t < p.T;
+      const float y0 = live ? cp_sigmoid_mul(a2[0][s][0] + bvv.x, a2[1][s][0] + bg.x) : 0.f;
+      const float y1 = live ? cp_sigmoid_mul(a2[0][s][1] + bvv.y, a2[1][s][1] + bg.y) : 0.f;
+      const float y2 = live ? cp_sigmoid_mul(a2[0][s][2] + bvv.z, a2[1][s][2] + bg.z) : 0.f;
+      const float y3 = live ? cp_sigmoid_mul(a2[0][s][3] + bvv.w, a2[1][s][3] + bg.w) : 0.f;
+      *reinterpret_cast<uint2*>(ytile + (16 * s + c) * kCmYPitch + n * 2) = make_uint2(cp_pack_bf16(y0, y1), cp_pack_bf16(y2, y3));
+    }
+  }
+#undef CM64_LOAD_SP
+  // pointwise_conv2's fragments of this wave (columns 32 w .. 32 w + 31), the epilogue's bias and row mask: in flight across the
+  // barrier and the depthwise phase
+  bf16x8 wf[2][8];
+  {
+    const uint4* base = p.wp + ((int64_t)(wave * 2) * 8) * 64 + lane;
+#pragma unroll
+    for (int jt = 0; jt < 2; ++jt)
+#pragma unroll
+      for (int ks = 0; ks < 8; ++ks) wf[jt][ks] = *reinterpret_cast<const bf16x8*>(base + (jt * 8 + ks) * 64);
+  }
+  float4 bv2[2];
+  float rs2[4];
+#pragma unroll
+  for (int jt = 0; jt < 2; ++jt) bv2[jt] = *reinterpret_cast<const float4*>(p.bias + ncol + 16 * jt);
+  if (p.mask) {
+#pragma unroll
+    for (int s = 0; s < 4; ++s) rs2[s] = p.mask[row0 + min(t0 + 16 * s + c, p.T - 1)];
+  } else {
+#pragma unroll
+    for (int s = 0; s < 4; ++s) rs2[s] = 1.0f;
+  }
+  __syncthreads();  // y tile complete; the a-tile is dead
+  CM_STAMP(5);
+
+  // ---- phase 2: depthwise conv + BatchNorm (affine) + Swish: frames t0 + 8 rg .. + 7, channels 4 cg .. + 3 -------------------------
+  // (a wave reads whole 512-byte y rows; 4 channels x 8 frames per thread keeps 60 taps in registers instead of 120, which leaves
+  // room for pointwise_conv2's fragments to be in flight here)
+  const int cg = tid & 63, rg = tid >> 6;
+  const int c0 = cg * 4;
+  {
+    float w[kCpMaxK][4];
+#pragma unroll
+    for (int k = 0; k < kCpMaxK; ++k) {
+      if (k < KS) {
+        const float4 w0 = *reinterpret_cast<const float4*>(wl + k * 256 + c0);
+        w[k][0] = w0.x; w[k][1] = w0.y; w[k][2] = w0.z; w[k][3] = w0.w;
+      } else {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) w[k][e] = 0.0f;
+      }
+    }
+    float dacc[8][4];
+#pragma unroll
+    for (int o = 0; o < 8; ++o)
+#pragma unroll
+      for (int e = 0; e < 4; ++e) dacc[o][e] = 0.0f;
+    const char* yb = ytile + (rg * 8 + kCm64Halo - half) * kCmYPitch + c0 * 2;  // y row of frame t0 + 8 rg - half
+#pragma unroll
+    for (int r = 0; r < kCpMaxK + 7; ++r) {  // y row r feeds output o with tap k = r - o
+      if (r < KS + 7) {
+        const uint2 q = *reinterpret_cast<const uint2*>(yb + r * kCmYPitch);
+        const float gv[4] = {cp_from_bf16(q.x & 0xffff), cp_from_bf16(q.x >> 16), cp_from_bf16(q.y & 0xffff), cp_from_bf16(q.y >> 16)};
+#pragma unroll
+        for (int o = 0; o < 8; ++o) {
+          const int k = r - o;
+          if (k >= 0 && k < kCpMaxK) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) dacc[o][e] = fmaf(w[k][e], gv[e], dacc[o][e]);
+          }
+        }
+      }
+    }
+    const float4 sc = *reinterpret_cast<const float4*>(par + 512 + c0), sh = *reinterpret_cast<const float4*>(par + 768 + c0);
+    CM_STAMP(6);
+#pragma unroll
+    for (int o = 0; o < 8; ++o) {
+      const float z0 = dacc[o][0] * sc.x + sh.x, z1 = dacc[o][1] * sc.y + sh.y;
+      const float z2 = dacc[o][2] * sc.z + sh.z, z3 = dacc[o][3] * sc.w + sh.w;
+      *reinterpret_cast<uint2*>(smem + (rg * 8 + o) * kCpPitch + c0 * 2) =  // z tile over the a-tile
+          make_uint2(cp_pack_bf16(cp_sigmoid_mul(z0, z0), cp_sigmoid_mul(z1, z1)), cp_pack_bf16(cp_sigmoid_mul(z2, z2), cp_sigmoid_mul(z3, z3)));
+    }
+  }
+  __syncthreads();
+  CM_STAMP(7);
+
+  // ---- phase 3: z . Wp2^T; x_out = x' + mask * (... + bias) ------------------------------------------------------------------------
+  f32x4 acc2[2][4];
+#pragma unroll
+  for (int jt = 0; jt < 2; ++jt)
+#pragma unroll
+    for (int s = 0; s < 4; ++s) acc2[jt][s] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int ks = 0; ks < 8; ++ks) {
+    bf16x8 af[4];
+#pragma unroll
+    for (int s = 0; s < 4; ++s) af[s] = *reinterpret_cast<const bf16x8*>(abase + s * 16 * kCpPitch + ks * 64);
+#pragma unroll
+    for (int jt = 0; jt < 2; ++jt)
+#pragma unroll
+      for (int s = 0; s < 4; ++s) acc2[jt][s] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[jt][ks], af[s], acc2[jt][s], 0, 0, 0);
+  }
+  CM_STAMP(8);
+#pragma unroll
+  for (int s = 0; s < 4; ++s) {
+    const int t = t0 + 16 * s + c;
+    if (t >= p.T) continue;
+    const int64_t m = row0 + t;
+    const float rs = rs2[s];
+#pragma unroll
+    for (int jt = 0; jt < 2; ++jt) {
+      const float4 bv = bv2[jt];
+      const f32x4 xv = xo[jt][s];
+      *reinterpret_cast<float4*>(p.xo + m * p.ldx + ncol + 16 * jt) =
+          make_float4(xv[0] + (acc2[jt][s][0] + bv.x) * rs, xv[1] + (acc2[jt][s][1] + bv.y) * rs,
+                      xv[2] + (acc2[jt][s][2] + bv.z) * rs, xv[3] + (acc2[jt][s][3] + bv.w) * rs);
+    }
+  }
+#ifdef MA_CM_PROF
+  CM_STAMP(9);
+  {
+    const int wg = blockIdx.y * gridDim.x + blockIdx.x;
+    const int slot = wg == 0 ? 0 : wg == 100 ? 1 : wg == 255 ? 2 : -1;
+    if (threadIdx.x == 0 && slot >= 0)
+      for (int k = 0; k < 10; ++k) g_cm_prof[slot * 16 + k] = cm_ts[k];
+  }
+#endif
+}
+
 #ifdef MA_CM_PROF
 extern "C" int ma_debug_cm_prof(unsigned long long* host48) {
   return hipMemcpyFromSymbol(host48, HIP_SYMBOL(g_cm_prof), sizeof(unsigned long long) * 48) == hipSuccess ? 0 : -1;
 }
 #endif
 
+MA_LDS_ATTR(convmodule64_kernel, Cm64Layout::kLds);
 MA_LDS_ATTR(convmid_pw2_kernel, (kCpTile + 2 * kCpMaxK - 1) * 256 * 4);
 MA_LDS_ATTR(convmodule_kernel<false>, CmLayout<false>::kLds);
 MA_LDS_ATTR(convmodule_kernel<true>, CmLayout<true>::kLds);
@@ -720,9 +1113,23 @@ extern "C" int ma_convmid_pw2_bf16(const void* y, int64_t ldy, int64_t batch, in
   return MA_OK;
 }
 
+// The OPROJ form runs on convmodule64_kernel; MINDAUDIO_AMD_CONVMOD=t32 selects the 32-frame convmodule_kernel<true> for the whole
+// process instead (same-library A/B, and the tests keep the fallback covered).  Every shape the entry points accept (C = 256, odd
+// k <= 15) fits either kernel.
+static bool convmod_use_t32() {
+  static const bool use = [] {
+    const char* e = getenv("MINDAUDIO_AMD_CONVMOD");
+    return e && e[0] == 't' && e[1] == '3' && e[2] == '2';
+  }();
+  return use;
+}
+
 static int convmodule_launch(ConvModParams& p, int64_t batch, int64_t T, ma_stream_t stream) {
   const dim3 grid((unsigned)((T + kCpTile - 1) / kCpTile), (unsigned)batch);
-  if (p.ctx)
+  if (p.ctx && !convmod_use_t32())
+    MA_LAUNCH(convmodule64_kernel, dim3((unsigned)((T + kCm64Tile - 1) / kCm64Tile), (unsigned)batch), dim3(kCm64Threads),
+              Cm64Layout::kLds, (hipStream_t)stream, p);
+  else if (p.ctx)
     MA_LAUNCH(convmodule_kernel<true>, grid, dim3(256), CmLayout<true>::kLds, (hipStream_t)stream, p);
   else
     MA_LAUNCH(convmodule_kernel<false>, grid, dim3(256), CmLayout<false>::kLds, (hipStream_t)stream, p);

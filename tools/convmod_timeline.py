@@ -1,5 +1,6 @@
-"""Phase timeline of convmodule_kernel<OPROJ> from a -DMA_CM_PROF build of convmid_pw2.hip (tools/cm_variants.sh): wall_clock64
-stamps (100 MHz) of wave 0 of three workgroups (first, middle, last)."""
+"""Phase timeline of the conv-module launch from a -DMA_CM_PROF build of convmid_pw2.hip (tools/cm_variants.sh): wall_clock64
+stamps (100 MHz) of wave 0 of three workgroups (first, middle, last).  The 64-frame convmodule64_kernel by default;
+MINDAUDIO_AMD_CONVMOD=t32 times the 32-frame convmodule_kernel<true> instead."""
 import ctypes
 import os
 import sys
@@ -35,8 +36,15 @@ for _ in range(50):
 e1.record()
 torch.cuda.synchronize()
 print("launch %.1f us (back to back, instrumented build)" % (e0.elapsed_time(e1) / 50 * 1e3))
-names = ["entry", "ctx tile + taps staged", "out-projection MFMAs", "+ residual, LN statistics", "a-tile written", "pw1 + GLU (y tile)",
-         "depthwise + BN + Swish", "z tile + barrier", "pw2 MFMAs", "end"]
+t32 = os.environ.get("MINDAUDIO_AMD_CONVMOD", "").startswith("t32")
+if t32:
+    names = ["entry", "ctx tile + taps staged", "out-projection MFMAs", "+ residual, LN statistics", "a-tile written",
+             "pw1 + GLU (y tile)", "depthwise + BN + Swish", "z tile + barrier", "pw2 MFMAs", "end"]
+    wgs = (0, 200, 511)
+else:
+    names = ["entry", "ctx tile + taps staged", "out-projection MFMAs", "+ residual, LN statistics", "a-tile written",
+             "pw1 + GLU (y tile)", "depthwise FMAs", "BN + Swish, z tile + barrier", "pw2 MFMAs", "end"]
+    wgs = (0, 100, 255)
 acc = {}
 N = 20
 lib.ma_debug_cm_prof.argtypes = [ctypes.c_void_p]
@@ -50,7 +58,7 @@ for it in range(N):
     for w in range(3):
         for k in range(10):
             acc.setdefault((w, k), []).append((a[w, k] - t0) / 100.0)
-print("%-28s %14s %14s %14s   (us since the first start; median of %d; +delta)" % ("phase", "wg 0", "wg 200", "wg 511", N))
+print("%-28s %14s %14s %14s   (us since the first start; median of %d; +delta)" % (("phase",) + tuple("wg %d" % w for w in wgs) + (N,)))
 prev = [0, 0, 0]
 for k in range(10):
     med = [float(np.median(acc[(w, k)])) for w in range(3)]
