@@ -301,6 +301,42 @@ int ma_ctc_greedy_search_f32(const float* logits, int64_t ld, int64_t batch, int
                              int32_t blank, int32_t* best, float* best_logp, int32_t* hyp, int32_t* hyp_len,
                              ma_stream_t stream);
 
+/* CTC top-k (the ops.TopK(ctc_probs, beam_size) of CTCPrefixBeamSearch, models/decoders/decoder_factory.py:195-239): per row of
+ * logits (rows, V) float32 with row stride ld, the k largest values of log_softmax(row) in descending order, equal values lower
+ * index first: topk_logp / topk_index (rows, k) contiguous.  One wave per row.  1 <= k <= 16 and k <= V, else MA_ERR_UNSUPPORTED
+ * (k > 16) / MA_ERR_INVALID_ARG. */
+int ma_ctc_topk_f32(const float* logits, int64_t ld, int64_t rows, int32_t V, int32_t k, float* topk_logp, int32_t* topk_index,
+                    ma_stream_t stream);
+
+/* CTC prefix beam search (utils/recognize.py:273-336), batched: one workgroup per utterance, one launch for the batch.
+ *   topk_logp (batch, T, beam) float32 / topk_index (batch, T, beam) int32: ma_ctc_topk_f32 with k = beam (indices of a frame
+ *     distinct, as TopK gives them); mask (batch*T) float32 or NULL: frames with mask == 0 are skipped wherever they are.
+ *   Per frame, for every (top-k entry s, hypothesis) pair in the reference's loop order: s == blank -> pb of the prefix; s == the
+ *   prefix's last token -> pnb of the prefix from pnb and pnb of prefix + s from pb; otherwise pnb of prefix + s from pb and pnb.
+ *   float64 arithmetic with the reference's log_add (argument order kept); the candidates ranked by log_add(pb, pnb) descending,
+ *   ties in first-touch order, the first `beam` kept.  Prefixes are compared exactly (a 64-bit hash only filters).
+ *   hyp (batch, beam, T) int32 (a hypothesis slot's tokens, zero padded), hyp_len (batch, beam), score (batch, beam) float64 =
+ *   log_add(pb, pnb), n_hyp (batch): how many hypotheses survived (<= beam: an utterance with one valid frame may have fewer;
+ *   slots past n_hyp hold length 0 and score -inf).
+ * Limits: 1 <= beam <= 16 and 2 * beam * T * 4 bytes of prefix tokens (double buffered in LDS) <= 144 KiB (beam 16: T <= 1152),
+ * else MA_ERR_UNSUPPORTED. */
+int ma_ctc_prefix_beam_search_f32(const float* topk_logp, const int32_t* topk_index, const float* mask, int64_t batch, int32_t T,
+                                  int32_t beam, int32_t blank, int32_t* hyp, int32_t* hyp_len, double* score, int32_t* n_hyp,
+                                  ma_stream_t stream);
+
+/* The score loop of attention_rescoring (utils/recognize.py:393-406) for n_utt utterances of `group` hypotheses each:
+ *   logits (n_utt*group*L1, V) float32 with row stride ld (the decoder's scores before log_softmax), tokens (n_utt*group, ld_tok)
+ *   int32 with lens (n_utt*group) <= L1 - 1, ctc_score (n_utt*group) float64, n_hyp (n_utt) int32 or NULL (all valid): hypotheses
+ *   h >= n_hyp[b] of an utterance are skipped.
+ *   hyp_score[h] = sum_{j < len} logp[j][tok_j] + logp[len][eos] + ctc_weight * ctc_score[h] summed in float64 in that order, logp
+ *   the row's log_softmax (one wave per row; -inf for a skipped hypothesis, NaN for a length or token out of range);
+ *   best_index / best_score (n_utt): the first hypothesis with the highest score (a later one wins only if strictly greater; 0 and
+ *   -inf when none is valid).  workspace >= n_utt*group*L1 float64.  Two launches. */
+int ma_hyp_score_f32(const float* logits, int64_t ld, int32_t V, int64_t n_utt, int32_t group, int32_t L1, const int32_t* tokens,
+                     int64_t ld_tok, const int32_t* lens, const int32_t* n_hyp, int32_t eos, const double* ctc_score,
+                     double ctc_weight, double* workspace, double* hyp_score, int32_t* best_index, double* best_score,
+                     ma_stream_t stream);
+
 /* float32 -> bf16 (round to nearest even), n % 4 == 0: the `cast` in front of a matmul operand. */
 int ma_cast_f32_bf16(const float* x, void* y, int64_t n, ma_stream_t stream);
 
@@ -823,6 +859,15 @@ int ma_mha_small_bwd_bf16(const void* q, int64_t ldq, const void* k, int64_t ldk
                           const float* probs, const void* ctx, int64_t ldc, const void* dctx, int64_t lddc, int64_t batch,
                           int32_t Lq, int32_t Lk, int32_t heads, int32_t d_k, float scale, void* dq, int64_t lddq, void* dk,
                           int64_t lddk, void* dv, int64_t lddv, ma_stream_t stream);
+
+/* ma_mha_small_fwd_bf16 for `batch` query rows groups that share keys: query batch b reads the keys, values and the (batch, 1, Lk)
+ * mask (mask_mode 1) of batch b / kv_group - k, v (batch / kv_group * Lk, ...), mask (batch / kv_group, 1, Lk); a (batch, Lq, Lk)
+ * mask (mode 2) stays per query batch.  The attention rescoring's source attention: beam hypotheses against one encoder output
+ * without repeating it.  batch % kv_group == 0; kv_group == 1 is ma_mha_small_fwd_bf16, bit for bit. */
+int ma_mha_small_fwd_grouped_bf16(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv,
+                                  const float* mask, int32_t mask_mode, int64_t batch, int32_t Lq, int32_t Lk, int32_t heads,
+                                  int32_t d_k, float scale, int32_t kv_group, void* ctx, int64_t ldc, float* probs,
+                                  ma_stream_t stream);
 
 /* The same on float32 activations (the float32 validation mode of the hybrid loss; always the un-staged form). */
 int ma_mha_small_fwd_x32(const float* q, int64_t ldq, const float* k, int64_t ldk, const float* v, int64_t ldv, const float* mask,

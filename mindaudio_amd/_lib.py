@@ -164,6 +164,10 @@ PROTOTYPES = {
     "ma_ctc_loss_grad_f32": (ctypes.c_int, [vp, i64, i64, i64, i32, vp, i32, vp, vp, i32, i32, f32, vp, vp, vp, vp, i64,
                                             vp, i64, vp]),
     "ma_ctc_greedy_search_f32": (ctypes.c_int, [vp, i64, i64, i64, i32, vp, i32, vp, vp, vp, vp, vp]),
+    "ma_ctc_topk_f32": (ctypes.c_int, [vp, i64, i64, i32, i32, vp, vp, vp]),
+    "ma_ctc_prefix_beam_search_f32": (ctypes.c_int, [vp, vp, vp, i64, i32, i32, i32, vp, vp, vp, vp, vp]),
+    "ma_hyp_score_f32": (ctypes.c_int, [vp, i64, i32, i64, i32, i32, vp, i64, vp, vp, i32, vp, ctypes.c_double, vp, vp, vp, vp,
+                                        vp]),
     "ma_cast_f32_bf16": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, i64, ctypes.c_void_p]),
     "ma_ecapa_pack_input_bf16": (ctypes.c_int, [vp, i64, i64, i32, i32, i32, vp, vp]),
     "ma_add_bf16": (ctypes.c_int, [vp, i64, vp, i64, vp, i64, i64, i64, vp]),
@@ -271,6 +275,8 @@ PROTOTYPES = {
                                              vp, i64, vp, i64, vp, i64, vp]),
     "ma_label_smoothing_loss_grad_len_f32": (ctypes.c_int, [vp, i64, i64, i32, vp, vp, f32, f32, vp, vp, i64, vp, vp, vp]),
     "ma_label_smoothing_loss_grad_len_x32": (ctypes.c_int, [vp, i64, i64, i32, vp, vp, f32, f32, vp, vp, i64, vp, vp, vp]),
+    "ma_mha_small_fwd_grouped_bf16": (ctypes.c_int, [vp, i64, vp, i64, vp, i64, vp, i32, i64, i32, i32, i32, i32, f32, i32, vp,
+                                                     i64, vp, vp]),
     "ma_mha_small_fwd_x32": (ctypes.c_int, [vp, i64, vp, i64, vp, i64, vp, i32, i64, i32, i32, i32, i32, f32, vp, i64, vp, vp]),
     "ma_mha_small_bwd_x32": (ctypes.c_int, [vp, i64, vp, i64, vp, i64, vp, vp, i64, vp, i64, i64, i32, i32, i32, i32, f32,
                                             vp, i64, vp, i64, vp, i64, vp]),

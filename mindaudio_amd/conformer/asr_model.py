@@ -178,3 +178,104 @@ def ctc_greedy_search(model, xs_pad, xs_masks, xs_lengths=None):
     lens = hyp_len.cpu().tolist()
     rows = hyp.cpu().tolist()
     return [r[:n] for r, n in zip(rows, lens)], logp.max(1).values
+
+
+class CTCPrefixBeamSearch(nn.Module):
+    """CTC prefix beam search net (models/decoders/decoder_factory.py:195-239): forward(xs_pad, xs_masks, xs_lengths) ->
+    (encoder_out (B, T', d), encoder_mask (B, 1, T'), top-k log-probabilities (B, T', beam) float32, top-k indices (B, T', beam)
+    int32) - TopK(log_softmax(ctc logits), beam_size) on ma_ctc_topk_f32.  `xs_masks` is the un-subsampled (B, 1, T) pad mask."""
+
+    def __init__(self, backbone, beam_size, pretrained_model=False):
+        super().__init__()
+        if pretrained_model:
+            raise NotImplementedError("wav2vec front ends are outside the built path")
+        self.backbone, self.beam_size = backbone, int(beam_size)
+
+    @torch.no_grad()
+    def forward(self, xs_pad, xs_masks, xs_lengths=None):
+        sub = xs_masks[:, :, :-2:2][:, :, :-2:2].contiguous()
+        enc, enc_mask = self.backbone.encoder(xs_pad, sub, sub)
+        b, t2, _ = enc.shape
+        logits = self.backbone.ctc.logits(enc)
+        logp, index = ops.ctc_topk(logits, logits.shape[1], self.beam_size)
+        return enc, enc_mask, logp.view(b, t2, self.beam_size), index.view(b, t2, self.beam_size)
+
+
+class AttentionRescoring(nn.Module):
+    """Attention rescoring net (decoder_factory.py:242-275): forward(encoder_out (B, T', d), encoder_mask (B, 1, T'), hyps_in_pad
+    (B*group, L), hyps_masks (B*group, L, L), group) -> the decoder's scores (B*group, L, V) float32 before the log_softmax, which
+    ma_hyp_score_f32 takes row by row.  The B encoder outputs are not repeated (TransformerDecoder.score_hypotheses)."""
+
+    def __init__(self, backbone, beam_size, pretrained_models=False):
+        super().__init__()
+        if pretrained_models:
+            raise NotImplementedError("wav2vec front ends are outside the built path")
+        if getattr(backbone, "decoder", None) is None:
+            raise NotImplementedError("attention rescoring needs the attention decoder (model_conf.ctc_weight < 1.0)")
+        self.backbone, self.beam_size = backbone, int(beam_size)
+
+    @torch.no_grad()
+    def forward(self, encoder_out, encoder_mask, hyps_in_pad, hyps_masks, group=None):
+        return self.backbone.decoder.score_hypotheses(encoder_out, encoder_mask, hyps_in_pad, hyps_masks,
+                                                      self.beam_size if group is None else group)
+
+
+def decoder_input(hyp, hyp_len, sos, eos, L1=None):
+    """The rescoring decoder's input (utils/recognize.py:370-385): add_sos_eos, pad_sequence with eos, and the (n, L1, L1) mask
+    ~make_pad_mask(len + 1) & subsequent_mask.  hyp (n, >= L1 - 1) int32 tokens, hyp_len (n,) -> (hyps_in_pad (n, L1) int32,
+    hyps_masks (n, L1, L1) float32).  L1 defaults to the longest hypothesis + 1 instead of the reference's max_tgt_len + 1 = 31: the
+    decoder is causal and the padding is masked, so the positions that count are the same (and hypotheses of more than 30 tokens fit)."""
+    lens = hyp_len.to(torch.int64).reshape(-1)
+    n = lens.numel()
+    if L1 is None:
+        L1 = int(lens.max()) + 1 if n else 1
+    pos = torch.arange(L1, device=hyp.device)
+    ys = torch.full((n, L1), int(eos), dtype=torch.int32, device=hyp.device)
+    ys[:, 0] = int(sos)
+    if L1 > 1:
+        ys[:, 1:] = torch.where(pos[None, 1:] <= lens[:, None], hyp[:, :L1 - 1].to(torch.int32), ys[:, 1:])
+    valid = pos[None, :] < (lens + 1)[:, None]
+    sub = torch.tril(torch.ones((L1, L1), dtype=torch.bool, device=hyp.device))
+    return ys, (valid[:, None, :] & sub[None]).to(torch.float32)
+
+
+def _prefix_search(model, xs_pad, xs_masks):
+    enc, enc_mask, logp, index = model(xs_pad, xs_masks)
+    b, t2, beam = logp.shape
+    mask = enc_mask.reshape(-1).to(torch.float32).contiguous()
+    hyp, hyp_len, score, n_hyp = ops.ctc_prefix_beam_search(logp.reshape(b * t2, beam), index.reshape(b * t2, beam), b, t2, beam,
+                                                            mask=mask)
+    return enc, enc_mask, hyp, hyp_len, score, n_hyp
+
+
+def ctc_prefix_beam_search(model, xs_pad, xs_masks, beam_size, xs_lengths=None):
+    """utils/recognize.py:273-336 for a batch of B >= 1 (the reference asserts B == 1): model is a CTCPrefixBeamSearch of that
+    beam size -> (hyps: per utterance the list of (prefix tuple, score) best first - fewer than beam_size when fewer survive,
+    encoder_out (B, T', d), encoder_mask (B, 1, T')).  Every utterance's result is what a one-utterance call gives."""
+    if model.beam_size != int(beam_size):
+        raise ValueError("the search net was built for beam %d, not %d" % (model.beam_size, beam_size))
+    enc, enc_mask, hyp, hyp_len, score, n_hyp = _prefix_search(model, xs_pad, xs_masks)
+    hyp, lens, score, n_hyp = hyp.cpu().tolist(), hyp_len.cpu().tolist(), score.cpu().tolist(), n_hyp.cpu().tolist()
+    out = [[(tuple(hyp[u][p][:lens[u][p]]), score[u][p]) for p in range(n_hyp[u])] for u in range(len(n_hyp))]
+    return out, enc, enc_mask
+
+
+def attention_rescoring(model_ctc, model_rescore, xs_pad, xs_masks, xs_lengths, sos, eos, beam_size, ctc_weight):
+    """utils/recognize.py:339-406 for a batch of B >= 1: the encoder runs once, the prefix search gives up to beam_size hypotheses
+    per utterance, the decoder scores all B * beam_size of them against the B encoder outputs, and each utterance keeps the first
+    hypothesis with the highest sum of decoder log-probabilities (+ eos) + ctc_weight * CTC score -> (per utterance the best prefix as
+    a list of tokens, per utterance its score)."""
+    if model_ctc.beam_size != int(beam_size):
+        raise ValueError("the search net was built for beam %d, not %d" % (model_ctc.beam_size, beam_size))
+    enc, enc_mask, hyp, hyp_len, score, n_hyp = _prefix_search(model_ctc, xs_pad, xs_masks)
+    b, beam, t2 = hyp.shape
+    hyp2, lens = hyp.reshape(b * beam, t2), hyp_len.reshape(-1)
+    ys, masks = decoder_input(hyp2, lens, sos, eos)
+    l1 = ys.shape[1]
+    scores = model_rescore(enc, enc_mask, ys, masks, beam)
+    v = scores.shape[2]
+    _, best, best_score = ops.hyp_score(scores.reshape(b * beam * l1, v), v, b, beam, l1, hyp2, lens, eos, score.reshape(-1),
+                                        ctc_weight, n_hyp)
+    best, best_score = best.cpu().tolist(), best_score.cpu().tolist()
+    hyp_h, lens_h = hyp.cpu(), hyp_len.cpu()
+    return [hyp_h[u, best[u], :int(lens_h[u, best[u]])].tolist() for u in range(b)], best_score

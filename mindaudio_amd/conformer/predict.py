@@ -1,12 +1,17 @@
 """`python -m mindaudio_amd.conformer.predict --config_path conformer.yaml` — the counterpart of examples/conformer/predict.py for
-decode_mode `ctc_greedy_search` (greedy CTC search + CER is the one external pin on the whole model, readme.md:126).
+decode_mode `ctc_greedy_search` (greedy CTC search + CER is the one external pin on the whole model, readme.md:126),
+`ctc_prefix_beam_search` (the best prefix of the CTC prefix beam search) and `attention_rescoring` (the prefix search's hypotheses
+rescored by the attention decoder, the mode of the reference's best CER).
 
 Same yaml keys (test_data, dict, exp_name, decode_ckpt, decode_mode, dataset_conf, collate_conf), same per-utterance flow
 (create_asr_predict_dataset, dataset.py:750-908: utterances outside the frame / token limits are dropped, one utterance per step,
 Kaldi fbank of the waveform x 2^15, zero-padded to its frame bucket, mask of the real frames), the same id -> character rule
 (predict.py:146-154: `w += 2`, stop at eos, ids past the dictionary skipped) and the same outputs: `<exp_name>/test_<mode>/result.txt`
-with "<uttid> <text>" lines, one "cer" log line per utterance, "cer_average" at the end.  The other decode modes of the reference
-(attention beam search, CTC prefix beam search, attention rescoring) are host-side searches this round does not build: they raise."""
+with "<uttid> <text>" lines, one "cer" log line per utterance, "cer_average" at the end.  The two beam modes take the yaml's top-level
+`beam_size` (default 10) and, for the rescoring, the decode section's top-level `ctc_weight` (default 0.0; not model_conf.ctc_weight);
+both searches run on the GPU (ma_ctc_topk_f32, ma_ctc_prefix_beam_search_f32, ma_hyp_score_f32).  `attention_rescoring` needs the
+attention decoder: a pure-CTC model (model_conf.ctc_weight 1.0) raises NotImplementedError, and so does the autoregressive
+`attention` mode, which is not built."""
 import argparse
 import os
 
@@ -61,19 +66,27 @@ def ids_to_text(hyp, eos, char_dict):
 
 
 def predict(config, device=None, log=print, model=None):
-    """Runs the greedy decode over config["test_data"]; returns (mean CER, [(uttid, text, cer)])."""
+    """Runs the decode of config["decode_mode"] over config["test_data"]; returns (mean CER, [(uttid, text, cer)])."""
     import numpy as np
     import torch
 
     from ..data.io import read
     from ..metric import wer
-    from .asr_model import CTCGreedySearch, ctc_greedy_search
+    from .asr_model import (AttentionRescoring, CTCGreedySearch, CTCPrefixBeamSearch, attention_rescoring, ctc_greedy_search,
+                            ctc_prefix_beam_search)
     from .dataset import compute_fbank_feats_batch
 
     mode = config.get("decode_mode", "ctc_greedy_search")
-    if mode != "ctc_greedy_search":
-        raise NotImplementedError("decode_mode %r: only ctc_greedy_search is built (the reference's attention / prefix-beam / rescoring "
-                                  "searches are host-side loops around the same encoder and decoder calls)" % mode)
+    if mode not in ("ctc_greedy_search", "ctc_prefix_beam_search", "attention_rescoring"):
+        raise NotImplementedError("decode_mode %r: ctc_greedy_search, ctc_prefix_beam_search and attention_rescoring are built (the "
+                                  "autoregressive attention search is not)" % mode)
+    if mode == "attention_rescoring":
+        has_decoder = getattr(model, "decoder", None) is not None if model is not None else \
+            float((config.get("model_conf") or {}).get("ctc_weight", 0.3)) != 1.0
+        if not has_decoder:
+            raise NotImplementedError("attention_rescoring needs the attention decoder; this model is pure CTC (ctc_weight 1.0)")
+    beam_size = int(config.get("beam_size", 10))
+    ctc_weight = float(config.get("ctc_weight", 0.0))
     if device is None:
         device = torch.device("cuda", torch.cuda.current_device())
     sos, eos, vocab_size, char_dict = load_language_dict(config["dict"])
@@ -89,7 +102,11 @@ def predict(config, device=None, log=print, model=None):
         load_mindspore_checkpoint(model, ckpt, strict=False)
         log("Successfully loading the asr model: %s" % ckpt)
     model.eval()
-    net = CTCGreedySearch(model)
+    if mode == "ctc_greedy_search":
+        net = CTCGreedySearch(model)
+    else:
+        net = CTCPrefixBeamSearch(model, beam_size)
+        rescore = AttentionRescoring(model, beam_size) if mode == "attention_rescoring" else None
     decode_dir = os.path.join(str(config.get("exp_name", "default")), "test_" + mode)
     os.makedirs(decode_dir, exist_ok=True)
     log("Total predict samples size: %d" % len(samples))
@@ -106,7 +123,13 @@ def predict(config, device=None, log=print, model=None):
             xs[0, :n] = feats[0, :n]
             masks = torch.zeros((1, 1, pad), dtype=torch.float32, device=device)
             masks[0, 0, :n] = 1
-            hyps, _ = ctc_greedy_search(net, xs, masks, None)
+            if mode == "ctc_greedy_search":
+                hyps, _ = ctc_greedy_search(net, xs, masks, None)
+            elif mode == "ctc_prefix_beam_search":
+                beams, _, _ = ctc_prefix_beam_search(net, xs, masks, beam_size, None)
+                hyps = [list(beams[0][0][0])]
+            else:
+                hyps, _ = attention_rescoring(net, rescore, xs, masks, None, sos, eos, beam_size, ctc_weight)
             content = ids_to_text(hyps[0], eos, char_dict)
             truth = [char_dict[w + 2] for w in tokens]
             log("Labs (%d/%d): %s %s" % (count, len(samples), uttid, "".join(str(c) for c in truth)))
@@ -134,6 +157,8 @@ def main(argv=None):
     ap.add_argument("--exp_name")
     ap.add_argument("--decode_ckpt")
     ap.add_argument("--decode_mode")
+    ap.add_argument("--beam_size", type=int)
+    ap.add_argument("--ctc_weight", type=float)
     a = ap.parse_args(argv)
     over = {k: v for k, v in vars(a).items() if k != "config_path" and v is not None}
     predict(load_config(a.config_path, over))

@@ -7,6 +7,7 @@
 //   mha_small fwd/bwd         softmax(q k^T / d_k + mask) v for 32 queries (a launch; longer labels: one launch per tile) x <= 256 keys per (batch, head); scores are
 //                             q*s . k*s with s = 1/sqrt(d_k), i.e. divided by d_k (attention.py:150-152); additive -10000
 //                             mask of shape (B, 1, Lk) or (B, Lq, Lk); probabilities are kept for the backward pass
+//                             (forward, grouped: query batch b reads the keys / values / (B, 1, Lk) mask of batch b / kvg)
 //   label_smoothing           KL(true_dist || softmax) summed over unmasked tokens / batch + its gradient + accuracy
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -192,6 +193,9 @@ struct SmallAttn {
   // round 6: labels longer than one 32-query tile - a launch covers rows q0 .. q0 + Lq - 1 of the LqT rows a batch element has;
   // acc: dk / dv of this launch are added to what the earlier query tiles stored (backward only)
   int q0, LqT, acc;
+  // forward only: query batch b reads the keys, values and (B, 1, Lk) mask of batch b / kvg (attention rescoring: beam hypotheses
+  // against one encoder output); 1 everywhere else
+  int kvg;
 };
 
 // out[q][16 w + c] (q < Lq, bf16) = sum_j S[q][j] X[j][16 w + c] for the 32 query rows of a (batch, head) on the matrix cores (round 4;
@@ -257,7 +261,7 @@ __global__ __launch_bounds__(256) void mha_small_fwd_kernel(const SmallAttn<AT> 
   // (query rows of 64 + 4 floats: 16-byte aligned, read as float4 - with single-float reads the score loop was 2000 LDS
   // instructions per thread, 27 of the launch's 45 us)
   float (*Qs)[kSmD + 4] = reinterpret_cast<float (*)[kSmD + 4]>(S + kSmQ * ss);
-  const int h = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
+  const int h = blockIdx.x, b = blockIdx.y, tid = threadIdx.x, kb = b / p.kvg;
   const int Lq = p.Lq, Lk = p.Lk;
   for (int i = tid; i < kSmQ * (kSmD / 8); i += 256) {  // 16-byte pieces (round 4; single elements before)
     const int qi = i / (kSmD / 8), ch = i % (kSmD / 8);
@@ -270,13 +274,13 @@ __global__ __launch_bounds__(256) void mha_small_fwd_kernel(const SmallAttn<AT> 
     for (int i = tid; i < kcap * (kSmD / 8); i += 256) {
       const int kj = i / (kSmD / 8), ch = i % (kSmD / 8);
       uint4 val = make_uint4(0, 0, 0, 0);
-      if (kj < Lk) val = *reinterpret_cast<const uint4*>(p.v + ((int64_t)b * Lk + kj) * p.ldv + h * kSmD + ch * 8);
+      if (kj < Lk) val = *reinterpret_cast<const uint4*>(p.v + ((int64_t)kb * Lk + kj) * p.ldv + h * kSmD + ch * 8);
       *reinterpret_cast<uint4*>(&Vs[kj][ch * 8]) = val;
     }
   __syncthreads();
   for (int j = tid; j < Lk; j += 256) {
     float kr[kSmD];
-    const AT* kp = p.k + ((int64_t)b * Lk + j) * p.ldk + h * kSmD;
+    const AT* kp = p.k + ((int64_t)kb * Lk + j) * p.ldk + h * kSmD;
 #pragma unroll
     for (int c8 = 0; c8 < kSmD / 8; ++c8) {
       float t8[8];
@@ -296,7 +300,7 @@ __global__ __launch_bounds__(256) void mha_small_fwd_kernel(const SmallAttn<AT> 
       }
       float s = (s0 + s1) + (s2 + s3);
       s *= p.scale;
-      if (p.mask_mode == 1 && p.mask[(int64_t)b * Lk + j] == 0.0f) s += -10000.0f;
+      if (p.mask_mode == 1 && p.mask[(int64_t)kb * Lk + j] == 0.0f) s += -10000.0f;
       if (p.mask_mode == 2 && p.mask[((int64_t)b * p.LqT + p.q0 + i) * Lk + j] == 0.0f) s += -10000.0f;
       S[i * ss + j] = s;
     }
@@ -335,7 +339,7 @@ __global__ __launch_bounds__(256) void mha_small_fwd_kernel(const SmallAttn<AT> 
       for (int jj = 0; jj < Lk; ++jj) {
         const float pv = S[qi * ss + jj];
         float t8[8];
-        d_ld8(p.v + ((int64_t)b * Lk + jj) * p.ldv + h * kSmD + dg, t8);
+        d_ld8(p.v + ((int64_t)kb * Lk + jj) * p.ldv + h * kSmD + dg, t8);
 #pragma unroll
         for (int e = 0; e < 8; ++e) acc[e] = fmaf(pv, t8[e], acc[e]);
       }
@@ -496,7 +500,7 @@ __global__ __launch_bounds__(256) void mha_small_fwd_mfma_kernel(const SmallAttn
   uint16_t (*Vs)[kSmD] = reinterpret_cast<uint16_t (*)[kSmD]>(sm_lds);
   float* S = reinterpret_cast<float*>(sm_lds + kcap * kSmD * 2);
   uint16_t* Qb = reinterpret_cast<uint16_t*>(S + kSmQ * ss);
-  const int h = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
+  const int h = blockIdx.x, b = blockIdx.y, tid = threadIdx.x, kb = b / p.kvg;
   const int lane = tid & 63, wave = tid >> 6, lq = lane & 15, lg = lane >> 4;
   const int Lq = p.Lq, Lk = p.Lk;
   // Staging with every load of a chunk in flight before the first LDS store (round 6).  As plain loops (one 16-byte load per thread
@@ -508,7 +512,7 @@ __global__ __launch_bounds__(256) void mha_small_fwd_mfma_kernel(const SmallAttn
 #pragma unroll
   for (int i = 0; i < kKf; ++i) {
     const int key = (wave + 4 * i) * 16 + lq, keyc = key < Lk ? key : Lk - 1;
-    const uint16_t* kp = p.k + ((int64_t)b * Lk + keyc) * p.ldk + h * kSmD + lg * 8;
+    const uint16_t* kp = p.k + ((int64_t)kb * Lk + keyc) * p.ldk + h * kSmD + lg * 8;
     kfr[i][0] = *reinterpret_cast<const sm_bf16x8*>(kp);
     kfr[i][1] = *reinterpret_cast<const sm_bf16x8*>(kp + 32);
   }
@@ -524,7 +528,7 @@ __global__ __launch_bounds__(256) void mha_small_fwd_mfma_kernel(const SmallAttn
         const int iv = base + u * 256, kj = iv / (kSmD / 8), cv = iv % (kSmD / 8);
         val[u] = make_uint4(0, 0, 0, 0);
         if (iv < kcap * (kSmD / 8) && kj < Lk)
-          val[u] = *reinterpret_cast<const uint4*>(p.v + ((int64_t)b * Lk + kj) * p.ldv + h * kSmD + cv * 8);
+          val[u] = *reinterpret_cast<const uint4*>(p.v + ((int64_t)kb * Lk + kj) * p.ldv + h * kSmD + cv * 8);
       }
 #pragma unroll
       for (int u = 0; u < kCh; ++u) {
@@ -549,14 +553,14 @@ __global__ __launch_bounds__(256) void mha_small_fwd_mfma_kernel(const SmallAttn
           kf1 = kfr[i][1];
         }
     } else {
-      const uint16_t* kp = p.k + ((int64_t)b * Lk + keyc) * p.ldk + h * kSmD + lg * 8;
+      const uint16_t* kp = p.k + ((int64_t)kb * Lk + keyc) * p.ldk + h * kSmD + lg * 8;
       kf0 = *reinterpret_cast<const sm_bf16x8*>(kp);
       kf1 = *reinterpret_cast<const sm_bf16x8*>(kp + 32);
     }
     // the tile's mask values: unconditional loads (clamped indices), all in flight under the MFMAs - behind `if (q < Lq)` /
     // `continue` each of them was a round trip of its own (eight per tile with the (B, Lq, Lk) label mask)
     float mk1 = 1.0f, mk2[2][4];
-    if (p.mask_mode == 1) mk1 = p.mask[(int64_t)b * Lk + keyc];
+    if (p.mask_mode == 1) mk1 = p.mask[(int64_t)kb * Lk + keyc];
     if (p.mask_mode == 2) {
 #pragma unroll
       for (int qt = 0; qt < 2; ++qt)
@@ -928,17 +932,20 @@ static int fill_small(SmallAttn<AT>& a, const void* q, int64_t ldq, const void* 
   a.mask = mask; a.mask_mode = mask_mode;
   a.Lq = Lq; a.Lk = Lk; a.H = heads; a.scale = scale;
   a.q0 = 0; a.LqT = Lq; a.acc = 0;  // (the launchers walk query tiles of kSmQ rows)
+  a.kvg = 1;
   return MA_OK;
 }
 
 template <typename AT>
 static int mha_small_fwd(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv, const float* mask,
                          int32_t mask_mode, int64_t batch, int32_t Lq, int32_t Lk, int32_t heads, int32_t d_k, float scale, void* ctx,
-                         int64_t ldc, float* probs, ma_stream_t stream) {
+                         int64_t ldc, float* probs, ma_stream_t stream, int32_t kv_group = 1) {
   SmallAttn<AT> a;
   const int rc = fill_small(a, q, ldq, k, ldk, v, ldv, mask, mask_mode, batch, Lq, Lk, heads, d_k, scale);
   if (rc != MA_OK) return rc;
   if (!ctx || !probs || (ldc & 7)) return MA_ERR_INVALID_ARG;
+  if (kv_group < 1 || batch % kv_group) return MA_ERR_INVALID_ARG;
+  a.kvg = kv_group;
   MA_LDS_ATTR_T((mha_small_fwd_kernel<false, AT>), 163840);
   // query tiles of kSmQ rows: one launch each (labels of more than 31 tokens - AISHELL's longest transcripts - take two or more)
   for (int q0 = 0; q0 < Lq; q0 += kSmQ) {
@@ -1008,6 +1015,13 @@ int ma_mha_small_fwd_bf16(const void* q, int64_t ldq, const void* k, int64_t ldk
                           const float* mask, int32_t mask_mode, int64_t batch, int32_t Lq, int32_t Lk, int32_t heads,
                           int32_t d_k, float scale, void* ctx, int64_t ldc, float* probs, ma_stream_t stream) {
   return mha_small_fwd<uint16_t>(q, ldq, k, ldk, v, ldv, mask, mask_mode, batch, Lq, Lk, heads, d_k, scale, ctx, ldc, probs, stream);
+}
+int ma_mha_small_fwd_grouped_bf16(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv,
+                                  const float* mask, int32_t mask_mode, int64_t batch, int32_t Lq, int32_t Lk, int32_t heads,
+                                  int32_t d_k, float scale, int32_t kv_group, void* ctx, int64_t ldc, float* probs,
+                                  ma_stream_t stream) {
+  return mha_small_fwd<uint16_t>(q, ldq, k, ldk, v, ldv, mask, mask_mode, batch, Lq, Lk, heads, d_k, scale, ctx, ldc, probs, stream,
+                                 kv_group);
 }
 int ma_mha_small_fwd_x32(const float* q, int64_t ldq, const float* k, int64_t ldk, const float* v, int64_t ldv, const float* mask,
                          int32_t mask_mode, int64_t batch, int32_t Lq, int32_t Lk, int32_t heads, int32_t d_k, float scale, float* ctx,

@@ -94,6 +94,20 @@ class TransformerDecoder(nn.Module):
         (B, 1, T'), ys_in_pad (B, L) token ids, ys_masks (B, L, L) -> (scores before softmax (B, L, V) float32, tensor0).
         Pre-norm layers with eps 1e-12 (models/conformer.py:417-419, 548); both attentions scale q AND k by 1/sqrt(d_k)
         (layers/attention.py:150-152), i.e. scores / d_k."""
+        return self._decode(memory, memory_mask, ys_in_pad, ys_masks, 1), torch.zeros(1, device=memory.device)
+
+    @torch.no_grad()
+    def score_hypotheses(self, memory, memory_mask, ys_in_pad, ys_masks, group):
+        """The evaluation decoder over B * group hypotheses against B encoder outputs without repeating them (attention rescoring;
+        utils/recognize.py:387-391 repeats encoder_out beam times): hypotheses u * group .. u * group + group - 1 belong to
+        utterance u.  memory (B, T', d), memory_mask (B, 1, T'), ys_in_pad (B*group, L), ys_masks (B*group, L, L) -> scores before
+        softmax (B*group, L, V) float32, a view of the 64-padded row buffer.  The source attention's K / V rows are computed once
+        per utterance and read by all of its hypotheses (ma_mha_small_fwd_grouped_bf16)."""
+        if ys_in_pad.shape[0] != memory.shape[0] * group:
+            raise ValueError("ys_in_pad holds %d hypotheses, not %d x %d" % (ys_in_pad.shape[0], memory.shape[0], group))
+        return self._decode(memory, memory_mask, ys_in_pad, ys_masks, int(group))
+
+    def _decode(self, memory, memory_mask, ys_in_pad, ys_masks, group):
         from ..train import kernels as K
 
         if self.training:
@@ -102,12 +116,13 @@ class TransformerDecoder(nn.Module):
             self.prepare()
         P = self._prepared
         f32 = torch.float32
-        b, t2, d = memory.shape
+        bm, t2, d = memory.shape
+        b = bm * group
         L1 = ys_in_pad.shape[1]
         dk = d // self.heads
         scale, eps = 1.0 / dk, 1e-12
-        mem_bf = ops.cast_bf16(memory.reshape(b * t2, d).to(f32).contiguous())
-        emask = memory_mask.reshape(b, t2).to(f32).contiguous()
+        mem_bf = ops.cast_bf16(memory.reshape(bm * t2, d).to(f32).contiguous())
+        emask = memory_mask.reshape(bm, t2).to(f32).contiguous()
         sub = ys_masks.to(f32).contiguous()
         toks = ys_in_pad.to(torch.int32).contiguous().reshape(-1)
         pe = self.pe[:L1].to(f32).contiguous()
@@ -120,7 +135,10 @@ class TransformerDecoder(nn.Module):
             a = ops.layernorm(x, l.norm2.gamma, l.norm2.beta, eps=eps)
             q = ops.gemm(a, W["ca_q_w"], bias=W["ca_q_b"])
             kv = ops.gemm(mem_bf, W["ca_kv_w"], bias=W["ca_kv_b"])
-            ctx, _ = K.mha_small_fwd(q, kv[:, :d], kv[:, d:], emask, 1, b, L1, t2, scale, self.heads, dk)
+            if group == 1:
+                ctx, _ = K.mha_small_fwd(q, kv[:, :d], kv[:, d:], emask, 1, b, L1, t2, scale, self.heads, dk)
+            else:  # (K / V of the B encoder outputs, read by the group's hypotheses)
+                ctx, _ = K.mha_small_fwd_grouped(q, kv[:, :d], kv[:, d:], emask, 1, b, L1, t2, scale, group, self.heads, dk)
             ops.gemm(ctx, W["ca_o_w"], bias=W["ca_o_b"], residual=x, out_dtype=f32, out=x)
             a = ops.layernorm(x, l.norm3.gamma, l.norm3.beta, eps=eps)
             h = ops.gemm(a, W["ff_w1"], bias=W["ff_b1"], act=_lib.ACT_RELU)
@@ -129,4 +147,4 @@ class TransformerDecoder(nn.Module):
         vp = P["out_b"].numel()
         logits = torch.empty((b * L1, vp), dtype=f32, device=memory.device)
         ops.gemm(y, P["out_w"], bias=P["out_b"], out_dtype=f32, out=logits[:, :self.vocab_size])
-        return logits[:, :self.vocab_size].view(b, L1, self.vocab_size), torch.zeros(1, device=memory.device)
+        return logits[:, :self.vocab_size].view(b, L1, self.vocab_size)

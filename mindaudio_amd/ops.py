@@ -492,3 +492,60 @@ def ctc_greedy_search(logits, batch, T, V, mask=None, blank=0):
                                       _host.ptr(logp), _host.ptr(hyp), _host.ptr(hyp_len), _host.current_stream_ptr())
     _lib.check(rc, "ctc_greedy_search")
     return best, logp, hyp, hyp_len
+
+
+def ctc_topk(logits, V, k):
+    """logits (rows, ld >= V) float32 -> (topk_logp (rows, k) float32, topk_index (rows, k) int32): the k largest values of
+    log_softmax(row), descending, equal values lower index first (k <= 16)."""
+    t = _host.torch()
+    assert logits.dtype == t.float32 and logits.dim() == 2 and logits.stride(1) == 1
+    rows = logits.shape[0]
+    logp = t.empty((rows, k), dtype=t.float32, device=logits.device)
+    index = t.empty((rows, k), dtype=t.int32, device=logits.device)
+    rc = _lib.load().ma_ctc_topk_f32(_host.ptr(logits), logits.stride(0), rows, V, k, _host.ptr(logp), _host.ptr(index),
+                                     _host.current_stream_ptr())
+    _lib.check(rc, "ctc_topk")
+    return logp, index
+
+
+def ctc_prefix_beam_search(topk_logp, topk_index, batch, T, beam, mask=None, blank=0):
+    """CTC prefix beam search of a batch (utils/recognize.py:273-336): topk_logp / topk_index (batch*T, beam) from ctc_topk with
+    k = beam, mask (batch*T) float32 or None -> (hyp (batch, beam, T) int32, hyp_len (batch, beam) int32, score (batch, beam)
+    float64, n_hyp (batch,) int32), hypotheses best first."""
+    t = _host.torch()
+    assert topk_logp.dtype == t.float32 and topk_index.dtype == t.int32 and topk_logp.is_contiguous() and topk_index.is_contiguous()
+    assert topk_logp.numel() == batch * T * beam and topk_index.numel() == batch * T * beam
+    if mask is not None:
+        assert mask.dtype == t.float32 and mask.is_contiguous() and mask.numel() == batch * T
+    dev = topk_logp.device
+    hyp = t.empty((batch, beam, T), dtype=t.int32, device=dev)
+    hyp_len = t.empty((batch, beam), dtype=t.int32, device=dev)
+    score = t.empty((batch, beam), dtype=t.float64, device=dev)
+    n_hyp = t.empty((batch,), dtype=t.int32, device=dev)
+    rc = _lib.load().ma_ctc_prefix_beam_search_f32(_host.ptr(topk_logp), _host.ptr(topk_index), _opt(mask), batch, T, beam, blank,
+                                                   _host.ptr(hyp), _host.ptr(hyp_len), _host.ptr(score), _host.ptr(n_hyp),
+                                                   _host.current_stream_ptr())
+    _lib.check(rc, "ctc_prefix_beam_search")
+    return hyp, hyp_len, score, n_hyp
+
+
+def hyp_score(logits, V, n_utt, group, L1, tokens, lens, eos, ctc_score, ctc_weight, n_hyp=None):
+    """The score loop of attention_rescoring (utils/recognize.py:393-406): logits (n_utt*group*L1, ld >= V) float32 decoder scores,
+    tokens (n_utt*group, >= L1 - 1) int32, lens (n_utt*group) int32, ctc_score (n_utt*group) float64, n_hyp (n_utt) int32 or None
+    -> (hyp_score (n_utt*group) float64, best_index (n_utt) int32, best_score (n_utt) float64)."""
+    t = _host.torch()
+    assert logits.dtype == t.float32 and logits.dim() == 2 and logits.stride(1) == 1 and logits.shape[0] == n_utt * group * L1
+    assert tokens.dtype == t.int32 and tokens.dim() == 2 and tokens.stride(1) == 1 and tokens.shape[0] == n_utt * group
+    assert lens.dtype == t.int32 and lens.is_contiguous() and ctc_score.dtype == t.float64 and ctc_score.is_contiguous()
+    if n_hyp is not None:
+        assert n_hyp.dtype == t.int32 and n_hyp.is_contiguous() and n_hyp.numel() == n_utt
+    dev = logits.device
+    ws = t.empty((n_utt * group * L1,), dtype=t.float64, device=dev)
+    scores = t.empty((n_utt * group,), dtype=t.float64, device=dev)
+    best = t.empty((n_utt,), dtype=t.int32, device=dev)
+    best_score = t.empty((n_utt,), dtype=t.float64, device=dev)
+    rc = _lib.load().ma_hyp_score_f32(_host.ptr(logits), logits.stride(0), V, n_utt, group, L1, _host.ptr(tokens), tokens.stride(0),
+                                      _host.ptr(lens), _opt(n_hyp), eos, _host.ptr(ctc_score), float(ctc_weight), _host.ptr(ws),
+                                      _host.ptr(scores), _host.ptr(best), _host.ptr(best_score), _host.current_stream_ptr())
+    _lib.check(rc, "hyp_score")
+    return scores, best, best_score

@@ -233,6 +233,18 @@ def mha_small_fwd(q, k, v, mask, mask_mode, batch, lq, lk, scale, heads=4, d_k=6
     return ctx, probs
 
 
+def mha_small_fwd_grouped(q, k, v, mask, mask_mode, batch, lq, lk, scale, kv_group, heads=4, d_k=64):
+    """mha_small_fwd where query batch b reads the keys / values / (B, 1, Lk) mask of batch b // kv_group: k, v
+    (B/kv_group*Lk, ...)."""
+    t = _t()
+    ctx = t.empty((batch * lq, heads * d_k), dtype=t.bfloat16, device=q.device)
+    probs = t.empty((batch, heads, lq, lk), dtype=t.float32, device=q.device)
+    _lib.check(_lib.load().ma_mha_small_fwd_grouped_bf16(_p(q), q.stride(0), _p(k), k.stride(0), _p(v), v.stride(0), _p(mask),
+                                                         mask_mode, batch, lq, lk, heads, d_k, float(scale), kv_group, _p(ctx),
+                                                         ctx.stride(0), _p(probs), _s()), "mha_small_fwd_grouped")
+    return ctx, probs
+
+
 def mha_small_bwd(q, k, v, probs, ctx, dctx, batch, lq, lk, scale, dq, dk, dv, heads=4, d_k=64):
     _lib.check(_lib.load().ma_mha_small_bwd_bf16(_p(q), q.stride(0), _p(k), k.stride(0), _p(v), v.stride(0), _p(probs),
                                                  _p(ctx), ctx.stride(0), _p(dctx), dctx.stride(0), batch, lq, lk, heads,
