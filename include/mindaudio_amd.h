@@ -1172,6 +1172,36 @@ int64_t ma_block_table_call_blob(const ma_block_table_t* table, int32_t backward
 int ma_conformer_block_fwd_train(ma_block_table_t* table, int32_t block, uint32_t seed, ma_stream_t stream);
 int ma_conformer_block_bwd_train(ma_block_table_t* table, int32_t block, uint32_t seed, ma_stream_t stream);
 
+/* ---- speaker verification scoring (examples/ECAPA-TDNN/speaker_verification_cosine.py: emb_mean, evaluate2) --------------------
+ * Embedding width D: a multiple of 32 up to 512, anything else MA_ERR_INVALID_ARG.  All launches are asynchronous on `stream`, none
+ * allocates, results are bit-identical from run to run (float64 sums in a fixed order, no floating-point atomics).
+ *   ma_cohort_stats_f32: mean[e] / std[e] (float64) = np.mean / np.std of the K largest cos(Q[e], C[n]) over n - the multiset
+ *     np.partition(s, kth=-K)[-K:] holds (K == N: all of them; K > N or K < 1: MA_ERR_INVALID_ARG).  Q (E, D), C (N, D) raw float32
+ *     rows, 16-byte aligned, ld % 4 == 0; a zero-norm row scores 0 against everything.  Scores are the exact-float32 MFMA product
+ *     scaled by float64 inverse norms and rounded to float32 once; the selection is an exact radix select on those float32 scores.
+ *     The workspace holds the norms and the score block of as many query rows as fit (at least one row: MA_ERR_WORKSPACE otherwise);
+ *     ma_cohort_stats_workspace_bytes(E, N) is the size for blocks of 512 rows.
+ *   ma_trial_scores_f32: score[t] (float64) = cos(emb[enrol_idx[t]], emb[test_idx[t]]), normalised with the per-embedding mean / std
+ *     of ma_cohort_stats_f32: MA_SCORE_NORM_Z (s - mean_e) / std_e, _T (s - mean_t) / std_t, _S the half-sum of the two, _NONE as is
+ *     (mean / std may then be NULL).  An index outside [0, n_emb) gives NaN.
+ *   ma_running_mean_sub_f32: Y[n] = X[n] - g_n, g_n = (1 - w) g_{n-1} + w X[n], w = 1 / (count + n + 1) (g_0 = X[0] when count == 0),
+ *     evaluated as the cumulative mean in float64; g_mean (D float64, device) is read as g_{-1} and left as g_{N-1}; the caller's
+ *     new count is count + N.  Y may alias X.
+ *   ma_sentence_mean_norm_f32: out[b, t, f] = x[b, t, f] - mean_t x[b, t, f]  (InputNormalization "sentence", std_norm=False). */
+#define MA_SCORE_NORM_NONE 0
+#define MA_SCORE_NORM_Z 1
+#define MA_SCORE_NORM_T 2
+#define MA_SCORE_NORM_S 3
+int64_t ma_cohort_stats_workspace_bytes(int64_t E, int64_t N);
+int ma_cohort_stats_f32(const float* Q, int64_t ldq, const float* C, int64_t ldc, int64_t E, int64_t N, int32_t D, int64_t K,
+                        double* mean, double* stdev, void* workspace, int64_t workspace_bytes, ma_stream_t stream);
+int ma_trial_scores_f32(const float* emb, int64_t ld, int64_t n_emb, int32_t D, const int32_t* enrol_idx, const int32_t* test_idx,
+                        int64_t T, const double* mean, const double* stdev, int32_t mode, double* score, ma_stream_t stream);
+int64_t ma_running_mean_sub_workspace_bytes(int64_t N, int32_t D);
+int ma_running_mean_sub_f32(const float* X, int64_t ldx, int64_t N, int32_t D, double* g_mean, int64_t count, float* Y, int64_t ldy,
+                            void* workspace, int64_t workspace_bytes, ma_stream_t stream);
+int ma_sentence_mean_norm_f32(const float* x, int64_t batch, int64_t T, int32_t F, float* out, ma_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

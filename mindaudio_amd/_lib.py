@@ -113,6 +113,7 @@ class GemmEpilogue(ctypes.Structure):
     ]
 
 
+SCORE_NORMS = {None: 0, "none": 0, "z-norm": 1, "t-norm": 2, "s-norm": 3}  # MA_SCORE_NORM_*
 ACT_NONE, ACT_SWISH, ACT_RELU, ACT_SIGMOID, ACT_TANH = 0, 1, 2, 3, 4
 
 # name -> (restype, argtypes); must list every symbol include/mindaudio_amd.h declares
@@ -347,6 +348,13 @@ PROTOTYPES = {
     "ma_convmid_bwd_x32": (ctypes.c_int, [vp, vp, i64, i64, i64, i32, vp, i32, vp, i64, vp, vp, vp, i64, vp]),
     "ma_ctc_loss_grad_x32": (ctypes.c_int, [vp, i64, i64, i64, i32, vp, i32, vp, vp, i32, i32, f32, vp, vp, vp, vp, i64, vp,
                                             i64, vp]),
+    # ---- speaker verification scoring ----
+    "ma_cohort_stats_workspace_bytes": (i64, [i64, i64]),
+    "ma_cohort_stats_f32": (ctypes.c_int, [vp, i64, vp, i64, i64, i64, i32, i64, vp, vp, vp, i64, vp]),
+    "ma_trial_scores_f32": (ctypes.c_int, [vp, i64, i64, i32, vp, vp, i64, vp, vp, i32, vp, vp]),
+    "ma_running_mean_sub_workspace_bytes": (i64, [i64, i32]),
+    "ma_running_mean_sub_f32": (ctypes.c_int, [vp, i64, i64, i32, vp, i64, vp, i64, vp, i64, vp]),
+    "ma_sentence_mean_norm_f32": (ctypes.c_int, [vp, i64, i64, i32, vp, vp]),
 }
 
 _lib = None

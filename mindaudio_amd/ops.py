@@ -549,3 +549,129 @@ def hyp_score(logits, V, n_utt, group, L1, tokens, lens, eos, ctc_score, ctc_wei
                                       _host.ptr(scores), _host.ptr(best), _host.ptr(best_score), _host.current_stream_ptr())
     _lib.check(rc, "hyp_score")
     return scores, best, best_score
+
+
+# ---- speaker verification scoring (csrc/verification.hip) ------------------------------------------------------------------------
+def _check_emb(x, what):
+    t = _host.torch()
+    if not isinstance(x, t.Tensor) or x.dim() != 2 or x.dtype != t.float32:
+        raise ValueError("%s must be a 2-D float32 tensor" % what)
+    if x.shape[0] < 1:
+        raise ValueError("%s has no rows" % what)
+    d = x.shape[1]
+    if d % 32 or not 32 <= d <= 512:
+        raise ValueError("%s: embedding width %d is not a multiple of 32 up to 512" % (what, d))
+    if x.stride(1) != 1 or x.stride(0) % 4 or x.data_ptr() % 16:
+        x = x.contiguous()
+    return x
+
+
+def cohort_stats(queries, cohort, k=None, block_rows=None):
+    """(mean, std): float64 (E,) tensors, np.mean / np.std of the `k` largest cos(queries[e], cohort[n]) over n - the values
+    np.partition(s, kth=-k)[-k:] holds (evaluate2 of the reference's speaker_verification_cosine.py).  k=None: the whole cohort.
+    queries (E, D), cohort (N, D): raw float32 device tensors, D a multiple of 32 up to 512.  block_rows: query rows scored per
+    pass (default: the library's 512-row recommendation)."""
+    t = _host.torch()
+    lib = _lib.load()
+    q, c = _check_emb(queries, "queries"), _check_emb(cohort, "cohort")
+    if q.shape[1] != c.shape[1]:
+        raise ValueError("queries and cohort differ in width: %d, %d" % (q.shape[1], c.shape[1]))
+    e, n = q.shape[0], c.shape[0]
+    k = n if k is None else int(k)
+    if k < 1 or k > n:
+        raise ValueError("kth(=%d) out of bounds (%d)" % (-k, n))  # what np.partition raises for cohort_size > N
+    nbytes = lib.ma_cohort_stats_workspace_bytes(e, n)
+    if nbytes < 0:
+        _lib.check(int(nbytes), "cohort_stats")
+    if block_rows is not None:
+        if block_rows < 1:
+            raise ValueError("block_rows must be positive")
+        row_bytes = (n + 3) // 4 * 16  # one query row of the score block
+        nbytes += (min(int(block_rows), e) - min(e, 512)) * row_bytes
+    ws = _host.workspace(nbytes, q.device)
+    mean = t.empty((e,), dtype=t.float64, device=q.device)
+    std = t.empty((e,), dtype=t.float64, device=q.device)
+    rc = lib.ma_cohort_stats_f32(_host.ptr(q), q.stride(0), _host.ptr(c), c.stride(0), e, n, q.shape[1], k, _host.ptr(mean),
+                                 _host.ptr(std), _host.ptr(ws), nbytes, _host.current_stream_ptr())
+    _lib.check(rc, "cohort_stats")
+    return mean, std
+
+
+def trial_scores(emb, enrol_idx, test_idx, mean=None, std=None, score_norm=None):
+    """float64 (T,) tensor: cos(emb[enrol_idx[t]], emb[test_idx[t]]), normalised as evaluate2 does with the per-embedding cohort
+    statistics of `cohort_stats`: score_norm None / "z-norm" / "t-norm" / "s-norm"."""
+    t = _host.torch()
+    lib = _lib.load()
+    if score_norm not in _lib.SCORE_NORMS:
+        raise ValueError("unknown score_norm %r (z-norm, t-norm, s-norm or None)" % (score_norm,))
+    mode = _lib.SCORE_NORMS[score_norm]
+    x = _check_emb(emb, "emb")
+    n = x.shape[0]
+    idx = []
+    for name, v in (("enrol_idx", enrol_idx), ("test_idx", test_idx)):
+        v = t.as_tensor(v)
+        if v.dim() != 1 or v.dtype in (t.float32, t.float64, t.bfloat16, t.float16, t.bool):
+            raise ValueError("%s must be a 1-D integer list" % name)
+        if v.numel() and (int(v.min()) < 0 or int(v.max()) >= n):
+            raise ValueError("%s holds an index outside [0, %d)" % (name, n))
+        idx.append(v.to(device=x.device, dtype=t.int32).contiguous())
+    if idx[0].numel() != idx[1].numel():
+        raise ValueError("enrol_idx and test_idx differ in length")
+    if mode:
+        if mean is None or std is None:
+            raise ValueError("score_norm %r needs the cohort mean and std" % (score_norm,))
+        for name, v in (("mean", mean), ("std", std)):
+            if v.dtype != t.float64 or tuple(v.shape) != (n,) or v.device != x.device:
+                raise ValueError("%s must be a float64 (%d,) tensor on the embeddings' device" % (name, n))
+        mean, std = mean.contiguous(), std.contiguous()
+    nt = idx[0].numel()
+    out = t.empty((nt,), dtype=t.float64, device=x.device)
+    rc = lib.ma_trial_scores_f32(_host.ptr(x), x.stride(0), n, x.shape[1], _host.ptr(idx[0]), _host.ptr(idx[1]), nt,
+                                 _host.ptr(mean) if mode else None, _host.ptr(std) if mode else None, mode, _host.ptr(out),
+                                 _host.current_stream_ptr())
+    _lib.check(rc, "trial_scores")
+    return out
+
+
+def running_mean_sub(x, g_mean=None, count=0):
+    """emb_mean of the reference as a column-wise scan: (y, g_mean, count) with y[n] = x[n] - g_n, g_n the running mean
+    (1 - w) g_{n-1} + w x[n], w = 1 / (count + n + 1); at count 0 the incoming g_mean is ignored (g = x[0]).
+    x (N, D) float32 device tensor; g_mean (D,) float64 device tensor or None; returns a new g_mean and count + N."""
+    t = _host.torch()
+    lib = _lib.load()
+    x = _check_emb(x, "x")
+    n, d = x.shape
+    count = int(count)
+    if count < 0:
+        raise ValueError("count must not be negative")
+    if g_mean is None:
+        if count:
+            raise ValueError("a running mean is needed when count > 0")
+        g = t.zeros((d,), dtype=t.float64, device=x.device)
+    else:
+        if tuple(g_mean.shape) != (d,):
+            raise ValueError("g_mean must have shape (%d,)" % d)
+        g = g_mean.to(device=x.device, dtype=t.float64).clone().contiguous()
+    nbytes = lib.ma_running_mean_sub_workspace_bytes(n, d)
+    ws = t.empty((max(int(nbytes), 8) // 8,), dtype=t.float64, device=x.device)
+    y = t.empty((n, d), dtype=t.float32, device=x.device)
+    rc = lib.ma_running_mean_sub_f32(_host.ptr(x), x.stride(0), n, d, _host.ptr(g), count, _host.ptr(y), y.stride(0), _host.ptr(ws),
+                                     nbytes, _host.current_stream_ptr())
+    _lib.check(rc, "running_mean_sub")
+    return y, g, count + n
+
+
+def sentence_mean_norm(x):
+    """InputNormalization(norm_type="sentence", std_norm=False): x (B, T, F) float32 minus its per-utterance, per-feature mean over T."""
+    t = _host.torch()
+    lib = _lib.load()
+    if not isinstance(x, t.Tensor) or x.dim() != 3 or x.dtype != t.float32 or 0 in x.shape:
+        raise ValueError("x must be a non-empty (B, T, F) float32 tensor")
+    x = x.contiguous()
+    out = t.empty_like(x)
+    b, tt, f = x.shape
+    for b0 in range(0, b, 65535):
+        nb = min(65535, b - b0)
+        rc = lib.ma_sentence_mean_norm_f32(_host.ptr(x[b0:]), nb, tt, f, _host.ptr(out[b0:]), _host.current_stream_ptr())
+        _lib.check(rc, "sentence_mean_norm")
+    return out
