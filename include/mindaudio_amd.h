@@ -1202,6 +1202,53 @@ int ma_running_mean_sub_f32(const float* X, int64_t ldx, int64_t N, int32_t D, d
                             void* workspace, int64_t workspace_bytes, ma_stream_t stream);
 int ma_sentence_mean_norm_f32(const float* x, int64_t batch, int64_t T, int32_t F, float* out, ma_stream_t stream);
 
+/* ---- waveform augmentation chain (csrc/augment.hip; mindaudio.data.augment, examples/ECAPA-TDNN/spec_augment.py) ----------------
+ * Rows are float32 waveforms `x + r * ldx` of n samples; every entry point that writes waveforms takes (out, ldo, n_out) and writes
+ * n_out columns per row: the result for columns < n (cut when n_out < n), 0.0 for columns in [n, n_out) - so an augmenter can
+ * write straight into its slice of the matrix the fbank reads.  Nothing allocates, nothing reads a scalar back: amplitudes live in
+ * a statistics buffer `double stats[rows][4]` = { sum |x|, sum x^2, max |x|, 0 } that the next kernel reads.  All sums run in a fixed
+ * order (no atomics): results are bit-identical from run to run.  rows <= 65535.
+ *   row_stats: the statistics of every row over its first n samples, float64 accumulation, one launch.
+ *   circular_fir: y[r][i] = sum_{k<K} h[k] x[r][(i - k) mod n], one filter (device, K <= 255 taps) for the batch; out must not
+ *     alias x.  (drop_freq: the reference's un-centred circular convolution.)
+ *   fft_conv: y[r][i] = sum_{k<K} h[k] x[r][(i + rot - k) mod n] (convolve1d(use_fft=True, rotation_index=rot); K <= n,
+ *     0 <= rot <= K) through zero-padded transforms of length L = ma_aug_fft_conv_length(n, K) (power of two >= n + K - 1), two rows
+ *     per complex transform, the filter's spectrum once per call; the wrapped tail is folded back in the pass that writes y.
+ *     stats_x != NULL: y is then rescaled to the input's average amplitude, y * amp(x) / (amp(y) + 1e-14), amp = sum|.| / n
+ *     (reverberate, rescale_amp="avg").  out may alias x.
+ *   babble_sum: out[r] = x[r - 1] + x[r - 2] + ... + x[r - speakers] (row indices mod rows, added in that order).
+ *   mix: out[r][i] = a_r x[r][i] + s_r noise[r * ld_noise + i] (ld_noise == 0: one noise row for the batch); out may alias x.
+ *     MA_AUG_MIX_NOISE   a = 1, s = gain * sqrt(stats_x[r].sumsq / n)                               (add_noise; gain = 10^(-snr/20))
+ *     MA_AUG_MIX_BABBLE  a = 1 - f, s = f * (sx / len) / (sn / blen + 1e-14), params[r] = { f, len, blen, 0 } (double)  (add_babble)
+ *     MA_AUG_MIX_UNIT_AVG  a = gain / (sx / len + 1e-14), params[r] = { len, .. }; MA_AUG_MIX_UNIT_PEAK  a = gain / (max|x| + 1e-14);
+ *       MA_AUG_MIX_UNIT_RMS  a = gain / (sqrt(sx2 / n) + 1e-8); all three with s = 0 and noise unused (unitarize / rescale /
+ *       rms_normalize).
+ *   drop_chunks: out = x with the intervals [start, end) of `intervals` (int32 (rows, n_max, 2), clipped to [0, n), empty ones
+ *     allowed, n_max <= 256) replaced in order j = 0 .. n_max - 1 (a later interval wins): by 0.0 when fill == NULL, else by
+ *     2 m u - m, m = 2 noise_factor stats[r].sumabs / lens[r], u = fill[fill_off[r * n_max + j] + i - start] (the host's uniform
+ *     draws, one run per interval).  Samples outside every interval are copied bit for bit.  out must not alias x. */
+#define MA_AUG_MIX_NOISE 0
+#define MA_AUG_MIX_BABBLE 1
+#define MA_AUG_MIX_UNIT_AVG 2
+#define MA_AUG_MIX_UNIT_PEAK 3
+#define MA_AUG_MIX_UNIT_RMS 4
+int ma_aug_row_stats_f32(const float* x, int64_t ldx, int64_t rows, int64_t n, double* stats, ma_stream_t stream);
+int ma_aug_circular_fir_f32(const float* x, int64_t ldx, int64_t rows, int64_t n, const float* h, int32_t K, float* out,
+                            int64_t ldo, int64_t n_out, ma_stream_t stream);
+int64_t ma_aug_fft_conv_length(int64_t n, int64_t K);
+int64_t ma_aug_fft_conv_workspace_bytes(int64_t rows, int64_t n, int64_t K);
+int ma_aug_fft_conv_f32(const float* x, int64_t ldx, int64_t rows, int64_t n, const float* h, int64_t K, int64_t rot,
+                        const double* stats_x, float* out, int64_t ldo, int64_t n_out, void* workspace, int64_t workspace_bytes,
+                        ma_stream_t stream);
+int ma_aug_babble_sum_f32(const float* x, int64_t ldx, int64_t rows, int64_t n, int32_t speakers, float* out, int64_t ldo,
+                          ma_stream_t stream);
+int ma_aug_mix_f32(const float* x, int64_t ldx, int64_t rows, int64_t n, const float* noise, int64_t ld_noise, int32_t mode,
+                   float gain, const double* params, const double* stats_x, const double* stats_noise, float* out, int64_t ldo,
+                   int64_t n_out, ma_stream_t stream);
+int ma_aug_drop_chunks_f32(const float* x, int64_t ldx, int64_t rows, int64_t n, const int32_t* intervals, int32_t n_max,
+                           const float* fill, const int32_t* fill_off, float noise_factor, const double* stats, const double* lens,
+                           float* out, int64_t ldo, int64_t n_out, ma_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

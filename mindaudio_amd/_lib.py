@@ -355,7 +355,18 @@ PROTOTYPES = {
     "ma_running_mean_sub_workspace_bytes": (i64, [i64, i32]),
     "ma_running_mean_sub_f32": (ctypes.c_int, [vp, i64, i64, i32, vp, i64, vp, i64, vp, i64, vp]),
     "ma_sentence_mean_norm_f32": (ctypes.c_int, [vp, i64, i64, i32, vp, vp]),
+    # ---- waveform augmentation chain ----
+    "ma_aug_row_stats_f32": (ctypes.c_int, [vp, i64, i64, i64, vp, vp]),
+    "ma_aug_circular_fir_f32": (ctypes.c_int, [vp, i64, i64, i64, vp, i32, vp, i64, i64, vp]),
+    "ma_aug_fft_conv_length": (i64, [i64, i64]),
+    "ma_aug_fft_conv_workspace_bytes": (i64, [i64, i64, i64]),
+    "ma_aug_fft_conv_f32": (ctypes.c_int, [vp, i64, i64, i64, vp, i64, i64, vp, vp, i64, i64, vp, i64, vp]),
+    "ma_aug_babble_sum_f32": (ctypes.c_int, [vp, i64, i64, i64, i32, vp, i64, vp]),
+    "ma_aug_mix_f32": (ctypes.c_int, [vp, i64, i64, i64, vp, i64, i32, f32, vp, vp, vp, vp, i64, i64, vp]),
+    "ma_aug_drop_chunks_f32": (ctypes.c_int, [vp, i64, i64, i64, vp, i32, vp, vp, f32, vp, vp, vp, i64, i64, vp]),
 }
+
+AUG_MIX_NOISE, AUG_MIX_BABBLE, AUG_MIX_UNIT_AVG, AUG_MIX_UNIT_PEAK, AUG_MIX_UNIT_RMS = 0, 1, 2, 3, 4  # MA_AUG_MIX_*
 
 _lib = None
 _tls = threading.local()  # .rec: the block table THIS thread is filling (train/block_table.py); load() then hands out its proxy

@@ -6,7 +6,7 @@ import numpy as np
 
 from .. import _host, _lib
 
-__all__ = ["resample", "resample_batch"]
+__all__ = ["resample", "resample_batch", "unitarize", "rescale"]
 
 
 def resampled_length(n, orig_freq, new_freq):
@@ -59,3 +59,50 @@ def resample(waveform, orig_freq=16000, new_freq=16000, res_type="fft", lowpass_
     if was_numpy:
         return y.cpu().numpy().astype(np.asarray(waveform).dtype)  # np.asarray(y_hat, dtype=waveform.dtype), :170
     return y
+
+
+def _unit(waveforms, lengths, amp_type, gain):
+    """gain * waveforms / (amplitude + 1e-14) in one mix launch behind the row statistics."""
+    from .. import ops
+    from . import spectrum as _spectrum
+
+    rows, restore, was_numpy = _spectrum._rows_channel_last(waveforms)
+    t = _host.torch()
+    stats = ops.aug_row_stats(rows)
+    if amp_type == "avg":
+        shape = tuple(np.shape(waveforms))
+        lens = t.as_tensor(rows.shape[1] if lengths is None else lengths, dtype=t.float64).reshape(-1)
+        if lens.numel() == 1:
+            lens = lens.expand(rows.shape[0])
+        elif len(shape) == 3:  # one length per batch entry, shared by its channels
+            lens = lens.repeat_interleave(shape[2])
+        params = t.zeros((rows.shape[0], 4), dtype=t.float64)
+        params[:, 0] = lens
+        out = ops.aug_mix(rows, _lib.AUG_MIX_UNIT_AVG, stats, gain=gain, params=params)
+    else:
+        out = ops.aug_mix(rows, _lib.AUG_MIX_UNIT_PEAK, stats, gain=gain)
+    out = restore(out)
+    return out.cpu().numpy() if was_numpy else out
+
+
+def unitarize(waveforms, lengths=None, amp_type="avg", eps=1e-14):
+    """processing.unitarize (processing.py:98-129): the waveforms over their average (sum |x| / lengths) or peak amplitude.
+    `[time]`, `[batch, time]` or `[batch, time, channels]`; eps is the reference's 1e-14 (the kernel's constant)."""
+    assert amp_type in ["avg", "peak"]
+    if eps != 1e-14:
+        raise NotImplementedError("eps other than the reference's default 1e-14 is not built")
+    return _unit(waveforms, lengths, amp_type, 1.0)
+
+
+def rescale(waveforms, target_lvl, lengths=None, amp_type="avg", dB=False):
+    """processing.rescale (processing.py:189-232): unitarize, then scale to `target_lvl` (a scalar; in dB when dB=True).  As in the
+    reference only amp_type="avg" passes both its own assertion ("max" | "avg") and unitarize's ("avg" | "peak")."""
+    from .spectrum import dB_to_amplitude
+
+    assert amp_type in ["max", "avg"]
+    assert dB in [True, False]
+    assert amp_type in ["avg", "peak"]  # unitarize's assertion, reached by the reference for "max"
+    if np.ndim(target_lvl) != 0:
+        raise NotImplementedError("rescale takes a scalar target level")
+    gain = float(dB_to_amplitude(float(target_lvl), ref=1.0, power=0.5)) if dB else float(target_lvl)
+    return _unit(waveforms, lengths, amp_type, gain)

@@ -10,7 +10,8 @@ import numpy as np
 
 from .. import _host, _lib
 
-__all__ = ["stft", "istft", "frame", "melspectrogram", "amplitude_to_dB", "spectrogram", "magphase"]
+__all__ = ["stft", "istft", "frame", "melspectrogram", "amplitude_to_dB", "spectrogram", "magphase", "compute_amplitude",
+           "dB_to_amplitude"]
 
 
 def _finish(out, lead, was_numpy):
@@ -259,3 +260,58 @@ def magphase(waveform, power, iscomplex=True):
     if was_numpy:
         return mag.cpu().numpy(), phase.cpu().numpy()
     return mag, phase
+
+
+# ---- amplitudes (spectrum.py:93-113, 497-544), used by data.augment and data.processing ---------------------------------------------
+def dB_to_amplitude(wavform, ref, power):
+    """ref * (10 ** (0.1 * wavform)) ** power (power 1: dB to power, 0.5: dB to amplitude).  Element-wise on whatever it is given
+    (scalars, arrays, tensors): the augmenters call it on a handful of SNR values on the host."""
+    ref_value = ref(wavform) if callable(ref) else abs(ref)
+    return ref_value * ((10.0 ** (0.1 * wavform)) ** power)
+
+
+def _rows_channel_last(waveforms):
+    """`[time]` / `[batch, time]` / `[batch, time, channels]` -> ((batch * channels, time) float32 device rows, restore(rows-like
+    (R, m) tensor -> the input's layout with m on the time axis), was_numpy)."""
+    t = _host.require_gpu()
+    was_numpy = not isinstance(waveforms, t.Tensor)
+    x = t.as_tensor(np.ascontiguousarray(waveforms) if was_numpy else waveforms).to(device="cuda", dtype=t.float32)
+    if x.dim() == 0 or x.dim() > 3:
+        raise NotImplementedError("waveforms must be [time], [batch, time] or [batch, time, channels]")
+    shape = tuple(x.shape)
+    if x.dim() == 1:
+        return x.reshape(1, -1), (lambda y: y.reshape(-1)), was_numpy
+    if x.dim() == 2:
+        return x, (lambda y: y), was_numpy
+    b, _, c = shape
+    rows = x.permute(0, 2, 1).reshape(b * c, shape[1])
+    return rows, (lambda y: y.reshape(b, c, -1).permute(0, 2, 1).contiguous()), was_numpy
+
+
+def compute_amplitude(waveforms, lengths=None, amp_type="avg", dB=False):
+    """Average (sum |x| over the time axis / `lengths`, or the mean) or peak amplitude, with the reference's kept time axis:
+    (batch, 1) or (batch, 1, channels); a `[time]` input counts as one row.  The sums are the device's row statistics (float64
+    accumulation); the result is float32."""
+    from .. import ops
+
+    if amp_type not in ("avg", "peak"):
+        raise TypeError("Unsupported amplitude type {}".format(repr(amp_type)))
+    rows, _, was_numpy = _rows_channel_last(waveforms)
+    t = _host.torch()
+    shape = tuple(np.shape(waveforms))
+    stats = ops.aug_row_stats(rows)
+    if len(shape) == 3:
+        pick = lambda k: stats[:, k].reshape(shape[0], shape[2])[:, None, :]  # noqa: E731
+    else:
+        pick = lambda k: stats[:, k].reshape(-1, 1)  # noqa: E731
+    if amp_type == "avg":
+        if lengths is None:
+            out = pick(0) / rows.shape[1]
+        else:
+            out = pick(0) / t.as_tensor(lengths, dtype=t.float64).to(rows.device)
+    else:
+        out = pick(2)
+    if dB:
+        out = (20 * t.log10(out)).clamp(min=-80)
+    out = out.to(t.float32)
+    return out.cpu().numpy() if was_numpy else out

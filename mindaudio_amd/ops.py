@@ -675,3 +675,157 @@ def sentence_mean_norm(x):
         rc = lib.ma_sentence_mean_norm_f32(_host.ptr(x[b0:]), nb, tt, f, _host.ptr(out[b0:]), _host.current_stream_ptr())
         _lib.check(rc, "sentence_mean_norm")
     return out
+
+
+# ---- waveform augmentation chain (csrc/augment.hip) -------------------------------------------------------------------------------
+# Device parts only: (rows, n) float32 device tensors whose rows may be strided (a slice of a wider matrix), small device arrays for
+# what the host decided, and `out` (rows, n_out): columns < n hold the result, the rest zeros.  Nothing here reads a value back.
+def _aug_rows(x, what="x"):
+    t = _host.torch()
+    if not isinstance(x, t.Tensor) or not x.is_cuda or x.dim() != 2 or x.dtype != t.float32 or 0 in x.shape:
+        raise ValueError("%s must be a non-empty (rows, n) float32 device tensor" % what)
+    if x.shape[0] > 65535:
+        raise ValueError("%s: at most 65535 rows per call" % what)
+    if x.stride(1) != 1 or (x.shape[0] > 1 and x.stride(0) < x.shape[1]):
+        x = x.contiguous()
+    return x
+
+
+def _aug_out(x, out, n_out=None):
+    t = _host.torch()
+    if out is None:
+        return t.empty((x.shape[0], x.shape[1] if n_out is None else int(n_out)), dtype=t.float32, device=x.device)
+    if (not isinstance(out, t.Tensor) or out.dim() != 2 or out.dtype != t.float32 or out.device != x.device or out.shape[0] != x.shape[0]
+            or out.stride(1) != 1 or (out.shape[0] > 1 and out.stride(0) < out.shape[1]) or 0 in out.shape):
+        raise ValueError("out must be a (rows, n_out) float32 tensor on x's device with unit column stride")
+    return out
+
+
+def _ld(x):
+    return x.stride(0) if x.shape[0] > 1 else x.shape[1]
+
+
+def _aug_f64(v, shape, device, what):
+    t = _host.torch()
+    v = t.as_tensor(v, dtype=t.float64).to(device).contiguous()
+    if tuple(v.shape) != tuple(shape):
+        raise ValueError("%s must have shape %r" % (what, tuple(shape)))
+    return v
+
+
+def aug_row_stats(x):
+    """(rows, 4) float64 device tensor: sum |x|, sum x^2, max |x|, 0 of every row."""
+    t = _host.torch()
+    x = _aug_rows(x)
+    stats = t.empty((x.shape[0], 4), dtype=t.float64, device=x.device)
+    rc = _lib.load().ma_aug_row_stats_f32(_host.ptr(x), _ld(x), x.shape[0], x.shape[1], _host.ptr(stats), _host.current_stream_ptr())
+    _lib.check(rc, "aug_row_stats")
+    return stats
+
+
+def aug_circular_fir(x, h, out=None):
+    """y[r][i] = sum_k h[k] x[r][(i - k) mod n]; h: up to 255 float32 taps on the device."""
+    t = _host.torch()
+    x = _aug_rows(x)
+    h = h.to(device=x.device, dtype=t.float32).contiguous()
+    if h.dim() != 1 or not 1 <= h.numel() <= 255:
+        raise ValueError("h must hold 1 to 255 taps")
+    out = _aug_out(x, out)
+    rc = _lib.load().ma_aug_circular_fir_f32(_host.ptr(x), _ld(x), x.shape[0], x.shape[1], _host.ptr(h), h.numel(), _host.ptr(out),
+                                             _ld(out), out.shape[1], _host.current_stream_ptr())
+    _lib.check(rc, "aug_circular_fir")
+    return out
+
+
+def aug_fft_conv(x, h, rot=0, stats_x=None, out=None):
+    """y[r][i] = sum_k h[k] x[r][(i + rot - k) mod n] (h: K <= n float32 taps on the device); with stats_x (aug_row_stats(x)) the result
+    is rescaled to x's average amplitude, as reverberate(rescale_amp="avg") does."""
+    t = _host.torch()
+    lib = _lib.load()
+    x = _aug_rows(x)
+    h = h.to(device=x.device, dtype=t.float32).contiguous()
+    rows, n = x.shape
+    if h.dim() != 1 or not 1 <= h.numel() <= n or not 0 <= int(rot) <= h.numel():
+        raise ValueError("h must hold 1 to n taps and 0 <= rot <= len(h)")
+    out = _aug_out(x, out)
+    nbytes = lib.ma_aug_fft_conv_workspace_bytes(rows, n, h.numel())
+    if nbytes < 0:
+        _lib.check(int(nbytes), "aug_fft_conv")
+    ws = _host.workspace(nbytes, x.device)
+    if stats_x is not None:
+        stats_x = _aug_f64(stats_x, (rows, 4), x.device, "stats_x")
+    rc = lib.ma_aug_fft_conv_f32(_host.ptr(x), _ld(x), rows, n, _host.ptr(h), h.numel(), int(rot),
+                                 None if stats_x is None else _host.ptr(stats_x), _host.ptr(out), _ld(out), out.shape[1], _host.ptr(ws),
+                                 ws.numel(), _host.current_stream_ptr())
+    _lib.check(rc, "aug_fft_conv")
+    return out
+
+
+def aug_babble_sum(x, speakers):
+    """out[r] = x[r - 1] + ... + x[r - speakers] (rows mod the batch)."""
+    t = _host.torch()
+    x = _aug_rows(x)
+    out = t.empty(tuple(x.shape), dtype=t.float32, device=x.device)
+    rc = _lib.load().ma_aug_babble_sum_f32(_host.ptr(x), _ld(x), x.shape[0], x.shape[1], int(speakers), _host.ptr(out), _ld(out),
+                                           _host.current_stream_ptr())
+    _lib.check(rc, "aug_babble_sum")
+    return out
+
+
+def aug_mix(x, mode, stats_x, noise=None, gain=1.0, params=None, stats_noise=None, out=None):
+    """out = a_r x[r] + s_r noise[row(r)] with a, s computed on the device (MA_AUG_MIX_* of the header); noise (n,) is one row for the
+    batch, (rows, n) one per row."""
+    t = _host.torch()
+    x = _aug_rows(x)
+    rows, n = x.shape
+    out = _aug_out(x, out)
+    stats_x = _aug_f64(stats_x, (rows, 4), x.device, "stats_x")
+    ldn = 0
+    if noise is not None:
+        noise = noise.to(device=x.device, dtype=t.float32)
+        if noise.dim() == 1:
+            noise = noise.contiguous()
+            if noise.numel() < n:
+                raise ValueError("noise is shorter than the rows")
+        else:
+            noise = _aug_rows(noise, "noise")
+            if noise.shape[0] != rows or noise.shape[1] < n:
+                raise ValueError("noise must be (rows, >= n)")
+            ldn = _ld(noise)
+    if params is not None:
+        params = _aug_f64(params, (rows, 4), x.device, "params")
+    if stats_noise is not None:
+        stats_noise = _aug_f64(stats_noise, (rows, 4), x.device, "stats_noise")
+    opt = lambda v: None if v is None else _host.ptr(v)  # noqa: E731
+    rc = _lib.load().ma_aug_mix_f32(_host.ptr(x), _ld(x), rows, n, opt(noise), ldn, int(mode), float(gain), opt(params),
+                                    _host.ptr(stats_x), opt(stats_noise), _host.ptr(out), _ld(out), out.shape[1],
+                                    _host.current_stream_ptr())
+    _lib.check(rc, "aug_mix")
+    return out
+
+
+def aug_drop_chunks(x, intervals, fill=None, fill_off=None, noise_factor=0.0, stats=None, lens=None, out=None):
+    """x with the intervals (rows, n_max, 2) int32 zeroed, or filled with 2 m u - m (u = the uniform draws in `fill`, m from the row's
+    amplitude in `stats`, see the header); samples outside the intervals are copied bit for bit."""
+    t = _host.torch()
+    x = _aug_rows(x)
+    rows, n = x.shape
+    out = _aug_out(x, out)
+    intervals = t.as_tensor(intervals).to(device=x.device, dtype=t.int32).contiguous()
+    if intervals.dim() != 3 or intervals.shape[0] != rows or intervals.shape[2] != 2 or intervals.shape[1] > 256:
+        raise ValueError("intervals must be (rows, n_max <= 256, 2)")
+    n_max = intervals.shape[1]
+    if fill is not None:
+        fill = fill.to(device=x.device, dtype=t.float32).contiguous()
+        fill_off = t.as_tensor(fill_off).to(device=x.device, dtype=t.int32).contiguous()
+        if tuple(fill_off.shape) != (rows, n_max):
+            raise ValueError("fill_off must be (rows, n_max)")
+        stats = _aug_f64(stats, (rows, 4), x.device, "stats")
+        lens = _aug_f64(lens, (rows,), x.device, "lens")
+    opt = lambda v: None if v is None else _host.ptr(v)  # noqa: E731
+    rc = _lib.load().ma_aug_drop_chunks_f32(_host.ptr(x), _ld(x), rows, n, _host.ptr(intervals) if n_max else None, n_max, opt(fill),
+                                            opt(fill_off) if fill is not None else None, float(noise_factor),
+                                            opt(stats) if fill is not None else None, opt(lens) if fill is not None else None,
+                                            _host.ptr(out), _ld(out), out.shape[1], _host.current_stream_ptr())
+    _lib.check(rc, "aug_drop_chunks")
+    return out

@@ -1,0 +1,211 @@
+"""CPU: the host halves of mindaudio_amd.data.augment against the reference's recorded decisions (tests/golden/augment_goldens.npz,
+written by tests/golden/gen_augment_goldens.py from the reference's own functions), the host-built filters, the argument errors, the
+C-ABI declarations, and the bookkeeping of ecapa.generate_train_data with the device part stubbed.  No kernel runs here."""
+import json
+import os
+import random
+import re
+import sys
+
+import numpy as np
+import pytest
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, HERE)
+
+import augment_cases as C  # noqa: E402
+
+from mindaudio_amd.data import augment as A  # noqa: E402
+from mindaudio_amd.data import filters  # noqa: E402
+
+
+@pytest.fixture(scope="module")
+def fix():
+    return np.load(os.path.join(HERE, "golden", "augment_goldens.npz"))
+
+
+@pytest.fixture(scope="module")
+def files(tmp_path_factory):
+    return C.make_files(str(tmp_path_factory.mktemp("augment_files")))
+
+
+def test_notch_filter_equals_the_reference(fix):
+    for key in [k for k in fix.files if k.startswith("notch/")]:
+        ours = filters.notch_filter(float(key.split("/")[1]))
+        assert ours.shape == (1, 101, 1) and ours.dtype == np.float64
+        assert np.abs(ours - fix[key]).max() <= 1e-12
+
+
+@pytest.mark.parametrize("name", ["drop_freq_1", "drop_freq_2"])
+def test_composed_drop_filter_equals_the_reference(fix, files, name):
+    """The filter is not an output of the reference; its effect is: a float64 circular convolution of the input with OUR filter,
+    delayed and wrapped as the reference applies it, equals the reference's output to 1e-12."""
+    case = C.CASES[name]
+    np.random.seed(case["seed"])
+    random.seed(case["seed"])
+    dec = case["host"](A, files)
+    assert dec["filter"].shape == (101,) and dec["filter"].dtype == np.float64
+    x = C.flat(C.f64(C.X_DF1() if name == "drop_freq_1" else C.X_DF2()), 1 if name == "drop_freq_2" else -1)
+    k = np.arange(101)
+    y = np.stack([sum(dec["filter"][j] * np.roll(row, j) for j in k) for row in x])
+    assert np.abs(y - fix[name + "/out"]).max() <= 1e-12
+
+
+HOST_CASES = [n for n, c in C.CASES.items() if c.get("host")]
+
+
+@pytest.mark.parametrize("name", HOST_CASES)
+def test_host_halves_reproduce_every_recorded_decision(fix, files, name):
+    """Same calls on the global generators, same order, same arguments, same results - and both generators end where the reference
+    leaves them (the log's last entry is the next draw of each)."""
+    want = json.loads(str(fix[name + "/draws"]))
+    with C.record_draws(C.CASES[name]["seed"]) as rec:
+        C.CASES[name]["host"](A, files)
+    assert len(rec.log) == len(want)
+    for got, exp in zip(rec.log, want):
+        assert got == exp
+
+
+@pytest.mark.parametrize("name,x", [("add_noise_cut", C.X_AN1), ("add_noise_pieces", C.X_AN2)])
+def test_add_noise_background_row(fix, files, name, x):
+    """x + background * rms(x) / 10^(snr / 20) in float64 with OUR background row and SNR is the reference's output to 1e-12."""
+    case = C.CASES[name]
+    np.random.seed(case["seed"])
+    random.seed(case["seed"])
+    dec = case["host"](A, files)
+    x = C.f64(x())
+    assert dec["background"].shape == (x.shape[1],) and dec["background"].dtype == np.float64
+    assert len(dec["paths"]) == (1 if name == "add_noise_cut" else len(dec["paths"])) and (name == "add_noise_cut" or len(dec["paths"]) > 2)
+    y = x + dec["background"][None, :] * (np.sqrt(np.square(x).mean(axis=-1, keepdims=True)) / 10 ** (dec["snr"] / 20))
+    assert np.abs(y - fix[name + "/out"]).max() <= 1e-12
+
+
+def test_drop_chunk_count0_case_has_a_row_without_chunks(files):
+    case = C.CASES["drop_chunk_count0"]
+    np.random.seed(case["seed"])
+    random.seed(case["seed"])
+    dec = case["host"](A, files)
+    assert 0 in dec["drop_times"].tolist() and dec["drop_times"].max() > 0
+    for i, n in enumerate(dec["drop_times"]):
+        assert len(dec["length"][i]) == n
+        assert all(hi == lo for lo, hi in dec["intervals"][i, n:])
+
+
+def test_argument_errors():
+    x = np.zeros((2, 2000), np.float32)
+    lens = np.ones(2)
+    for kw in (dict(drop_length_low=200, drop_length_high=100), dict(drop_count_low=3, drop_count_high=2),
+               dict(drop_start=500, drop_end=100)):
+        with pytest.raises(ValueError, match="Low limit must not be more than high limit"):
+            A.drop_chunk(x, lens, **kw)
+    with pytest.raises(NotImplementedError):
+        A.convolve1d(x, np.ones(3, np.float32), use_fft=False)
+    x4 = np.zeros((1, 2, 3, 64), np.float32)
+    with pytest.raises(NotImplementedError):
+        A.convolve1d(x4, np.ones(3, np.float32))
+    with pytest.raises(NotImplementedError):
+        A.reverberate(x4, np.ones(3, np.float32))
+    with pytest.raises(NotImplementedError):
+        A.add_reverb(x4, ["unused.wav"])
+    with pytest.raises(NotImplementedError):
+        A.add_noise(x4, ["unused.wav"], 0, 10)
+    for amp in ("peak", None, "max"):
+        with pytest.raises(NotImplementedError):
+            A.reverberate(x, np.ones(3, np.float32), rescale_amp=amp)
+
+
+def test_rotated_kernel_matches_the_reference_layout():
+    """concat(kernel[rot:], zeros, kernel[:rot]) as taps + rotation: y[i] = sum_k taps[k] x[(i + rot - k) mod n]."""
+    rng = np.random.RandomState(0)
+    for n, klen, rot in ((50, 7, 3), (20, 31, 4), (33, 5, 0)):
+        x, kernel = rng.randn(n), rng.randn(klen)
+        kern = kernel[:n]
+        full = np.concatenate((kern[rot:], np.zeros(n - kern.shape[0]), kern[:rot]))
+        want = np.fft.irfft(np.fft.rfft(x) * np.fft.rfft(full), n=n)
+        taps, r = A.rotated_kernel(kernel, n, rot)
+        got = np.array([sum(taps[k] * x[(i + r - k) % n] for k in range(taps.shape[0])) for i in range(n)])
+        assert np.abs(got - want).max() <= 1e-12
+
+
+def test_new_entry_points_declared_exported_and_bound():
+    from mindaudio_amd import _build, _lib
+
+    names = ["ma_aug_row_stats_f32", "ma_aug_circular_fir_f32", "ma_aug_fft_conv_length", "ma_aug_fft_conv_workspace_bytes",
+             "ma_aug_fft_conv_f32", "ma_aug_babble_sum_f32", "ma_aug_mix_f32", "ma_aug_drop_chunks_f32"]
+    header = open(os.path.join(os.path.dirname(HERE), "include", "mindaudio_amd.h")).read()
+    header = re.sub(r"/\*.*?\*/", "", header, flags=re.S)
+    _build.build()
+    lib = _lib.load()
+    for name in names:
+        assert re.search(r"\b%s\s*\(" % name, header), name
+        assert name in _lib.PROTOTYPES and hasattr(lib, name), name
+    assert "#define MA_ABI_VERSION 3" in header and lib.ma_abi_version() == _lib.ABI_VERSION == 3
+    # host-only entry points: the transform length and the workspace of the example's reverb (48 000 samples, 16 000 taps)
+    assert lib.ma_aug_fft_conv_length(48000, 16000) == 65536
+    assert lib.ma_aug_fft_conv_length(48000, 48000) == 131072
+    assert lib.ma_aug_fft_conv_length(100, 101) == -1
+    assert lib.ma_aug_fft_conv_workspace_bytes(32, 48000, 16000) >= 2 * 17 * 65536 * 8
+
+
+def test_generate_train_data_bookkeeping_with_the_device_stubbed(tmp_path):
+    """csv parsing, speaker numbering in order of first appearance, random_chunk on the global generator, file naming, id layout."""
+    from mindaudio_amd.ecapa import generate_train_data as G
+
+    csv_path = tmp_path / "train.csv"
+    rows = [("id10003--a--0", "6.0", C.WAV, "0", "48000", "id10003"), ("id10001--a--0", "5.999", C.WAV, "100", "48100", "id10001"),
+            ("id10003--b--0", "6.0", C.WAV, "0", "48000", "id10003"), ("id10002--a--0", "6.0", C.WAV, "0", "48000", "id10002"),
+            ("id10001--b--0", "6.0", C.WAV, "0", "48000", "id10001")]
+    with open(csv_path, "w") as fh:
+        fh.write("ID,duration,wav,start,stop,spk_id\n")
+        for r in rows:
+            fh.write(",".join(r) + "\n")
+    parsed, spk = G.read_annotation(str(csv_path))
+    assert spk == {"id10003": 0, "id10001": 1, "id10002": 2} and len(parsed) == 5
+    random.seed(5)
+    starts = [random.randint(0, int(float(r[1]) * 16000) - 48000) for r in rows]
+    seen = []
+
+    def featurize(wavs, spec_aug, concat_augment):
+        seen.append(wavs)
+        return np.zeros((6 * wavs.shape[0], 301, 80), np.float32)
+
+    cfg = dict(train_annotation=str(csv_path), feat_folder=str(tmp_path / "feat"), sample_rate=16000, sentence_len=3.0,
+               random_chunk=True, number_of_epochs=1, concat_augment=True, dataloader_options=dict(batch_size=2))
+    random.seed(5)
+    labels, feas = G.generate_train_data(cfg, spec_aug=[], log=lambda *a: None, featurize=featurize)
+    assert [w.shape for w in seen] == [(2, 48000), (2, 48000), (1, 48000)] and seen[0].dtype == np.float32
+    w = C.wav()
+    assert np.array_equal(seen[0][1], w[starts[1]:starts[1] + 48000].astype(np.float32))
+    assert len(labels) == len(feas) == 3 and labels == sorted(labels)
+    feat_dir = str(tmp_path / "feat")
+    assert open(os.path.join(feat_dir, "label.lst")).read().split() == labels
+    assert open(os.path.join(feat_dir, "fea.lst")).read().split() == feas
+    ids = [np.load(os.path.join(feat_dir, n)) for n in labels]
+    assert [i.shape for i in ids] == [(12, 1), (12, 1), (6, 1)]
+    assert ids[0][:, 0].tolist() == [0, 1] * 6 and ids[1][:, 0].tolist() == [0, 2] * 6 and ids[2][:, 0].tolist() == [1] * 6
+    for lab, fea in zip(labels, feas):
+        assert re.fullmatch(r"\d+\.\d+_0_id\.npy", lab) and fea == lab.replace("_id.npy", "_fea.npy")
+        assert np.load(os.path.join(feat_dir, fea)).dtype == np.float32
+    # random_chunk off: samples start..stop of the row
+    cfg["random_chunk"] = False
+    cfg["feat_folder"] = str(tmp_path / "feat2")
+    del seen[:]
+    G.generate_train_data(cfg, spec_aug=[], log=lambda *a: None, featurize=featurize)
+    assert np.array_equal(seen[0][1], w[100:48100].astype(np.float32))
+
+
+def test_env_corrupt_reads_the_csv_and_refuses_to_download(tmp_path, files):
+    from mindaudio_amd.ecapa.spec_augment import EnvCorrupt, InputNormalization, TimeDomainSpecAugment
+
+    env = EnvCorrupt(reverb_csv=files["reverb_csv"], noise_csv=files["noise_csv"], noise_snr_high=15)
+    assert env.add_noise.noise_data == files["noise"] and env.add_reverb.rir_data == files["rir"] and not hasattr(env, "add_babble")
+    assert not hasattr(EnvCorrupt(reverb_csv=files["reverb_csv"], noise_csv=files["noise_csv"], noise_prob=0.0), "add_noise")
+    folder = os.path.dirname(files["noise_csv"])
+    env = EnvCorrupt(openrir_folder=folder, reverb_prob=0.0)
+    assert env.add_noise.csv_file == files["noise_csv"] and not hasattr(env, "add_reverb")
+    with pytest.raises(FileNotFoundError):
+        EnvCorrupt(openrir_folder=str(tmp_path))
+    with pytest.raises(NotImplementedError):
+        InputNormalization()
+    aug = TimeDomainSpecAugment(drop_chunk_count_high=7)
+    assert aug.drop_chunk_count_high == 7 and aug.speeds == [95, 100, 105]
