@@ -1249,6 +1249,41 @@ int ma_aug_drop_chunks_f32(const float* x, int64_t ldx, int64_t rows, int64_t n,
                            const float* fill, const int32_t* fill_off, float noise_factor, const double* stats, const double* lens,
                            float* out, int64_t ldo, int64_t n_out, ma_stream_t stream);
 
+/* ---- ECAPA speaker-classification head (mindaudio/models/ecapatdnn.py:477-488 Classifier.construct with lin_blocks = 0,
+ * mindaudio/loss/AdditiveAngularMargin.py:27-39, and SoftmaxCrossEntropyWithLogits(sparse=False, reduction="mean") / CorrectLabelNum
+ * of examples/ECAPA-TDNN/train_speaker_embeddings.py:273-317) ------------------------------------------------------------------
+ * x (B, D) embeddings, W (N, D) class weights, y (B) int32 labels; contiguous float32, 16-byte aligned.  D a multiple of 32 in
+ * [32, 512] (anything else MA_ERR_UNSUPPORTED), B >= 1, N >= 2.  float32 operands and accumulation (f32 MFMA), accurate exp / log,
+ * no floating-point atomics: two runs give the same bits.  All launches are asynchronous on `stream`, none allocates.
+ *   e_i = x_i / sqrt(max(sum x_i^2, eps)), w_j likewise (MindSpore's L2Normalize); c = e w^T; sine = sqrt(max(1 - c^2, 0));
+ *   phi = c cos m - sine sin m, kept where c > cos(pi - m) (easy_margin: c > 0), else c - sin(pi - m) m (easy_margin: c);
+ *   output = scale (onehot phi + (1 - onehot) c); row_loss_i = logsumexp_j output_ij - output_i,y_i; loss = mean_i row_loss_i;
+ *   correct = sum_i [argmax_j output_ij == y_i], ties to the lowest index.
+ *   A label outside [0, N) is never used as an index: that row has no target (row_loss = its logsumexp, never correct).
+ *   ma_aam_softmax_fwd_f32 (3 launches): output (B, N), row_loss (B), loss (1), correct (1), and what the backward reads again:
+ *     inv_x (B), inv_w (N) the inverse norms, lse (B) the log-sum-exp, tgrad (B) d phi / d c of the target column
+ *     (cos m + sin m c / max(sine, 2^-12) on the phi branch, 1 on the other; rows without a target are left unwritten).
+ *   ma_aam_softmax_bwd_f32 (3 launches): dx (B, D) and dW (N, D) = *grad_scale times the exact derivative of `loss`, both
+ *     normalisations included (a row with sum r^2 <= eps is divided by the constant sqrt(eps), and differentiated as that);
+ *     dW additionally receives l2 * W.  grad_scale is a device scalar.  Probabilities are recomputed from `output` and `lse`.
+ *   Workspace: ma_aam_softmax_workspace_bytes(B, D, N) serves either call (forward: three (B, ceil(N / 32)) partial arrays; backward:
+ *     (S, B, D) partial sums of dx over S <= 64 slabs of classes); 16-byte aligned, MA_ERR_WORKSPACE when too small.
+ *   ma_aam_cosine_f32 (2 launches): cosine (B, N) = c alone, with the inverse norms (Classifier.construct).
+ *   ma_aam_margin_f32: out[i] = scale (targets[i] phi(cosine[i]) + (1 - targets[i]) cosine[i]) on n elements
+ *     (AdditiveAngularMargin.construct on given cosines and one-hot targets). */
+int64_t ma_aam_softmax_workspace_bytes(int64_t B, int32_t D, int64_t N);
+int ma_aam_softmax_fwd_f32(const float* x, const float* W, const int32_t* y, int64_t B, int32_t D, int64_t N, float margin, float scale,
+                           int32_t easy_margin, float eps, float* output, float* row_loss, float* loss, int32_t* correct, float* inv_x,
+                           float* inv_w, float* lse, float* tgrad, void* workspace, int64_t workspace_bytes, ma_stream_t stream);
+int ma_aam_softmax_bwd_f32(const float* x, const float* W, const int32_t* y, int64_t B, int32_t D, int64_t N, float scale, float eps,
+                           const float* output, const float* inv_x, const float* inv_w, const float* lse, const float* tgrad,
+                           const float* grad_scale, float l2, float* dx, float* dW, void* workspace, int64_t workspace_bytes,
+                           ma_stream_t stream);
+int ma_aam_cosine_f32(const float* x, const float* W, int64_t B, int32_t D, int64_t N, float eps, float* cosine, float* inv_x,
+                      float* inv_w, ma_stream_t stream);
+int ma_aam_margin_f32(const float* cosine, const float* targets, int64_t n, float margin, float scale, int32_t easy_margin, float* out,
+                      ma_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -364,6 +364,12 @@ PROTOTYPES = {
     "ma_aug_babble_sum_f32": (ctypes.c_int, [vp, i64, i64, i64, i32, vp, i64, vp]),
     "ma_aug_mix_f32": (ctypes.c_int, [vp, i64, i64, i64, vp, i64, i32, f32, vp, vp, vp, vp, i64, i64, vp]),
     "ma_aug_drop_chunks_f32": (ctypes.c_int, [vp, i64, i64, i64, vp, i32, vp, vp, f32, vp, vp, vp, i64, i64, vp]),
+    # ---- ECAPA speaker-classification head ----
+    "ma_aam_softmax_workspace_bytes": (i64, [i64, i32, i64]),
+    "ma_aam_softmax_fwd_f32": (ctypes.c_int, [vp, vp, vp, i64, i32, i64, f32, f32, i32, f32, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, vp]),
+    "ma_aam_softmax_bwd_f32": (ctypes.c_int, [vp, vp, vp, i64, i32, i64, f32, f32, vp, vp, vp, vp, vp, vp, f32, vp, vp, vp, i64, vp]),
+    "ma_aam_cosine_f32": (ctypes.c_int, [vp, vp, i64, i32, i64, f32, vp, vp, vp, vp]),
+    "ma_aam_margin_f32": (ctypes.c_int, [vp, vp, i64, f32, f32, i32, vp, vp]),
 }
 
 AUG_MIX_NOISE, AUG_MIX_BABBLE, AUG_MIX_UNIT_AVG, AUG_MIX_UNIT_PEAK, AUG_MIX_UNIT_RMS = 0, 1, 2, 3, 4  # MA_AUG_MIX_*

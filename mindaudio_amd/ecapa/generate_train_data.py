@@ -16,8 +16,9 @@ repeated once per version - and the sorted fea.lst / label.lst into feat_folder.
 
 Out of scope: prepare_voxceleb and the download of the verification list (network, data set: `train_annotation` must exist, with
 the columns ID,duration,wav,start,stop,spk_id); the Manager / Process fan-out over `data_process_num` CPU processes (one process,
-one GPU: the annotation is read in file order, without the example's shuffling MindSpore CSVDataset); data_trans_dp (the
-concatenation of these files into feat_folder_merge - its inputs are exactly the files and lists written here)."""
+one GPU: the annotation is read in file order, without the example's shuffling MindSpore CSVDataset).  data_trans_dp (the
+concatenation of these files into feat_folder_merge - its inputs are exactly the files and lists written here) is in
+ecapa/train_speaker_embeddings.py."""
 import argparse
 import csv
 import datetime

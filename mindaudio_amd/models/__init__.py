@@ -1,2 +1,3 @@
 from .conformer import ConformerEncoder  # noqa: F401
 from .ecapatdnn import EcapaTDNN  # noqa: F401
+from .ecapatdnn import Classifier  # noqa: F401

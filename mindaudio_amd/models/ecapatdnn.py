@@ -279,3 +279,21 @@ class EcapaTDNN(nn.Module):
             return ops.gemm(pooled, P["fc"]["w"], bias=P["fc"]["b"], out_dtype=t.float32, out=emb)
         _lib.check(rc, "linear_small")
         return emb
+
+
+class Classifier(nn.Module):
+    """Cosine classifier on top of the embeddings (ecapatdnn.py:436-488, the example builds it as Classifier(1, 0, emb_size, class_num)):
+    `weight` (out_neurons, lin_neurons), Xavier-uniform; forward(x) = normalise(x) . normalise(weight)^T with MindSpore's L2Normalize
+    (x / sqrt(max(sum x^2, 1e-4))).  forward() is the inference path and records no graph; a training step goes through
+    ops.aam_softmax_loss(emb, classifier.weight, labels), which owns the backward."""
+
+    def __init__(self, input_size, lin_blocks=0, lin_neurons=192, out_neurons=1211):
+        super().__init__()
+        if lin_blocks:
+            raise NotImplementedError("Classifier with lin_blocks > 0 (BatchNorm + Dense blocks) is not built; the example uses 0")
+        self.weight = nn.Parameter(torch.empty(out_neurons, lin_neurons, dtype=torch.float32))
+        nn.init.xavier_uniform_(self.weight)
+
+    def forward(self, x):
+        x = x.detach()
+        return ops.aam_cosine(x if x.is_contiguous() else x.contiguous(), self.weight.detach())

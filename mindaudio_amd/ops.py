@@ -829,3 +829,154 @@ def aug_drop_chunks(x, intervals, fill=None, fill_off=None, noise_factor=0.0, st
                                             _host.ptr(out), _ld(out), out.shape[1], _host.current_stream_ptr())
     _lib.check(rc, "aug_drop_chunks")
     return out
+
+
+# ---- ECAPA speaker-classification head (csrc/aam_softmax.hip) ---------------------------------------------------------------------
+def _aam_check(emb, weight, labels=None, check_labels=True):
+    """Argument checks of the head, in the order the mirrors raise: shapes / dtypes / layout (ValueError), label range (ValueError),
+    width (NotImplementedError), device (MindaudioAmdError).  Returns the labels as a 1-D int32 tensor on the embeddings' device
+    (None without labels)."""
+    t = _host.torch()
+    for name, v in (("emb", emb), ("weight", weight)):
+        if not isinstance(v, t.Tensor) or v.dim() != 2 or v.dtype != t.float32:
+            raise ValueError("%s must be a 2-D float32 tensor" % name)
+        if not v.is_contiguous():
+            raise ValueError("%s must be contiguous" % name)
+    b, d = emb.shape
+    n = weight.shape[0]
+    if weight.shape[1] != d:
+        raise ValueError("emb and weight differ in width: %d, %d" % (d, weight.shape[1]))
+    if b < 1 or n < 2:
+        raise ValueError("the head needs at least one row and two classes")
+    if labels is not None:
+        labels = t.as_tensor(labels)
+        if labels.dtype not in (t.int32, t.int64, t.int16, t.uint8, t.int8) or labels.dim() != 1 or labels.shape[0] != b:
+            raise ValueError("labels must be %d integers" % b)
+        if check_labels and (int(labels.min()) < 0 or int(labels.max()) >= n):
+            raise ValueError("labels hold a class outside [0, %d)" % n)
+    if d % 32 or not 32 <= d <= 512:
+        raise NotImplementedError("embedding width %d is not a multiple of 32 in [32, 512]" % d)
+    _host.require_gpu()
+    if not emb.is_cuda or weight.device != emb.device:
+        raise ValueError("emb and weight must be tensors of one HIP device")
+    return None if labels is None else labels.to(device=emb.device, dtype=t.int32).contiguous()
+
+
+def _aam_workspace(b, d, n, device):
+    nbytes = _lib.load().ma_aam_softmax_workspace_bytes(b, d, n)
+    if nbytes < 0:
+        _lib.check(int(nbytes), "aam_softmax")
+    return _host.workspace(nbytes, device), int(nbytes)
+
+
+def aam_softmax_fwd(emb, weight, labels, margin=0.2, scale=30.0, easy_margin=False, eps=1e-4):
+    """ma_aam_softmax_fwd_f32 on checked arguments (labels: int32 on the device).  Returns (output (B, N), row_loss (B), loss (1),
+    correct (1, int32), saved) with saved = (inv_x, inv_w, lse, tgrad), what aam_softmax_bwd reads again."""
+    t = _host.torch()
+    b, d = emb.shape
+    n = weight.shape[0]
+    dev = emb.device
+    ws, nbytes = _aam_workspace(b, d, n, dev)
+    f32 = dict(dtype=t.float32, device=dev)
+    output = t.empty((b, n), **f32)
+    row_loss, lse, tgrad, inv_x = (t.empty((b,), **f32) for _ in range(4))
+    inv_w = t.empty((n,), **f32)
+    loss = t.empty((1,), **f32)
+    correct = t.empty((1,), dtype=t.int32, device=dev)
+    rc = _lib.load().ma_aam_softmax_fwd_f32(_host.ptr(emb), _host.ptr(weight), _host.ptr(labels), b, d, n, float(margin), float(scale),
+                                            int(bool(easy_margin)), float(eps), _host.ptr(output), _host.ptr(row_loss),
+                                            _host.ptr(loss), _host.ptr(correct), _host.ptr(inv_x), _host.ptr(inv_w), _host.ptr(lse),
+                                            _host.ptr(tgrad), _host.ptr(ws), nbytes, _host.current_stream_ptr())
+    _lib.check(rc, "aam_softmax_fwd")
+    return output, row_loss, loss, correct, (inv_x, inv_w, lse, tgrad)
+
+
+def aam_softmax_bwd(emb, weight, labels, output, saved, grad_scale, l2=0.0, scale=30.0, eps=1e-4, dx=None, dw=None):
+    """ma_aam_softmax_bwd_f32: (dx, dW) = grad_scale (a float32 device scalar) times d loss / d (emb, weight); dW + l2 * weight."""
+    t = _host.torch()
+    b, d = emb.shape
+    n = weight.shape[0]
+    ws, nbytes = _aam_workspace(b, d, n, emb.device)
+    inv_x, inv_w, lse, tgrad = saved
+    dx = t.empty_like(emb) if dx is None else dx
+    dw = t.empty_like(weight) if dw is None else dw
+    rc = _lib.load().ma_aam_softmax_bwd_f32(_host.ptr(emb), _host.ptr(weight), _host.ptr(labels), b, d, n, float(scale), float(eps),
+                                            _host.ptr(output), _host.ptr(inv_x), _host.ptr(inv_w), _host.ptr(lse), _host.ptr(tgrad),
+                                            _host.ptr(grad_scale), float(l2), _host.ptr(dx), _host.ptr(dw), _host.ptr(ws), nbytes,
+                                            _host.current_stream_ptr())
+    _lib.check(rc, "aam_softmax_bwd")
+    return dx, dw
+
+
+_aam_fn = None
+
+
+def _aam_function():
+    """The torch.autograd.Function around the two entry points (built on first use: torch is imported lazily in this module)."""
+    global _aam_fn
+    if _aam_fn is not None:
+        return _aam_fn
+    t = _host.torch()
+
+    class AamSoftmaxLoss(t.autograd.Function):
+        @staticmethod
+        def forward(ctx, emb, weight, labels, margin, scale, easy_margin, eps):
+            output, _, loss, correct, saved = aam_softmax_fwd(emb, weight, labels, margin, scale, easy_margin, eps)
+            ctx.save_for_backward(emb, weight, labels, output, *saved)
+            ctx.head = (scale, eps)
+            correct = correct.reshape(())
+            ctx.mark_non_differentiable(correct, output)
+            return loss.reshape(()), correct, output
+
+        @staticmethod
+        def backward(ctx, g_loss, _g_correct, _g_output):
+            emb, weight, labels, output = ctx.saved_tensors[:4]
+            scale, eps = ctx.head
+            gs = g_loss.detach().to(dtype=t.float32).reshape(1).contiguous()
+            dx, dw = aam_softmax_bwd(emb, weight, labels, output, ctx.saved_tensors[4:], gs, 0.0, scale, eps)
+            return dx, dw, None, None, None, None, None
+
+    _aam_fn = AamSoftmaxLoss
+    return _aam_fn
+
+
+def aam_softmax_loss(emb, weight, labels, margin=0.2, scale=30.0, easy_margin=False, eps=1e-4, return_output=False):
+    """The loss head of the ECAPA example behind the embedding: cosine Classifier (lin_blocks = 0) -> AdditiveAngularMargin ->
+    softmax cross-entropy (mean) -> CorrectLabelNum on the margin-penalised output.  emb (B, D), weight (N, D) contiguous float32
+    device tensors, labels (B,) integers.  Returns (loss, correct[, output]); loss.backward() fills emb.grad and weight.grad through
+    ma_aam_softmax_bwd_f32.  Reading the labels' range costs a device read-back when they live on the device."""
+    labels = _aam_check(emb, weight, labels)
+    loss, correct, output = _aam_function().apply(emb, weight, labels, float(margin), float(scale), bool(easy_margin), float(eps))
+    return (loss, correct, output) if return_output else (loss, correct)
+
+
+def aam_cosine(emb, weight, eps=1e-4):
+    """Classifier.construct with lin_blocks = 0: cos(emb[b], weight[n]) (B, N), both sides normalised as MindSpore's L2Normalize."""
+    t = _host.torch()
+    _aam_check(emb, weight)
+    b, d = emb.shape
+    n = weight.shape[0]
+    out = t.empty((b, n), dtype=t.float32, device=emb.device)
+    inv_x = t.empty((b,), dtype=t.float32, device=emb.device)
+    inv_w = t.empty((n,), dtype=t.float32, device=emb.device)
+    rc = _lib.load().ma_aam_cosine_f32(_host.ptr(emb), _host.ptr(weight), b, d, n, float(eps), _host.ptr(out), _host.ptr(inv_x),
+                                       _host.ptr(inv_w), _host.current_stream_ptr())
+    _lib.check(rc, "aam_cosine")
+    return out
+
+
+def aam_margin(cosine, targets, margin=0.0, scale=1.0, easy_margin=False):
+    """AdditiveAngularMargin.construct: scale (targets phi + (1 - targets) cosine), elementwise on float32 device tensors."""
+    t = _host.torch()
+    for name, v in (("outputs", cosine), ("targets", targets)):
+        if not isinstance(v, t.Tensor) or v.dtype != t.float32:
+            raise ValueError("%s must be a float32 tensor" % name)
+    if cosine.shape != targets.shape:
+        raise ValueError("outputs and targets differ in shape")
+    _host.require_gpu()
+    c, tg = cosine.contiguous(), targets.to(cosine.device).contiguous()
+    out = t.empty_like(c)
+    rc = _lib.load().ma_aam_margin_f32(_host.ptr(c), _host.ptr(tg), c.numel(), float(margin), float(scale), int(bool(easy_margin)),
+                                       _host.ptr(out), _host.current_stream_ptr())
+    _lib.check(rc, "aam_margin")
+    return out
