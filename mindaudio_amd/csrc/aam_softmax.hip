@@ -20,6 +20,7 @@
 #include <math.h>
 #include <stdint.h>
 
+#include "device_common.h"
 #include "launch.h"
 
 namespace {
@@ -46,12 +47,6 @@ __device__ __forceinline__ float margin_dphi(float c, const Margin& p) {
   return p.cos_m + p.sin_m * c / fmaxf(sine, 0x1p-12f);
 }
 
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 // sum of squares of one row, one wave per row: the forward's norm and the backward's saturation test use the same bits
 __device__ __forceinline__ double row_sumsq(const float* __restrict__ row, int D, int lane) {
   double s = 0.0;
@@ -59,7 +54,7 @@ __device__ __forceinline__ double row_sumsq(const float* __restrict__ row, int D
     const double v = (double)row[d];
     s += v * v;
   }
-  return wave_sum(s);
+  return ma::wave_sum(s);
 }
 
 // inv[r] = 1 / sqrt(max(sum x[r]^2, eps)) for the rows of x (B) then W (N): MindSpore's L2Normalize
@@ -224,7 +219,7 @@ __global__ __launch_bounds__(FIN_THREADS) void aam_fwd_finish_kernel(const float
     }
     double se = 0.0;
     for (int64_t k = lane; k < nblk; k += 64) se += (double)psum[b * nblk + k] * (double)expf(pm[k] - v);
-    se = wave_sum(se);
+    se = ma::wave_sum(se);
     const float l = (float)((double)v + log(se));
     const int64_t yb = y[b];
     const bool has = yb >= 0 && yb < N;
@@ -383,7 +378,7 @@ __global__ __launch_bounds__(256) void aam_bwd_finish_kernel(const float* __rest
       dot += (double)u[j] * (double)v[j];
     }
   }
-  dot = wave_sum(dot);
+  dot = ma::wave_sum(dot);
 #pragma unroll
   for (int j = 0; j < 8; ++j) {
     const int d = lane + 64 * j;

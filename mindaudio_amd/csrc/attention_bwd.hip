@@ -23,27 +23,13 @@
 
 #include "../../include/mindaudio_amd.h"
 
+#include "device_common.h"
 #include "launch.h"
 
 namespace ma {
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
 typedef short ab_v4s __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) ab_v4s ab_lds_v4s;
-
-__device__ __forceinline__ uint16_t ab_to_bf16(float f) {
-  uint32_t u = __builtin_bit_cast(uint32_t, f);
-  if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40);
-  u += 0x7fffu + ((u >> 16) & 1u);
-  return (uint16_t)(u >> 16);
-}
-__device__ __forceinline__ float ab_from_bf16(uint16_t h) { return __builtin_bit_cast(float, (uint32_t)h << 16); }
-__device__ __forceinline__ uint32_t ab_pack(float lo, float hi) {  // v_cvt_pk_bf16_f32: RNE, one instruction
-  uint32_t r;
-  asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(lo), "v"(hi));
-  return r;
-}
 
 // workspace (float32): D [B*H][Tp] | bias_part [H][B * Tp/64][128] | dp_part [B][Tp][256]   (until round 4 it began with 576 Tp bf16
 // per (b, h): row-major and transposed copies of Q', K' and dO^T)
@@ -66,10 +52,10 @@ __device__ __forceinline__ void ab_unpack8(const uint4& v, float (&f)[8]) {
   }
 }
 __device__ __forceinline__ uint4 ab_pack8(const float (&f)[8]) {
-  return make_uint4((uint32_t)ab_to_bf16(f[0]) | ((uint32_t)ab_to_bf16(f[1]) << 16),
-                    (uint32_t)ab_to_bf16(f[2]) | ((uint32_t)ab_to_bf16(f[3]) << 16),
-                    (uint32_t)ab_to_bf16(f[4]) | ((uint32_t)ab_to_bf16(f[5]) << 16),
-                    (uint32_t)ab_to_bf16(f[6]) | ((uint32_t)ab_to_bf16(f[7]) << 16));
+  return make_uint4((uint32_t)f2bf(f[0]) | ((uint32_t)f2bf(f[1]) << 16),
+                    (uint32_t)f2bf(f[2]) | ((uint32_t)f2bf(f[3]) << 16),
+                    (uint32_t)f2bf(f[4]) | ((uint32_t)f2bf(f[5]) << 16),
+                    (uint32_t)f2bf(f[6]) | ((uint32_t)f2bf(f[7]) << 16));
 }
 // D[b, h, t] = sum_d dO[t, d] O[t, d] (the softmax backward's row term); 4 threads per row
 __global__ __launch_bounds__(256) void attn_bwd_prep_kernel(const uint16_t* __restrict__ ctx, int64_t ld_ctx,
@@ -283,8 +269,8 @@ __global__ __launch_bounds__(256, NF >= MA_AB_OCC1 ? 1 : 2) void attn_bwd_kernel
       if (KEYS_FIXED && st * 64 + xr_ + 16 * i < T) {  // q -> bf16(q + u) or bf16(q + v)
         float f[8];
         ab_unpack8(v, f);
-        v = make_uint4(ab_pack(f[0] + xbias[0], f[1] + xbias[1]), ab_pack(f[2] + xbias[2], f[3] + xbias[3]),
-                       ab_pack(f[4] + xbias[4], f[5] + xbias[5]), ab_pack(f[6] + xbias[6], f[7] + xbias[7]));
+        v = make_uint4(pack2_bf16_asm(f[0] + xbias[0], f[1] + xbias[1]), pack2_bf16_asm(f[2] + xbias[2], f[3] + xbias[3]),
+                       pack2_bf16_asm(f[4] + xbias[4], f[5] + xbias[5]), pack2_bf16_asm(f[6] + xbias[6], f[7] + xbias[7]));
       }
       if (KEYS_FIXED) *reinterpret_cast<uint4*>(&Xs[(xr_ + 16 * i) * kXs + xc_ * 8]) = v;
       else *reinterpret_cast<uint4*>(&Xs[(yr_ + 32 * (i & 1)) * kXs + 64 * (i >> 1) + yc_ * 8]) = v;
@@ -345,10 +331,10 @@ __global__ __launch_bounds__(256, NF >= MA_AB_OCC1 ? 1 : 2) void attn_bwd_kernel
           p[r] = __expf(e);
           g[r] = p[r] * (dp[r] - (KEYS_FIXED ? r1v[r] : f_D[nf])) * scale;
         }
-        pb[nf][mh][0] = ab_pack(p[0], p[1]);
-        pb[nf][mh][1] = ab_pack(p[2], p[3]);
-        db[nf][mh][0] = ab_pack(g[0], g[1]);
-        db[nf][mh][1] = ab_pack(g[2], g[3]);
+        pb[nf][mh][0] = pack2_bf16_asm(p[0], p[1]);
+        pb[nf][mh][1] = pack2_bf16_asm(p[2], p[3]);
+        db[nf][mh][0] = pack2_bf16_asm(g[0], g[1]);
+        db[nf][mh][1] = pack2_bf16_asm(g[2], g[3]);
         if (NF >= 4) __builtin_amdgcn_sched_barrier(0);  // (keeps the slabs' live ranges apart: the scheduler otherwise interleaves them)
       }
     }
@@ -400,11 +386,11 @@ __global__ __launch_bounds__(256, NF >= MA_AB_OCC1 ? 1 : 2) void attn_bwd_kernel
 #pragma unroll
       for (int ct = 0; ct < 4; ++ct)  // dk
         *reinterpret_cast<uint2*>(orow + dm + ct * 16) =
-            make_uint2(ab_pack(acc_x[nf][ct][0], acc_x[nf][ct][1]), ab_pack(acc_x[nf][ct][2], acc_x[nf][ct][3]));
+            make_uint2(pack2_bf16_asm(acc_x[nf][ct][0], acc_x[nf][ct][1]), pack2_bf16_asm(acc_x[nf][ct][2], acc_x[nf][ct][3]));
 #pragma unroll
       for (int dt = 0; dt < 4; ++dt)  // dv
         *reinterpret_cast<uint2*>(orow + 2 * dm + dt * 16) =
-            make_uint2(ab_pack(acc_y[nf][dt][0], acc_y[nf][dt][1]), ab_pack(acc_y[nf][dt][2], acc_y[nf][dt][3]));
+            make_uint2(pack2_bf16_asm(acc_y[nf][dt][0], acc_y[nf][dt][1]), pack2_bf16_asm(acc_y[nf][dt][2], acc_y[nf][dt][3]));
       // dp: per-batch partial (B, Tp, 256) float32; attn_dpos_reduce_kernel sums over the batch (2.6 M contended atomics
       // on (T, 256) cost more than the kernel's MFMAs)
       float* prow = ws.dp_part + ((int64_t)bv * Tp + fidx[nf]) * dm + hv * 64 + lg * 4;
@@ -421,8 +407,8 @@ __global__ __launch_bounds__(256, NF >= MA_AB_OCC1 ? 1 : 2) void attn_bwd_kernel
 #pragma unroll
       for (int ct = 0; ct < 4; ++ct)  // dq = dQ'[:, c] + dQ'[:, 64 + c]
         *reinterpret_cast<uint2*>(orow + ct * 16) =
-            make_uint2(ab_pack(acc_x[nf][ct][0] + acc_x[nf][ct + 4][0], acc_x[nf][ct][1] + acc_x[nf][ct + 4][1]),
-                       ab_pack(acc_x[nf][ct][2] + acc_x[nf][ct + 4][2], acc_x[nf][ct][3] + acc_x[nf][ct + 4][3]));
+            make_uint2(pack2_bf16_asm(acc_x[nf][ct][0] + acc_x[nf][ct + 4][0], acc_x[nf][ct][1] + acc_x[nf][ct + 4][1]),
+                       pack2_bf16_asm(acc_x[nf][ct][2] + acc_x[nf][ct + 4][2], acc_x[nf][ct][3] + acc_x[nf][ct + 4][3]));
     }
     // du / dv: sum over the queries of this wave (its NF slabs in the lane, then the 16 lanes lq)
 #pragma unroll

@@ -11,32 +11,10 @@
 
 #include "../../include/mindaudio_amd.h"
 
+#include "device_common.h"
 #include "launch.h"
 
 namespace ma {
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-
-__device__ __forceinline__ uint16_t to_bf16(float f) {
-  uint32_t u = __builtin_bit_cast(uint32_t, f);
-  if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40);
-  u += 0x7fffu + ((u >> 16) & 1u);
-  return (uint16_t)(u >> 16);
-}
-__device__ __forceinline__ float from_bf16(uint16_t h) { return __builtin_bit_cast(float, (uint32_t)h << 16); }
-// two f32 -> packed bf16x2, round to nearest even, one instruction (v_cvt_pk_bf16_f32, gfx950)
-__device__ __forceinline__ uint32_t pack2_bf16(float lo, float hi) {
-  uint32_t r;
-  asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(lo), "v"(hi));
-  return r;
-}
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
 
 // ---- LayerNorm: one wave per row, D = 4 * 64 * VEC floats held in registers ---------------------------------
 template <int VEC>
@@ -85,8 +63,8 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict_
     o.w = (v[i].w * inv * g.w + b.w) * rs;
     if (out_bf16) {
       uint2 pk;
-      pk.x = pack2_bf16(o.x, o.y);
-      pk.y = pack2_bf16(o.z, o.w);
+      pk.x = pack2_bf16_asm(o.x, o.y);
+      pk.y = pack2_bf16_asm(o.z, o.w);
       *reinterpret_cast<uint2*>(reinterpret_cast<uint16_t*>(out) + row * ldo + c) = pk;
     } else {
       *reinterpret_cast<float4*>(reinterpret_cast<float*>(out) + row * ldo + c) = o;
@@ -129,8 +107,8 @@ __global__ __launch_bounds__(256) void layernorm2_kernel(const float* __restrict
   v.x = v.x * inv * g.x + b.x; v.y = v.y * inv * g.y + b.y; v.z = v.z * inv * g.z + b.z; v.w = v.w * inv * g.w + b.w;
   if (out2_bf16) {
     uint2 pk;
-    pk.x = pack2_bf16(v.x, v.y);
-    pk.y = pack2_bf16(v.z, v.w);
+    pk.x = pack2_bf16_asm(v.x, v.y);
+    pk.y = pack2_bf16_asm(v.z, v.w);
     *reinterpret_cast<uint2*>(reinterpret_cast<uint16_t*>(out2) + row * ldo2 + c) = pk;
   } else {
     *reinterpret_cast<float4*>(reinterpret_cast<float*>(out2) + row * ldo2 + c) = v;
@@ -140,7 +118,7 @@ __global__ __launch_bounds__(256) void layernorm2_kernel(const float* __restrict
 // ---- CMVN + Conv2d(1 -> C, 3x3, stride 2, valid) + ReLU, output NHWC bf16 -----------------------------------
 // One workgroup per (b, output time t): 256 threads = channels (C == 256) or C/… loop; the 3 x idim input rows are
 // normalised into LDS once, each thread keeps its 9 weights in registers and walks the F1 output columns.
-__device__ __forceinline__ void st_pair(uint16_t* p, float a, float b) { *reinterpret_cast<uint32_t*>(p) = pack2_bf16(a, b); }
+__device__ __forceinline__ void st_pair(uint16_t* p, float a, float b) { *reinterpret_cast<uint32_t*>(p) = pack2_bf16_asm(a, b); }
 __device__ __forceinline__ void st_pair(float* p, float a, float b) { *reinterpret_cast<float2*>(p) = make_float2(a, b); }
 template <typename OT>  // uint16_t: bf16 NHWC (throughput path); float: the float32 validation mode (ma_subsample_conv1_nhwc_x32)
 __global__ __launch_bounds__(256) void subsample_conv1_kernel(const float* __restrict__ x, int64_t sb, int64_t st, int64_t sf,
@@ -269,10 +247,10 @@ __global__ __launch_bounds__(256) void subsample_conv1_c256_kernel(const float* 
           for (int j = 0; j < 8; ++j) acc[j] = fmaf(wv[j][kh * 3 + kw], xv, acc[j]);
         }
       uint4 pk;
-      pk.x = pack2_bf16(fmaxf(acc[0], 0.0f), fmaxf(acc[1], 0.0f));
-      pk.y = pack2_bf16(fmaxf(acc[2], 0.0f), fmaxf(acc[3], 0.0f));
-      pk.z = pack2_bf16(fmaxf(acc[4], 0.0f), fmaxf(acc[5], 0.0f));
-      pk.w = pack2_bf16(fmaxf(acc[6], 0.0f), fmaxf(acc[7], 0.0f));
+      pk.x = pack2_bf16_asm(fmaxf(acc[0], 0.0f), fmaxf(acc[1], 0.0f));
+      pk.y = pack2_bf16_asm(fmaxf(acc[2], 0.0f), fmaxf(acc[3], 0.0f));
+      pk.z = pack2_bf16_asm(fmaxf(acc[4], 0.0f), fmaxf(acc[5], 0.0f));
+      pk.w = pack2_bf16_asm(fmaxf(acc[6], 0.0f), fmaxf(acc[7], 0.0f));
       *reinterpret_cast<uint4*>(o + (int64_t)f1 * 256) = pk;
     }
   }
@@ -305,12 +283,7 @@ constexpr int kVsStride = 80;        // bf16 elements per V row (160 B = 40 dwor
 // (100 MHz) values in SGPRs and writes them out at the end of the kernel.
 #ifdef MA_ATT_PROF
 __device__ unsigned long long g_att_prof[3 * 16];
-#define ATT_STAMP(k)                                   \
-  do {                                                 \
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); \
-    att_ts[(k)] = wall_clock64();                      \
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); \
-  } while (0)
+#define ATT_STAMP(k) MA_PHASE_STAMP(att_ts, k)
 #else
 #define ATT_STAMP(k) do { } while (0)
 #endif
@@ -359,9 +332,9 @@ __global__ __launch_bounds__(NW * 64, (NW == 8 || QF == 2) ? 2 : 4) void relpos_
       uint32_t o[4];
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
-        const float lo = from_bf16((uint16_t)(wds[e] & 0xffff)) + bias[2 * e];
-        const float hi = from_bf16((uint16_t)(wds[e] >> 16)) + bias[2 * e + 1];
-        o[e] = pack2_bf16(lo, hi);
+        const float lo = bf2f((uint16_t)(wds[e] & 0xffff)) + bias[2 * e];
+        const float hi = bf2f((uint16_t)(wds[e] >> 16)) + bias[2 * e + 1];
+        o[e] = pack2_bf16_asm(lo, hi);
       }
       const uint4 pk = make_uint4(o[0], o[1], o[2], o[3]);
       qf[f][ks] = __builtin_bit_cast(bf16x8, pk);
@@ -485,15 +458,7 @@ __global__ __launch_bounds__(NW * 64, (NW == 8 || QF == 2) ? 2 : 4) void relpos_
     for (int f = 0; f < QF; ++f) {
       // the row maximum over the 4 lane groups through gfx950's row swaps (two VALU instructions instead of two ds_bpermute round
       // trips on the critical path of every key tile; tools/ubench/permlane_test.hip)
-      {
-        float a = tmax[f], b = tmax[f];
-        asm volatile("s_nop 1\n\tv_permlane16_swap_b32 %0, %1" : "+v"(a), "+v"(b));
-        tmax[f] = fmaxf(a, b);
-        a = tmax[f];
-        b = tmax[f];
-        asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(a), "+v"(b));
-        tmax[f] = fmaxf(a, b);
-      }
+      tmax[f] = max_xor32(max_xor16(tmax[f]));
       const float mnew = fmaxf(mrow[f], tmax[f]);  // finite: key 0 of the first tile always exists
       const float alpha = (mrow[f] == -INFINITY) ? 0.0f : __builtin_amdgcn_exp2f(mrow[f] - mnew);
       mrow[f] = mnew;
@@ -503,8 +468,8 @@ __global__ __launch_bounds__(NW * 64, (NW == 8 || QF == 2) ? 2 : 4) void relpos_
         const float e0 = __builtin_amdgcn_exp2f(s[f][c][0] - mnew), e1 = __builtin_amdgcn_exp2f(s[f][c][1] - mnew);
         const float e2 = __builtin_amdgcn_exp2f(s[f][c][2] - mnew), e3 = __builtin_amdgcn_exp2f(s[f][c][3] - mnew);
         psum += (e0 + e1) + (e2 + e3);
-        pb[f][c][0] = pack2_bf16(e0, e1);
-        pb[f][c][1] = pack2_bf16(e2, e3);
+        pb[f][c][0] = pack2_bf16_asm(e0, e1);
+        pb[f][c][1] = pack2_bf16_asm(e2, e3);
       }
       lrow[f] = lrow[f] * alpha + psum;  // this lane group's share: alpha is the same in the row's 4 lanes, the groups are summed once at the end
 #pragma unroll
@@ -547,16 +512,7 @@ __global__ __launch_bounds__(NW * 64, (NW == 8 || QF == 2) ? 2 : 4) void relpos_
 #pragma unroll
   for (int f = 0; f < QF; ++f) {
     const int qi = q_base + 16 * f + lq;
-    float lr = lrow[f];
-    {  // the row's sum over its 4 lane groups
-      float a = lr, b = lr;
-      asm volatile("s_nop 1\n\tv_permlane16_swap_b32 %0, %1" : "+v"(a), "+v"(b));
-      lr = a + b;
-      a = lr;
-      b = lr;
-      asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(a), "+v"(b));
-      lr = a + b;
-    }
+    const float lr = sum_xor32(sum_xor16(lrow[f]));  // the row's sum over its 4 lane groups
     // log-sum-exp of the scaled, masked scores of row qi: what the backward pass needs to rebuild the probabilities
     if (lse && qi < T && lg == 0) lse[((int64_t)b * H + h) * T + qi] = (mrow[f] + __log2f(lr)) * 0.6931471805599453f;
     if (qi < T) {
@@ -565,8 +521,8 @@ __global__ __launch_bounds__(NW * 64, (NW == 8 || QF == 2) ? 2 : 4) void relpos_
 #pragma unroll
       for (int dt = 0; dt < 4; ++dt) {
         uint2 pk;
-        pk.x = pack2_bf16(oacc[f][dt][0] * inv, oacc[f][dt][1] * inv);
-        pk.y = pack2_bf16(oacc[f][dt][2] * inv, oacc[f][dt][3] * inv);
+        pk.x = pack2_bf16_asm(oacc[f][dt][0] * inv, oacc[f][dt][1] * inv);
+        pk.y = pack2_bf16_asm(oacc[f][dt][2] * inv, oacc[f][dt][3] * inv);
         *reinterpret_cast<uint2*>(o + dt * 16) = pk;
       }
     }
@@ -626,8 +582,8 @@ __global__ __launch_bounds__(256) void convmodule_mid_kernel(const uint16_t* __r
         const uint32_t aw[4] = {av.x, av.y, av.z, av.w}, gw[4] = {gv.x, gv.y, gv.z, gv.w};
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-          const float a0 = from_bf16((uint16_t)(aw[e] & 0xffff)), a1 = from_bf16((uint16_t)(aw[e] >> 16));
-          const float g0 = from_bf16((uint16_t)(gw[e] & 0xffff)), g1 = from_bf16((uint16_t)(gw[e] >> 16));
+          const float a0 = bf2f((uint16_t)(aw[e] & 0xffff)), a1 = bf2f((uint16_t)(aw[e] >> 16));
+          const float g0 = bf2f((uint16_t)(gw[e] & 0xffff)), g1 = bf2f((uint16_t)(gw[e] >> 16));
           // layers/glu.py:24-28: out * sigmoid(gate)
           g[2 * e] = a0 * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.4426950408889634f * g0));
           g[2 * e + 1] = a1 * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.4426950408889634f * g1));
@@ -694,7 +650,7 @@ __global__ __launch_bounds__(256) void convmodule_mid_kernel(const uint16_t* __r
         float z1 = acc[o][2 * e + 1] * sc[2 * e + 1] + sh[2 * e + 1];
         z0 = z0 * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.4426950408889634f * z0));
         z1 = z1 * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.4426950408889634f * z1));
-        pk[e] = pack2_bf16(z0, z1);
+        pk[e] = pack2_bf16_asm(z0, z1);
       }
       *reinterpret_cast<uint4*>(out + (row0 + t) * ldo + c0) = make_uint4(pk[0], pk[1], pk[2], pk[3]);
     }
@@ -722,7 +678,7 @@ __global__ __launch_bounds__(256) void convmodule_mid_kernel(const uint16_t* __r
       float z1 = acc[2 * e + 1] * sc[2 * e + 1] + sh[2 * e + 1];
       z0 = z0 * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.4426950408889634f * z0));
       z1 = z1 * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.4426950408889634f * z1));
-      pk[e] = pack2_bf16(z0, z1);
+      pk[e] = pack2_bf16_asm(z0, z1);
     }
     *reinterpret_cast<uint4*>(out + (row0 + t) * ldo + c0) = make_uint4(pk[0], pk[1], pk[2], pk[3]);
   }

@@ -23,14 +23,10 @@
 
 #include "../../include/mindaudio_amd.h"
 
+#include "device_common.h"
 #include "launch.h"
 
 namespace ma {
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((address_space(3))) void lds_void_t;
-typedef __attribute__((address_space(1))) const void gl_void_t;
 
 constexpr int kDiBM = 128, kDiBN = 128, kDiBK = 64, kDiStages = 2, kDiThreads = 256;
 constexpr int kDiStageBytes = (kDiBM + kDiBN) * kDiBK * 2;
@@ -45,12 +41,6 @@ struct DinParams {
   int32_t B, H, Wd, C, Ho, Wo;
   int32_t tiles_m[4];    // row tiles of class (ph, pw) = index 2 ph + pw
 };
-
-__device__ __forceinline__ uint32_t di_pack_bf16(float lo, float hi) {
-  uint32_t r;
-  asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(lo), "v"(hi));
-  return r;
-}
 
 __global__ __launch_bounds__(kDiThreads, 2) void conv2_dinput_kernel(const DinParams p) {
   constexpr int FM = kDiBM / 32, FN = kDiBN / 32, GA = kDiBM / 32, GW = kDiBN / 32;
@@ -102,11 +92,11 @@ __global__ __launch_bounds__(kDiThreads, 2) void conv2_dinput_kernel(const DinPa
 #pragma unroll
     for (int g = 0; g < GA; ++g) {
       const uint16_t* src = ((vmask[g] >> tap) & 1u) ? a_src[g] + ka : zsrc;
-      __builtin_amdgcn_global_load_lds((gl_void_t*)src, (lds_void_t*)(st + (wave + 4 * g) * 1024), 16, 0, 0);
+      __builtin_amdgcn_global_load_lds((gl_cvoid_t*)src, (lds_void_t*)(st + (wave + 4 * g) * 1024), 16, 0, 0);
     }
 #pragma unroll
     for (int g = 0; g < GW; ++g)
-      __builtin_amdgcn_global_load_lds((gl_void_t*)(w_src[g] + kw), (lds_void_t*)(st + kDiBM * 128 + (wave + 4 * g) * 1024), 16, 0, 0);
+      __builtin_amdgcn_global_load_lds((gl_cvoid_t*)(w_src[g] + kw), (lds_void_t*)(st + kDiBM * 128 + (wave + 4 * g) * 1024), 16, 0, 0);
   };
 
   f32x4 acc[FM][FN];
@@ -154,7 +144,7 @@ __global__ __launch_bounds__(kDiThreads, 2) void conv2_dinput_kernel(const DinPa
 #pragma unroll
     for (int j = 0; j < FN; ++j)
       *reinterpret_cast<uint2*>(smem + (wm * (kDiBM / 2) + i * 16 + em) * kRow + (wn * (kDiBN / 2) + j * 16 + en) * 2) =
-          make_uint2(di_pack_bf16(acc[i][j][0], acc[i][j][1]), di_pack_bf16(acc[i][j][2], acc[i][j][3]));
+          make_uint2(pack2_bf16_asm(acc[i][j][0], acc[i][j][1]), pack2_bf16_asm(acc[i][j][2], acc[i][j][3]));
   __syncthreads();
   constexpr int kChunks = kDiBN * 2 / 16;  // 16 lanes per row
   for (int cidx = tid; cidx < kDiBM * kChunks; cidx += kDiThreads) {
@@ -189,13 +179,6 @@ MA_LDS_ATTR(conv2_dinput_kernel, kDiLds);
 constexpr int kD8Threads = 512, kD8Unit = 128 * 128, kD8Buf = 4 * kD8Unit;
 constexpr int kD8CRow = 256 * 2 + 16, kD8Lds = 256 * kD8CRow;  // 132 KiB: the staged output tile (>= the two 64 KiB buffers)
 
-__device__ __forceinline__ int d8_div(int m, int d, float inv) {  // floor(m / d) for 0 <= m < 2^24
-  int q = (int)((float)m * inv);
-  if (q * d > m) --q;
-  if ((q + 1) * d <= m) ++q;
-  return q;
-}
-
 __global__ __launch_bounds__(kD8Threads, 1) void conv2_dinput8_kernel(const DinParams p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63;
@@ -221,8 +204,8 @@ __global__ __launch_bounds__(kD8Threads, 1) void conv2_dinput8_kernel(const DinP
       const int u = 8 * (wid + 8 * i) + lr;
       int m = m0 + (u >> 6) * 128 + 64 * q + (u & 63);
       if (m >= Mc) m = Mc - 1;  // rows past the class: computed, never stored
-      const int t = d8_div(m, Wc, inv_wc), ww = m - t * Wc;
-      const int b = d8_div(t, Hc, inv_hc), hh = t - b * Hc;
+      const int t = div_small(m, Wc, inv_wc), ww = m - t * Wc;
+      const int b = div_small(t, Hc, inv_hc), hh = t - b * Hc;
       a_src[q][i] = p.dy + (((int64_t)b * p.Ho + hh) * p.Wo + ww) * p.C + kc_src * 8;
       uint32_t vm = 0;
       for (int tap = 0; tap < ntaps; ++tap) {
@@ -247,14 +230,14 @@ __global__ __launch_bounds__(kD8Threads, 1) void conv2_dinput8_kernel(const DinP
       const int64_t ka = -((int64_t)ih * p.Wo + iw) * p.C + kin;
       const uint16_t* s0 = ((vmask[q][0] >> tap) & 1u) ? a_src[q][0] + ka : zsrc;
       const uint16_t* s1 = ((vmask[q][1] >> tap) & 1u) ? a_src[q][1] + ka : zsrc;
-      __builtin_amdgcn_global_load_lds((gl_void_t*)s0, (lds_void_t*)dst, 16, 0, 0);
-      __builtin_amdgcn_global_load_lds((gl_void_t*)s1, (lds_void_t*)(dst + 8192), 16, 0, 0);
+      __builtin_amdgcn_global_load_lds((gl_cvoid_t*)s0, (lds_void_t*)dst, 16, 0, 0);
+      __builtin_amdgcn_global_load_lds((gl_cvoid_t*)s1, (lds_void_t*)(dst + 8192), 16, 0, 0);
     } else {
       constexpr int q = U == 2;
       const int khw = (ph ? 1 : 2 * ih) * 3 + (pw ? 1 : 2 * iw);
       const int64_t kw = (int64_t)khw * p.C * p.C + kin;
-      __builtin_amdgcn_global_load_lds((gl_void_t*)(w_src[q][0] + kw), (lds_void_t*)dst, 16, 0, 0);
-      __builtin_amdgcn_global_load_lds((gl_void_t*)(w_src[q][1] + kw), (lds_void_t*)(dst + 8192), 16, 0, 0);
+      __builtin_amdgcn_global_load_lds((gl_cvoid_t*)(w_src[q][0] + kw), (lds_void_t*)dst, 16, 0, 0);
+      __builtin_amdgcn_global_load_lds((gl_cvoid_t*)(w_src[q][1] + kw), (lds_void_t*)(dst + 8192), 16, 0, 0);
     }
   };
   const int frow = lane & 15, fk = lane >> 4;
@@ -342,8 +325,8 @@ __global__ __launch_bounds__(kD8Threads, 1) void conv2_dinput8_kernel(const DinP
   auto row_off = [&](int r) __attribute__((always_inline)) -> int64_t {  // element offset of tile row r in act / out; < 0: past the class
     const int m = m0 + r;
     if (m >= Mc) return -1;
-    const int t = d8_div(m, Wc, inv_wc), ww = m - t * Wc;
-    const int b = d8_div(t, Hc, inv_hc), hh = t - b * Hc;
+    const int t = div_small(m, Wc, inv_wc), ww = m - t * Wc;
+    const int b = div_small(t, Hc, inv_hc), hh = t - b * Hc;
     return ((((int64_t)b * p.H + 2 * hh + ph) * p.Wd) + 2 * ww + pw) * p.C + cc * 8;
   };
   uint4 av[16];
@@ -361,7 +344,7 @@ __global__ __launch_bounds__(kD8Threads, 1) void conv2_dinput8_kernel(const DinP
 #pragma unroll
     for (int j = 0; j < 4; ++j)
       *reinterpret_cast<uint2*>(smem + (wr * 128 + i * 16 + em) * kD8CRow + (wc * 64 + j * 16 + en) * 2) =
-          make_uint2(di_pack_bf16(acc[i][j][0], acc[i][j][1]), di_pack_bf16(acc[i][j][2], acc[i][j][3]));
+          make_uint2(pack2_bf16_asm(acc[i][j][0], acc[i][j][1]), pack2_bf16_asm(acc[i][j][2], acc[i][j][3]));
   __syncthreads();
 #pragma unroll
   for (int k = 0; k < 16; ++k) {

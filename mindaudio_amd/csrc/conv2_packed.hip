@@ -16,29 +16,13 @@
 #include <stdlib.h>
 
 #include <type_traits>
-#include <utility>
 
 #include "../../include/mindaudio_amd.h"
 
+#include "device_common.h"
 #include "launch.h"
 
 namespace ma {
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
-typedef __attribute__((ext_vector_type(2))) float f32x2;
-typedef __attribute__((address_space(3))) void lds_void_t;
-typedef __attribute__((address_space(1))) const void gl_void_t;
-
-template <int... Is, class F>
-__device__ __forceinline__ void c2_static_for_impl(std::integer_sequence<int, Is...>, F&& f) {
-  (f(std::integral_constant<int, Is>{}), ...);
-}
-template <int N, class F>
-__device__ __forceinline__ void c2_static_for(F&& f) {
-  c2_static_for_impl(std::make_integer_sequence<int, N>{}, f);
-}
 
 constexpr int kC2Rows = 128, kC2C = 256, kC2N = 256, kC2Threads = 256;
 constexpr int kC2Chunks = 9 * kC2C / 64;      // 36 K-chunks of 64
@@ -53,11 +37,6 @@ struct Conv2PackedParams {
   int32_t M, H, Wd, Ho, Wo;
   int32_t relu;
 };
-
-__device__ __forceinline__ uint32_t c2_pack_bf16(float lo, float hi) {
-  const bf16x2 r = __builtin_convertvector((f32x2){lo, hi}, bf16x2);
-  return *reinterpret_cast<const uint32_t*>(&r);
-}
 
 // item (wave w, chunk c, k-step kk, tile jt): lane (i, g) holds W[64 w + 16 jt + i][64 c + 32 kk + 8 g .. + 8], k = (kh, kw, ch)
 __global__ void conv2_pack_kernel(const uint16_t* __restrict__ w, uint4* __restrict__ out) {
@@ -94,7 +73,7 @@ __global__ __launch_bounds__(kC2Threads, 2) void conv2_packed_kernel(const Conv2
     const int64_t koff = ((int64_t)kh * p.Wd + kw) * kC2C + (cc & 3) * 64;
 #pragma unroll
     for (int i = 0; i < 4; ++i)
-      __builtin_amdgcn_global_load_lds((gl_void_t*)(a_src[i] + koff),
+      __builtin_amdgcn_global_load_lds((gl_cvoid_t*)(a_src[i] + koff),
                                        (lds_void_t*)(smem + stage * kC2Stage + (wave + 4 * i) * 1024), 16, 0, 0);
   };
   // ---- weight fragments: SGPR chunk base + lane offset, 8 per chunk, register ring of 16 -----------------------------------------
@@ -144,7 +123,7 @@ __global__ __launch_bounds__(kC2Threads, 2) void conv2_packed_kernel(const Conv2
     C2_LDS(0, 0); C2_LDS(0, 1); C2_LDS(0, 2); C2_LDS(0, 3); C2_LDS(0, 4); C2_LDS(0, 5); C2_LDS(0, 6); C2_LDS(0, 7);
     C2_LDS(1, 0); C2_LDS(1, 1); C2_LDS(1, 2); C2_LDS(1, 3); C2_LDS(1, 4); C2_LDS(1, 5); C2_LDS(1, 6); C2_LDS(1, 7);
 #undef C2_LDS
-    c2_static_for<2>([&](auto kc) __attribute__((always_inline)) {
+    static_for<2>([&](auto kc) __attribute__((always_inline)) {
       constexpr int kk = decltype(kc)::value;
       if constexpr (kk == 0)
         asm volatile("s_waitcnt lgkmcnt(8)"
@@ -154,11 +133,11 @@ __global__ __launch_bounds__(kC2Threads, 2) void conv2_packed_kernel(const Conv2
         asm volatile("s_waitcnt lgkmcnt(0)"
                      : "+v"(af[1][0]), "+v"(af[1][1]), "+v"(af[1][2]), "+v"(af[1][3]), "+v"(af[1][4]), "+v"(af[1][5]),
                        "+v"(af[1][6]), "+v"(af[1][7])::"memory");
-      c2_static_for<4>([&](auto tc) __attribute__((always_inline)) {
+      static_for<4>([&](auto tc) __attribute__((always_inline)) {
         constexpr int jt = decltype(tc)::value;
         constexpr int q = kk * 4 + jt;
         asm volatile("s_waitcnt vmcnt(11)" : "+v"(ring[q])::"memory");
-        c2_static_for<8>([&](auto sc) __attribute__((always_inline)) {
+        static_for<8>([&](auto sc) __attribute__((always_inline)) {
           constexpr int s = decltype(sc)::value;
           acc[jt][s] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ring[q], af[kk][s], acc[jt][s], 0, 0, 0);
         });
@@ -199,7 +178,7 @@ __global__ __launch_bounds__(kC2Threads, 2) void conv2_packed_kernel(const Conv2
         v3 = fmaxf(v3, 0.f);
       }
       // (plain stores: written through (sc0 sc1), these 8-byte pieces cost +2.6 % of the whole step)
-      *reinterpret_cast<uint2*>(orow + 16 * jt) = make_uint2(c2_pack_bf16(v0, v1), c2_pack_bf16(v2, v3));
+      *reinterpret_cast<uint2*>(orow + 16 * jt) = make_uint2(pack2_bf16(v0, v1), pack2_bf16(v2, v3));
     }
   }
 }

@@ -13,22 +13,13 @@
 
 #include "../../include/mindaudio_amd.h"
 
+#include "device_common.h"
 #include "launch.h"
 
 namespace ma {
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
-typedef __attribute__((ext_vector_type(2))) float f32x2;
-
 constexpr int kCpTile = 32, kCpC = 256, kCpMaxK = 15, kCpPitch = 544;
 
-__device__ __forceinline__ float cp_from_bf16(uint32_t h) { return __builtin_bit_cast(float, h << 16); }
-__device__ __forceinline__ uint32_t cp_pack_bf16(float lo, float hi) {
-  const bf16x2 r = __builtin_convertvector((f32x2){lo, hi}, bf16x2);
-  return *reinterpret_cast<const uint32_t*>(&r);
-}
 __device__ __forceinline__ float cp_sigmoid_mul(float v, float gate) {
   return v * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.4426950408889634f * gate));
 }
@@ -67,8 +58,8 @@ __global__ __launch_bounds__(256, 2) void convmid_pw2_kernel(const ConvPw2Params
       const uint32_t aw[4] = {av.x, av.y, av.z, av.w}, gw[4] = {gv.x, gv.y, gv.z, gv.w};
 #pragma unroll
       for (int e = 0; e < 4; ++e) {  // layers/glu.py:24-28: out * sigmoid(gate)
-        gl[2 * e] = cp_sigmoid_mul(cp_from_bf16(aw[e] & 0xffff), cp_from_bf16(gw[e] & 0xffff));
-        gl[2 * e + 1] = cp_sigmoid_mul(cp_from_bf16(aw[e] >> 16), cp_from_bf16(gw[e] >> 16));
+        gl[2 * e] = cp_sigmoid_mul(bf2f_lo(aw[e] & 0xffff), bf2f_lo(gw[e] & 0xffff));
+        gl[2 * e + 1] = cp_sigmoid_mul(bf2f_lo(aw[e] >> 16), bf2f_lo(gw[e] >> 16));
       }
     }
     float4* dst = reinterpret_cast<float4*>(glu + i * 256 + c0);
@@ -127,7 +118,7 @@ __global__ __launch_bounds__(256, 2) void convmid_pw2_kernel(const ConvPw2Params
       for (int e = 0; e < 4; ++e) {
         const float z0 = acc[o][2 * e] * sc[2 * e] + sh[2 * e];
         const float z1 = acc[o][2 * e + 1] * sc[2 * e + 1] + sh[2 * e + 1];
-        pk[e] = cp_pack_bf16(cp_sigmoid_mul(z0, z0), cp_sigmoid_mul(z1, z1));
+        pk[e] = pack2_bf16(cp_sigmoid_mul(z0, z0), cp_sigmoid_mul(z1, z1));
       }
       zrow[o] = make_uint4(pk[0], pk[1], pk[2], pk[3]);
     }
@@ -185,7 +176,6 @@ __global__ __launch_bounds__(256, 2) void convmid_pw2_kernel(const ConvPw2Params
   }
 }
 
-
 // ---- the whole ConvolutionModule after its LayerNorm in one launch (convolution.py:96-127 + the block's residual) --------------
 //     y = glu(a . Wp1^T + bp1);  z = swish(bn(depthwise_k(y)));  x[m, :] += mask[m] * (z[m, :] . Wp2^T + bp2)
 // pointwise_conv1 is run by the workgroup itself on the 32 + k - 1 <= 46 (padded to 48) frames its 32-frame tile needs: the
@@ -239,28 +229,11 @@ struct ConvModParams {
   float ln_eps;
 };
 
-// x[l] + x[l ^ 16] and x[l] + x[l ^ 32] in every lane through gfx950's row swaps (see ffn_packed.hip; tools/ubench/permlane_test.hip)
-__device__ __forceinline__ float cp_sum_xor16(float x) {
-  float a = x, b = x;
-  asm volatile("s_nop 1\n\tv_permlane16_swap_b32 %0, %1" : "+v"(a), "+v"(b));
-  return a + b;
-}
-__device__ __forceinline__ float cp_sum_xor32(float x) {
-  float a = x, b = x;
-  asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(a), "+v"(b));
-  return a + b;
-}
-
 // Phase stamps for tools/convmod_timeline.py (compiled in only with -DMA_CM_PROF): wave 0 of three workgroups keeps wall_clock64()
 // (100 MHz) values in SGPRs and writes them out at the end of the kernel.
 #ifdef MA_CM_PROF
 __device__ unsigned long long g_cm_prof[3 * 16];
-#define CM_STAMP(k)                                    \
-  do {                                                 \
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); \
-    cm_ts[(k)] = wall_clock64();                       \
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); \
-  } while (0)
+#define CM_STAMP(k) MA_PHASE_STAMP(cm_ts, k)
 #else
 #define CM_STAMP(k) do { } while (0)
 #endif
@@ -392,7 +365,7 @@ __global__ __launch_bounds__(256, 2) void convmodule_kernel(const ConvModParams 
 #pragma unroll
     for (int s = 0; s < 4; ++s) {
       // (row swaps instead of __shfl_xor: 16 ds_bpermute round trips in a row were ~1.5 us of this phase)
-      const float a = cp_sum_xor32(cp_sum_xor16(rsum[s])), b = cp_sum_xor32(cp_sum_xor16(rsq[s]));
+      const float a = sum_xor32(sum_xor16(rsum[s])), b = sum_xor32(sum_xor16(rsq[s]));
       if (g == 0) {
         red[wave * 64 + 16 * s + c] = a;
         red[256 + wave * 64 + 16 * s + c] = b;
@@ -415,8 +388,8 @@ __global__ __launch_bounds__(256, 2) void convmodule_kernel(const ConvModParams 
         const float4 be = *reinterpret_cast<const float4*>(reinterpret_cast<const float*>(smem + L::kOffPar0) + 256 + n);
         const f32x4 v = acc[jt][s];
         *reinterpret_cast<uint2*>(smem + r * kCpPitch + n * 2) =
-            make_uint2(cp_pack_bf16(((v[0] - mean) * inv * ga.x + be.x) * msk[s], ((v[1] - mean) * inv * ga.y + be.y) * msk[s]),
-                       cp_pack_bf16(((v[2] - mean) * inv * ga.z + be.z) * msk[s], ((v[3] - mean) * inv * ga.w + be.w) * msk[s]));
+            make_uint2(pack2_bf16(((v[0] - mean) * inv * ga.x + be.x) * msk[s], ((v[1] - mean) * inv * ga.y + be.y) * msk[s]),
+                       pack2_bf16(((v[2] - mean) * inv * ga.z + be.z) * msk[s], ((v[3] - mean) * inv * ga.w + be.w) * msk[s]));
       }
     }
 #pragma unroll
@@ -467,7 +440,7 @@ __global__ __launch_bounds__(256, 2) void convmodule_kernel(const ConvModParams 
         const float y1 = live ? cp_sigmoid_mul(a2[0][s][1] + bvv.y, a2[1][s][1] + bg.y) : 0.f;
         const float y2 = live ? cp_sigmoid_mul(a2[0][s][2] + bvv.z, a2[1][s][2] + bg.z) : 0.f;
         const float y3 = live ? cp_sigmoid_mul(a2[0][s][3] + bvv.w, a2[1][s][3] + bg.w) : 0.f;
-        *reinterpret_cast<uint2*>(ytile + (16 * s + c) * kCmYPitch + n * 2) = make_uint2(cp_pack_bf16(y0, y1), cp_pack_bf16(y2, y3));
+        *reinterpret_cast<uint2*>(ytile + (16 * s + c) * kCmYPitch + n * 2) = make_uint2(pack2_bf16(y0, y1), pack2_bf16(y2, y3));
       }
     }
 #undef CM_LOAD_SP
@@ -528,7 +501,7 @@ __global__ __launch_bounds__(256, 2) void convmodule_kernel(const ConvModParams 
         const float y1 = live ? cp_sigmoid_mul(acc[jt][s][1] + bv.y, acc[jt + 2][s][1] + bg.y) : 0.f;
         const float y2 = live ? cp_sigmoid_mul(acc[jt][s][2] + bv.z, acc[jt + 2][s][2] + bg.z) : 0.f;
         const float y3 = live ? cp_sigmoid_mul(acc[jt][s][3] + bv.w, acc[jt + 2][s][3] + bg.w) : 0.f;
-        *reinterpret_cast<uint2*>(ytile + (16 * s + c) * kCmYPitch + n * 2) = make_uint2(cp_pack_bf16(y0, y1), cp_pack_bf16(y2, y3));
+        *reinterpret_cast<uint2*>(ytile + (16 * s + c) * kCmYPitch + n * 2) = make_uint2(pack2_bf16(y0, y1), pack2_bf16(y2, y3));
       }
     }
   }
@@ -565,8 +538,8 @@ __global__ __launch_bounds__(256, 2) void convmodule_kernel(const ConvModParams 
     for (int r = 0; r < kCpMaxK + 3; ++r) {  // y row i0 + r feeds output o with tap k = r - o
       if (r < KS + 3) {
         const uint4 q = *reinterpret_cast<const uint4*>(ytile + (i0 + r) * kCmYPitch + c0 * 2);
-        const float gv[8] = {cp_from_bf16(q.x & 0xffff), cp_from_bf16(q.x >> 16), cp_from_bf16(q.y & 0xffff), cp_from_bf16(q.y >> 16),
-                             cp_from_bf16(q.z & 0xffff), cp_from_bf16(q.z >> 16), cp_from_bf16(q.w & 0xffff), cp_from_bf16(q.w >> 16)};
+        const float gv[8] = {bf2f_lo(q.x & 0xffff), bf2f_lo(q.x >> 16), bf2f_lo(q.y & 0xffff), bf2f_lo(q.y >> 16),
+                             bf2f_lo(q.z & 0xffff), bf2f_lo(q.z >> 16), bf2f_lo(q.w & 0xffff), bf2f_lo(q.w >> 16)};
 #pragma unroll
         for (int o = 0; o < 4; ++o) {
           const int k = r - o;
@@ -595,7 +568,7 @@ __global__ __launch_bounds__(256, 2) void convmodule_kernel(const ConvModParams 
       for (int e = 0; e < 4; ++e) {
         const float z0 = acc[o][2 * e] * sc[2 * e] + sh[2 * e];
         const float z1 = acc[o][2 * e + 1] * sc[2 * e + 1] + sh[2 * e + 1];
-        pk[e] = cp_pack_bf16(cp_sigmoid_mul(z0, z0), cp_sigmoid_mul(z1, z1));
+        pk[e] = pack2_bf16(cp_sigmoid_mul(z0, z0), cp_sigmoid_mul(z1, z1));
       }
       zrow[o] = make_uint4(pk[0], pk[1], pk[2], pk[3]);
     }
@@ -872,7 +845,7 @@ __global__ __launch_bounds__(kCm64Threads, 1) void convmodule64_kernel(const Con
       float rs = 0.f, rq = 0.f;
       rs += ps[s][0]; rs += ps[s][1]; rs += o.x; rs += o.y;
       rq += pq[s][0]; rq += pq[s][1]; rq += o.z; rq += o.w;
-      const float a = cp_sum_xor32(cp_sum_xor16(rs)), q = cp_sum_xor32(cp_sum_xor16(rq));
+      const float a = sum_xor32(sum_xor16(rs)), q = sum_xor32(sum_xor16(rq));
       if (g == 0) {
         wsum[(16 * s + c) * 4 + (wave >> 1)] = a;
         wsum[kCm64Rows * 4 + (16 * s + c) * 4 + (wave >> 1)] = q;
@@ -897,8 +870,8 @@ __global__ __launch_bounds__(kCm64Threads, 1) void convmodule64_kernel(const Con
       const float4 be = *reinterpret_cast<const float4*>(par0 + 256 + n);
       const f32x4 v = acc[jt][s];
       *reinterpret_cast<uint2*>(smem + r * kCpPitch + n * 2) =
-          make_uint2(cp_pack_bf16(((v[0] - mean) * inv * ga.x + be.x) * msk[s], ((v[1] - mean) * inv * ga.y + be.y) * msk[s]),
-                     cp_pack_bf16(((v[2] - mean) * inv * ga.z + be.z) * msk[s], ((v[3] - mean) * inv * ga.w + be.w) * msk[s]));
+          make_uint2(pack2_bf16(((v[0] - mean) * inv * ga.x + be.x) * msk[s], ((v[1] - mean) * inv * ga.y + be.y) * msk[s]),
+                     pack2_bf16(((v[2] - mean) * inv * ga.z + be.z) * msk[s], ((v[3] - mean) * inv * ga.w + be.w) * msk[s]));
     }
   }
   // x' of the own frames t0 + 16 s + c in the epilogue's layout: row 16 s + c + 8 = lane c ^ 8 of row tile s (c < 8) or s + 1
@@ -947,7 +920,7 @@ __global__ __launch_bounds__(kCm64Threads, 1) void convmodule64_kernel(const Con
       const float y1 = live ? cp_sigmoid_mul(a2[0][s][1] + bvv.y, a2[1][s][1] + bg.y) : 0.f;
       const float y2 = live ? cp_sigmoid_mul(a2[0][s][2] + bvv.z, a2[1][s][2] + bg.z) : 0.f;
       const float y3 = live ? cp_sigmoid_mul(a2[0][s][3] + bvv.w, a2[1][s][3] + bg.w) : 0.f;
-      *reinterpret_cast<uint2*>(ytile + (16 * s + c) * kCmYPitch + n * 2) = make_uint2(cp_pack_bf16(y0, y1), cp_pack_bf16(y2, y3));
+      *reinterpret_cast<uint2*>(ytile + (16 * s + c) * kCmYPitch + n * 2) = make_uint2(pack2_bf16(y0, y1), pack2_bf16(y2, y3));
     }
   }
 #undef CM64_LOAD_SP
@@ -1002,7 +975,7 @@ __global__ __launch_bounds__(kCm64Threads, 1) void convmodule64_kernel(const Con
     for (int r = 0; r < kCpMaxK + 7; ++r) {  // y row r feeds output o with tap k = r - o
       if (r < KS + 7) {
         const uint2 q = *reinterpret_cast<const uint2*>(yb + r * kCmYPitch);
-        const float gv[4] = {cp_from_bf16(q.x & 0xffff), cp_from_bf16(q.x >> 16), cp_from_bf16(q.y & 0xffff), cp_from_bf16(q.y >> 16)};
+        const float gv[4] = {bf2f_lo(q.x & 0xffff), bf2f_lo(q.x >> 16), bf2f_lo(q.y & 0xffff), bf2f_lo(q.y >> 16)};
 #pragma unroll
         for (int o = 0; o < 8; ++o) {
           const int k = r - o;
@@ -1020,7 +993,7 @@ __global__ __launch_bounds__(kCm64Threads, 1) void convmodule64_kernel(const Con
       const float z0 = dacc[o][0] * sc.x + sh.x, z1 = dacc[o][1] * sc.y + sh.y;
       const float z2 = dacc[o][2] * sc.z + sh.z, z3 = dacc[o][3] * sc.w + sh.w;
       *reinterpret_cast<uint2*>(smem + (rg * 8 + o) * kCpPitch + c0 * 2) =  // z tile over the a-tile
-          make_uint2(cp_pack_bf16(cp_sigmoid_mul(z0, z0), cp_sigmoid_mul(z1, z1)), cp_pack_bf16(cp_sigmoid_mul(z2, z2), cp_sigmoid_mul(z3, z3)));
+          make_uint2(pack2_bf16(cp_sigmoid_mul(z0, z0), cp_sigmoid_mul(z1, z1)), pack2_bf16(cp_sigmoid_mul(z2, z2), cp_sigmoid_mul(z3, z3)));
     }
   }
   __syncthreads();

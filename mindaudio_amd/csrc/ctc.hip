@@ -12,20 +12,11 @@
 
 #include "../../include/mindaudio_amd.h"
 
+#include "device_common.h"
 #include "launch.h"
 
 namespace ma {
 
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, 64));
-  return v;
-}
-__device__ __forceinline__ float wave_add(float v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
 __device__ __forceinline__ float log_add(float a, float b) {
   const float m = fmaxf(a, b);
   if (m == -INFINITY) return -INFINITY;
@@ -78,7 +69,7 @@ __global__ __launch_bounds__(256) void ctc_lse_kernel(const float* __restrict__ 
     float s = 0.f;
 #pragma unroll
     for (int k = 0; k < kLseRegQ; ++k) s += (expf(r[k].x - m) + expf(r[k].y - m)) + (expf(r[k].z - m) + expf(r[k].w - m));
-    s = wave_add(s);
+    s = wave_sum(s);
     if (lane == 0) lse[row] = m + logf(s);
     return;
   }
@@ -87,7 +78,7 @@ __global__ __launch_bounds__(256) void ctc_lse_kernel(const float* __restrict__ 
   m = wave_max(m);
   float s = 0.f;
   for (int v = lane; v < V; v += 64) s += expf(p[v] - m);
-  s = wave_add(s);
+  s = wave_sum(s);
   if (lane == 0) lse[row] = m + logf(s);
 }
 
@@ -196,7 +187,7 @@ __device__ __forceinline__ void ctc_alpha_body(const float* __restrict__ logits,
     if (s == S - 1 || (s == S - 2 && S > 1)) fin = log_add(fin, alpha[c]);
   }
   float m = wave_max(fin);
-  float sum = wave_add(fin == -INFINITY ? 0.0f : expf(fin - m));
+  float sum = wave_sum(fin == -INFINITY ? 0.0f : expf(fin - m));
   if (lane == 0) loss[b] = (m == -INFINITY) ? INFINITY : -(m + logf(sum));
 }
 
@@ -318,6 +309,7 @@ __global__ __launch_bounds__(64) void ctc_alpha_beta_kernel(const float* __restr
 // Backward, step 2: one workgroup per (b, t) row: dlogits[v] = scale * (softmax[v] - sum_{s: l'_s = v} w_t(s)) as bf16;
 // rows past the utterance's length, and utterances with an infinite loss (zero_infinity), get zeros.  Columns
 // [V, ld_out) are zeroed (GEMM K padding).
+// (not f2bf: no NaN branch - a private copy because f2bf in its place changes this file's device code)
 __device__ __forceinline__ uint32_t dlogit_bits(float g) {  // bf16, round to nearest even
   uint32_t u = __float_as_uint(g);
   u += 0x7fffu + ((u >> 16) & 1u);
@@ -432,7 +424,7 @@ __global__ __launch_bounds__(256) void ctc_greedy_kernel(const float* __restrict
   }
   float s = 0.f;
   for (int v = lane; v < V; v += 64) s += expf(p[v] - m);
-  s = wave_add(s);
+  s = wave_sum(s);
   if (lane == 0) {
     const bool keep = !mask || mask[row] != 0.0f;
     best[row] = keep ? am : 0;
@@ -474,10 +466,7 @@ __global__ void ctc_reduce_kernel(const float* __restrict__ loss, int B, int zer
 __global__ __launch_bounds__(256) void cast_f32_bf16_kernel(const float* __restrict__ x, uint16_t* __restrict__ y, int64_t n4) {
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) {
     const float4 v = reinterpret_cast<const float4*>(x)[i];
-    uint32_t lo, hi;
-    asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(lo) : "v"(v.x), "v"(v.y));
-    asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(hi) : "v"(v.z), "v"(v.w));
-    reinterpret_cast<uint2*>(y)[i] = make_uint2(lo, hi);
+    reinterpret_cast<uint2*>(y)[i] = make_uint2(pack2_bf16_asm(v.x, v.y), pack2_bf16_asm(v.z, v.w));
   }
 }
 

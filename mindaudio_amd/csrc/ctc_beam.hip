@@ -14,6 +14,7 @@
 
 #include "../../include/mindaudio_amd.h"
 
+#include "device_common.h"
 #include "launch.h"
 
 namespace ma {
@@ -26,22 +27,6 @@ constexpr uint64_t kBmHashMul = 0x9E3779B97F4A7C15ull;
 
 __device__ __forceinline__ bool cb_better(float v, int i, float w, int j) { return v > w || (v == w && i < j); }
 
-__device__ __forceinline__ float cb_wave_max(float v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, 64));
-  return v;
-}
-__device__ __forceinline__ float cb_wave_add(float v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-__device__ __forceinline__ double cb_wave_add_f64(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-
 // One wave per row: logp = (x - max) - log(sum exp(x - max)) in float32, each lane keeps the 16 best (logp, index) of its columns in
 // a sorted register list (columns visited in ascending order, so equal values keep the lower index first), then k rounds of a wave
 // arg-max over the lanes' heads; the winning lane pops its head.
@@ -53,10 +38,10 @@ __global__ __launch_bounds__(256) void ctc_topk_kernel(const float* __restrict__
   const float* p = logits + row * ld;
   float m = -INFINITY;
   for (int v = lane; v < V; v += 64) m = fmaxf(m, p[v]);
-  m = cb_wave_max(m);
+  m = wave_max(m);
   float s = 0.0f;
   for (int v = lane; v < V; v += 64) s += expf(p[v] - m);
-  const float lse = logf(cb_wave_add(s));
+  const float lse = logf(wave_sum(s));
   float val[kTkList];
   int idx[kTkList];
 #pragma unroll
@@ -329,10 +314,10 @@ __global__ __launch_bounds__(256) void hyp_term_kernel(const float* __restrict__
   const float* p = logits + row * ld;
   float m = -INFINITY;
   for (int v = lane; v < V; v += 64) m = fmaxf(m, p[v]);
-  m = cb_wave_max(m);
+  m = wave_max(m);
   double s = 0.0;
   for (int v = lane; v < V; v += 64) s += (double)expf(p[v] - m);
-  s = cb_wave_add_f64(s);
+  s = wave_sum(s);
   if (lane == 0) terms[row] = (tok >= 0 && tok < V) ? ((double)p[tok] - (double)m) - log(s) : NAN;
 }
 

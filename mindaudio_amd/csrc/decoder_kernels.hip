@@ -15,18 +15,14 @@
 
 #include "../../include/mindaudio_amd.h"
 
+#include "device_common.h"
 #include "launch.h"
 
 namespace ma {
 
-__device__ __forceinline__ float d_bf2f(uint16_t h) { return __uint_as_float((uint32_t)h << 16); }
-__device__ __forceinline__ uint16_t d_f2bf(float f) {
-  uint32_t u = __float_as_uint(f);
-  if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40);
-  u += 0x7fffu + ((u >> 16) & 1u);
-  return (uint16_t)(u >> 16);
-}
-__device__ __forceinline__ bool d_keep(uint32_t seed, uint32_t salt, uint64_t idx, uint32_t thresh) {  // = train_kernels.hip
+// The decoder's OWN dropout hash, one word per element - not the quad hash of the training kernels (train_common.h: drop_quad_hash /
+// keep_elem), which is a different function.  Its arithmetic decides the decoder's masks: changing it changes training results.
+__device__ __forceinline__ bool d_keep(uint32_t seed, uint32_t salt, uint64_t idx, uint32_t thresh) {
   uint32_t x = (uint32_t)idx ^ (seed * 0x9E3779B9u) ^ (salt * 0x85EBCA6Bu) ^ ((uint32_t)(idx >> 32) * 0xC2B2AE35u);
   x ^= x >> 16; x *= 0x7feb352du; x ^= x >> 15; x *= 0x846ca68bu; x ^= x >> 16;
   x += salt; x ^= x >> 16; x *= 0x7feb352du; x ^= x >> 15;
@@ -40,9 +36,9 @@ static uint32_t d_thresh(float p) {
 
 // activation element type of the small-attention / label-smoothing kernels: uint16_t = bf16 bit patterns (throughput mode) or float
 // (the float32 validation mode, entry points with the _x32 suffix)
-__device__ __forceinline__ float d_ld(const uint16_t* p) { return d_bf2f(*p); }
+__device__ __forceinline__ float d_ld(const uint16_t* p) { return bf2f(*p); }
 __device__ __forceinline__ float d_ld(const float* p) { return *p; }
-__device__ __forceinline__ void d_st(uint16_t* p, float v) { *p = d_f2bf(v); }
+__device__ __forceinline__ void d_st(uint16_t* p, float v) { *p = f2bf(v); }
 __device__ __forceinline__ void d_st(float* p, float v) { *p = v; }
 __device__ __forceinline__ void d_ld8(const uint16_t* p, float (&d)[8]) {  // 16-byte aligned
   const uint4 v = *reinterpret_cast<const uint4*>(p);
@@ -60,7 +56,7 @@ __device__ __forceinline__ void d_ld8(const float* p, float (&d)[8]) {
 __device__ __forceinline__ void d_st8(uint16_t* p, const float (&d)[8]) {
   uint32_t o[4];
 #pragma unroll
-  for (int e = 0; e < 4; ++e) o[e] = (uint32_t)d_f2bf(d[2 * e]) | ((uint32_t)d_f2bf(d[2 * e + 1]) << 16);
+  for (int e = 0; e < 4; ++e) o[e] = (uint32_t)f2bf(d[2 * e]) | ((uint32_t)f2bf(d[2 * e + 1]) << 16);
   *reinterpret_cast<uint4*>(p) = make_uint4(o[0], o[1], o[2], o[3]);
 }
 __device__ __forceinline__ void d_st8(float* p, const float (&d)[8]) {
@@ -207,13 +203,11 @@ struct SmallAttn {
 // products were 14 of the forward's 39 us and 14 of the backward's 46 us at 255 keys.
 typedef short sm_v4s __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) sm_v4s sm_lds_v4s;
-typedef __attribute__((ext_vector_type(8))) __bf16 sm_bf16x8;
-typedef __attribute__((ext_vector_type(4))) float sm_f32x4;
 __device__ __forceinline__ void sm_rows_times_tile(const float* S, int ss, const uint16_t (*X)[64], int Lq, int Lk, uint16_t* out,
                                                    int64_t ldo) {
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int lq = lane & 15, lg = lane >> 4, la = lq >> 2, lb = lq & 3;
-  sm_f32x4 acc[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
+  f32x4 acc[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
   const int nks = (Lk + 31) >> 5;
   for (int ks = 0; ks < nks; ++ks) {
     const uint16_t* x0 = &X[ks * 32 + lg * 8 + la][16 * w + lb * 4];
@@ -221,7 +215,7 @@ __device__ __forceinline__ void sm_rows_times_tile(const float* S, int ss, const
     const sm_v4s hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((sm_lds_v4s*)(x0 + 4 * 64));
     typedef short v8s __attribute__((ext_vector_type(8)));
     const v8s bv = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-    const sm_bf16x8 bfrag = __builtin_bit_cast(sm_bf16x8, bv);
+    const bf16x8 bfrag = __builtin_bit_cast(bf16x8, bv);
 #pragma unroll
     for (int qt = 0; qt < 2; ++qt) {
       const float* sr = S + (16 * qt + lq) * ss + ks * 32 + lg * 8;
@@ -230,10 +224,10 @@ __device__ __forceinline__ void sm_rows_times_tile(const float* S, int ss, const
       for (int e = 0; e < 4; ++e) {
         const int j = ks * 32 + lg * 8 + 2 * e;
         const float p0 = j < Lk ? sr[2 * e] : 0.0f, p1 = j + 1 < Lk ? sr[2 * e + 1] : 0.0f;
-        asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(pk[e]) : "v"(p0), "v"(p1));
+        pk[e] = pack2_bf16_asm(p0, p1);
       }
       const uint4 av = make_uint4(pk[0], pk[1], pk[2], pk[3]);
-      acc[qt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(sm_bf16x8, av), bfrag, acc[qt], 0, 0, 0);
+      acc[qt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, av), bfrag, acc[qt], 0, 0, 0);
     }
   }
   // lane (c = lq, g): rows q = 16 qt + 4 g + r, column 16 w + c
@@ -242,7 +236,7 @@ __device__ __forceinline__ void sm_rows_times_tile(const float* S, int ss, const
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int q = 16 * qt + 4 * lg + r;
-      if (q < Lq) out[(int64_t)q * ldo + 16 * w + lq] = d_f2bf(acc[qt][r]);
+      if (q < Lq) out[(int64_t)q * ldo + 16 * w + lq] = f2bf(acc[qt][r]);
     }
 }
 
@@ -508,13 +502,13 @@ __global__ __launch_bounds__(256) void mha_small_fwd_mfma_kernel(const SmallAttn
   // more: 24 us for a launch whose arithmetic is a few microseconds (B x heads = 160 workgroups of latency).
   // the K fragments of this wave's first kKf key tiles are requested first of all (they are used right behind the barrier)
   constexpr int kKf = 5;  // key tiles kt = wave + 4 i, i < kKf, held in registers (Lk <= 320: all of them)
-  sm_bf16x8 kfr[kKf][2];
+  bf16x8 kfr[kKf][2];
 #pragma unroll
   for (int i = 0; i < kKf; ++i) {
     const int key = (wave + 4 * i) * 16 + lq, keyc = key < Lk ? key : Lk - 1;
     const uint16_t* kp = p.k + ((int64_t)kb * Lk + keyc) * p.ldk + h * kSmD + lg * 8;
-    kfr[i][0] = *reinterpret_cast<const sm_bf16x8*>(kp);
-    kfr[i][1] = *reinterpret_cast<const sm_bf16x8*>(kp + 32);
+    kfr[i][0] = *reinterpret_cast<const bf16x8*>(kp);
+    kfr[i][1] = *reinterpret_cast<const bf16x8*>(kp + 32);
   }
   {
     const int i = tid, qi = i / (kSmD / 8), ch = i % (kSmD / 8);  // kSmQ * kSmD / 8 = 256 pieces: one per thread
@@ -542,7 +536,7 @@ __global__ __launch_bounds__(256) void mha_small_fwd_mfma_kernel(const SmallAttn
   int kti = 0;
   for (int kt = wave; kt * 16 < Lk; kt += 4, ++kti) {
     const int key = kt * 16 + lq, keyc = key < Lk ? key : Lk - 1;
-    sm_bf16x8 kf0, kf1;
+    bf16x8 kf0, kf1;
     if (kti < kKf) {  // (kti is wave-uniform; the unrolled select keeps the register array statically indexed)
       kf0 = kfr[0][0];
       kf1 = kfr[0][1];
@@ -554,8 +548,8 @@ __global__ __launch_bounds__(256) void mha_small_fwd_mfma_kernel(const SmallAttn
         }
     } else {
       const uint16_t* kp = p.k + ((int64_t)kb * Lk + keyc) * p.ldk + h * kSmD + lg * 8;
-      kf0 = *reinterpret_cast<const sm_bf16x8*>(kp);
-      kf1 = *reinterpret_cast<const sm_bf16x8*>(kp + 32);
+      kf0 = *reinterpret_cast<const bf16x8*>(kp);
+      kf1 = *reinterpret_cast<const bf16x8*>(kp + 32);
     }
     // the tile's mask values: unconditional loads (clamped indices), all in flight under the MFMAs - behind `if (q < Lq)` /
     // `continue` each of them was a round trip of its own (eight per tile with the (B, Lq, Lk) label mask)
@@ -570,12 +564,12 @@ __global__ __launch_bounds__(256) void mha_small_fwd_mfma_kernel(const SmallAttn
           mk2[qt][r] = p.mask[((int64_t)b * p.LqT + p.q0 + qc) * Lk + keyc];
         }
     }
-    sm_f32x4 sc[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
+    f32x4 sc[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
 #pragma unroll
     for (int qt = 0; qt < 2; ++qt) {
       const uint16_t* qr = Qb + (16 * qt + lq) * kPq + lg * 8;
-      sc[qt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(*reinterpret_cast<const sm_bf16x8*>(qr), kf0, sc[qt], 0, 0, 0);
-      sc[qt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(*reinterpret_cast<const sm_bf16x8*>(qr + 32), kf1, sc[qt], 0, 0, 0);
+      sc[qt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(*reinterpret_cast<const bf16x8*>(qr), kf0, sc[qt], 0, 0, 0);
+      sc[qt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(*reinterpret_cast<const bf16x8*>(qr + 32), kf1, sc[qt], 0, 0, 0);
     }
     if (key < Lk) {
       const float madd1 = (p.mask_mode == 1 && mk1 == 0.0f) ? -10000.0f : 0.0f;
@@ -647,11 +641,6 @@ MA_LDS_ATTR(mha_small_fwd_mfma_kernel, 163840);
 //   (attention_bwd.hip); a lane ends up with four consecutive features of its key: 8-byte stores.
 // As a thread-per-key FMA loop (192 values of row state in registers, 31 queries x 192 FMAs behind 48 LDS reads each) this phase
 // was ~17 us of the launch at 255 keys and 14 us at 31 keys, where 31 threads of 256 worked.
-__device__ __forceinline__ uint32_t sm_pack(float lo, float hi) {
-  uint32_t r;
-  asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(lo), "v"(hi));
-  return r;
-}
 __global__ __launch_bounds__(256) void mha_small_bwd_mfma_kernel(const SmallAttn<uint16_t> p, const float* __restrict__ probs,
                                                                  const uint16_t* __restrict__ ctx, int64_t ldc,
                                                                  const uint16_t* __restrict__ dctx, int64_t lddc,
@@ -743,17 +732,17 @@ __global__ __launch_bounds__(256) void mha_small_bwd_mfma_kernel(const SmallAttn
     const sm_v4s hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((sm_lds_v4s*)(a0 + 16 * kPq));
     typedef short v8s __attribute__((ext_vector_type(8)));
     const v8s v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-    return __builtin_bit_cast(sm_bf16x8, v);
+    return __builtin_bit_cast(bf16x8, v);
   };
   for (int kt = wave; kt * 16 < Lk; kt += 4) {
     const int key = kt * 16 + lq;
-    sm_f32x4 dp[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
+    f32x4 dp[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
 #pragma unroll
     for (int ks = 0; ks < 2; ++ks) {
-      const sm_bf16x8 vf = *reinterpret_cast<const sm_bf16x8*>(&Vs[key][ks * 32 + lg * 8]);
+      const bf16x8 vf = *reinterpret_cast<const bf16x8*>(&Vs[key][ks * 32 + lg * 8]);
 #pragma unroll
       for (int qt = 0; qt < 2; ++qt) {
-        const sm_bf16x8 of = *reinterpret_cast<const sm_bf16x8*>(dOb + (16 * qt + lq) * kPq + ks * 32 + lg * 8);
+        const bf16x8 of = *reinterpret_cast<const bf16x8*>(dOb + (16 * qt + lq) * kPq + ks * 32 + lg * 8);
         dp[qt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(of, vf, dp[qt], 0, 0, 0);
       }
     }
@@ -768,18 +757,18 @@ __global__ __launch_bounds__(256) void mha_small_bwd_mfma_kernel(const SmallAttn
         ds[qt][r] = in ? pv[qt][r] * (dp[qt][r] - Dq[q]) * p.scale : 0.0f;
         if (in) S[q * ss + key] = ds[qt][r];
       }
-    const uint4 ppk = make_uint4(sm_pack(pv[0][0], pv[0][1]), sm_pack(pv[0][2], pv[0][3]), sm_pack(pv[1][0], pv[1][1]),
-                                 sm_pack(pv[1][2], pv[1][3]));
-    const uint4 gpk = make_uint4(sm_pack(ds[0][0], ds[0][1]), sm_pack(ds[0][2], ds[0][3]), sm_pack(ds[1][0], ds[1][1]),
-                                 sm_pack(ds[1][2], ds[1][3]));
-    const sm_bf16x8 pf = __builtin_bit_cast(sm_bf16x8, ppk), gf = __builtin_bit_cast(sm_bf16x8, gpk);
+    const uint4 ppk = make_uint4(pack2_bf16_asm(pv[0][0], pv[0][1]), pack2_bf16_asm(pv[0][2], pv[0][3]), pack2_bf16_asm(pv[1][0], pv[1][1]),
+                                 pack2_bf16_asm(pv[1][2], pv[1][3]));
+    const uint4 gpk = make_uint4(pack2_bf16_asm(ds[0][0], ds[0][1]), pack2_bf16_asm(ds[0][2], ds[0][3]), pack2_bf16_asm(ds[1][0], ds[1][1]),
+                                 pack2_bf16_asm(ds[1][2], ds[1][3]));
+    const bf16x8 pf = __builtin_bit_cast(bf16x8, ppk), gf = __builtin_bit_cast(bf16x8, gpk);
     uint16_t* dvp = dv + ((int64_t)b * Lk + key) * lddv + h * kSmD + 4 * lg;
     uint16_t* dkp = dk + ((int64_t)b * Lk + key) * lddk + h * kSmD + 4 * lg;
 #pragma unroll
     for (int dt = 0; dt < 4; ++dt) {
-      const sm_f32x4 z = {0.f, 0.f, 0.f, 0.f};
-      const sm_f32x4 av = __builtin_amdgcn_mfma_f32_16x16x32_bf16(tr_frag(dOb, dt), pf, z, 0, 0, 0);
-      const sm_f32x4 ak = __builtin_amdgcn_mfma_f32_16x16x32_bf16(tr_frag(Qb, dt), gf, z, 0, 0, 0);
+      const f32x4 z = {0.f, 0.f, 0.f, 0.f};
+      const f32x4 av = __builtin_amdgcn_mfma_f32_16x16x32_bf16(tr_frag(dOb, dt), pf, z, 0, 0, 0);
+      const f32x4 ak = __builtin_amdgcn_mfma_f32_16x16x32_bf16(tr_frag(Qb, dt), gf, z, 0, 0, 0);
       if (key < Lk) {
         float v4[4] = {av[0], av[1], av[2], av[3]}, k4[4] = {ak[0], ak[1], ak[2], ak[3]};
         if (p.acc) {  // (a later query tile: add to what the earlier ones stored)
@@ -789,8 +778,8 @@ __global__ __launch_bounds__(256) void mha_small_bwd_mfma_kernel(const SmallAttn
           k4[0] += __uint_as_float(ok.x << 16); k4[1] += __uint_as_float(ok.x & 0xffff0000u);
           k4[2] += __uint_as_float(ok.y << 16); k4[3] += __uint_as_float(ok.y & 0xffff0000u);
         }
-        *reinterpret_cast<uint2*>(dvp + 16 * dt) = make_uint2(sm_pack(v4[0], v4[1]), sm_pack(v4[2], v4[3]));
-        *reinterpret_cast<uint2*>(dkp + 16 * dt) = make_uint2(sm_pack(k4[0], k4[1]), sm_pack(k4[2], k4[3]));
+        *reinterpret_cast<uint2*>(dvp + 16 * dt) = make_uint2(pack2_bf16_asm(v4[0], v4[1]), pack2_bf16_asm(v4[2], v4[3]));
+        *reinterpret_cast<uint2*>(dkp + 16 * dt) = make_uint2(pack2_bf16_asm(k4[0], k4[1]), pack2_bf16_asm(k4[2], k4[3]));
       }
     }
   }

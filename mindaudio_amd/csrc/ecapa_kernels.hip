@@ -13,17 +13,10 @@
 
 #include "../../include/mindaudio_amd.h"
 
+#include "device_common.h"
 #include "launch.h"
 
 namespace ma {
-
-__device__ __forceinline__ float e_bf2f(uint16_t h) { return __uint_as_float((uint32_t)h << 16); }
-__device__ __forceinline__ uint16_t e_f2bf(float f) {
-  uint32_t u = __float_as_uint(f);
-  if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40);
-  u += 0x7fffu + ((u >> 16) & 1u);
-  return (uint16_t)(u >> 16);
-}
 
 __global__ __launch_bounds__(256) void ecapa_pack_input_kernel(const float* __restrict__ x, int T, int F, int H, int Cpad,
                                                                uint16_t* __restrict__ out, int64_t total) {
@@ -36,7 +29,7 @@ __global__ __launch_bounds__(256) void ecapa_pack_input_kernel(const float* __re
     const int t = tp - H;
     float v = 0.0f;
     if (t >= 0 && t < T && c < F) v = x[(b * T + t) * F + c];
-    out[i] = e_f2bf(v);
+    out[i] = f2bf(v);
   }
 }
 
@@ -56,7 +49,7 @@ __global__ __launch_bounds__(256) void add_bf16_kernel(const uint16_t* __restric
       for (int e = 0; e < 4; ++e) {
         const float lo = __uint_as_float(ap[e] << 16) + __uint_as_float(bp[e] << 16);
         const float hi = __uint_as_float(ap[e] & 0xffff0000u) + __uint_as_float(bp[e] & 0xffff0000u);
-        ap[e] = (uint32_t)e_f2bf(lo) | ((uint32_t)e_f2bf(hi) << 16);
+        ap[e] = (uint32_t)f2bf(lo) | ((uint32_t)f2bf(hi) << 16);
       }
     }
     *reinterpret_cast<uint4*>(out + r * ldo + c) = av;
@@ -73,13 +66,13 @@ __global__ __launch_bounds__(256) void time_mean_kernel(const uint16_t* __restri
   float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
   int t = 0;
   for (; t + 3 < T; t += 4) {
-    s0 += e_bf2f(p[(int64_t)t * ldx]);
-    s1 += e_bf2f(p[(int64_t)(t + 1) * ldx]);
-    s2 += e_bf2f(p[(int64_t)(t + 2) * ldx]);
-    s3 += e_bf2f(p[(int64_t)(t + 3) * ldx]);
+    s0 += bf2f(p[(int64_t)t * ldx]);
+    s1 += bf2f(p[(int64_t)(t + 1) * ldx]);
+    s2 += bf2f(p[(int64_t)(t + 2) * ldx]);
+    s3 += bf2f(p[(int64_t)(t + 3) * ldx]);
   }
-  for (; t < T; ++t) s0 += e_bf2f(p[(int64_t)t * ldx]);
-  out[(int64_t)b * C + c] = e_f2bf(((s0 + s1) + (s2 + s3)) / (float)T);
+  for (; t < T; ++t) s0 += bf2f(p[(int64_t)t * ldx]);
+  out[(int64_t)b * C + c] = f2bf(((s0 + s1) + (s2 + s3)) / (float)T);
 }
 
 // The same with 16-byte loads (C % 64 == 0): grid (C / 64, B); thread (cg = tid & 7: 8 channels, ts = tid >> 3) sums every 32nd
@@ -107,7 +100,7 @@ __global__ __launch_bounds__(256) void time_mean8_kernel(const uint16_t* __restr
   if (threadIdx.x < 64) {
     float a = 0.0f;
     for (int k = 0; k < 32; ++k) a += red[k][threadIdx.x];
-    out[(int64_t)b * C + blockIdx.x * 64 + threadIdx.x] = e_f2bf(a / (float)T);
+    out[(int64_t)b * C + blockIdx.x * 64 + threadIdx.x] = f2bf(a / (float)T);
   }
 }
 
@@ -136,7 +129,7 @@ __global__ __launch_bounds__(256) void se_apply_kernel(const uint16_t* __restric
         const float lo = __uint_as_float(xp[e] << 16) * __uint_as_float(gp[e] << 16) + __uint_as_float(rp[e] << 16);
         const float hi = __uint_as_float(xp[e] & 0xffff0000u) * __uint_as_float(gp[e] & 0xffff0000u) +
                          __uint_as_float(rp[e] & 0xffff0000u);
-        op[e] = (uint32_t)e_f2bf(lo) | ((uint32_t)e_f2bf(hi) << 16);
+        op[e] = (uint32_t)f2bf(lo) | ((uint32_t)f2bf(hi) << 16);
       }
     }
     *reinterpret_cast<uint4*>(out + r * ldo + c) = o;
@@ -156,7 +149,7 @@ __global__ __launch_bounds__(256) void asp_pool_kernel(const uint16_t* __restric
   const int64_t r0 = (int64_t)b * Tp + H;
   float m = -INFINITY;
   if (c < C)
-    for (int t = ts; t < T; t += 4) m = fmaxf(m, e_bf2f(logits[(r0 + t) * ldl + c]));
+    for (int t = ts; t < T; t += 4) m = fmaxf(m, bf2f(logits[(r0 + t) * ldl + c]));
   red[0][ts][cl] = m;
   __syncthreads();
   m = fmaxf(fmaxf(red[0][0][cl], red[0][1][cl]), fmaxf(red[0][2][cl], red[0][3][cl]));
@@ -164,8 +157,8 @@ __global__ __launch_bounds__(256) void asp_pool_kernel(const uint16_t* __restric
   float s0 = 0.f, s1 = 0.f, s2 = 0.f;
   if (c < C)
     for (int t = ts; t < T; t += 4) {
-      const float w = __expf(e_bf2f(logits[(r0 + t) * ldl + c]) - m);
-      const float xv = e_bf2f(x[(r0 + t) * ldx + c]);
+      const float w = __expf(bf2f(logits[(r0 + t) * ldl + c]) - m);
+      const float xv = bf2f(x[(r0 + t) * ldx + c]);
       s0 += w;
       s1 += w * xv;
       s2 += w * xv * xv;
@@ -182,8 +175,8 @@ __global__ __launch_bounds__(256) void asp_pool_kernel(const uint16_t* __restric
     const float var = fmaxf(s2 / s0 - mean * mean, eps);
     const float sd = sqrtf(var);
     // cat((mean, std), 1) -> BatchNorm over 2C channels (ecapatdnn.py:306-308, 427)
-    out[(int64_t)b * 2 * C + c] = e_f2bf(mean * bn_scale[c] + bn_shift[c]);
-    out[(int64_t)b * 2 * C + C + c] = e_f2bf(sd * bn_scale[C + c] + bn_shift[C + c]);
+    out[(int64_t)b * 2 * C + c] = f2bf(mean * bn_scale[c] + bn_shift[c]);
+    out[(int64_t)b * 2 * C + C + c] = f2bf(sd * bn_scale[C + c] + bn_shift[C + c]);
   }
 }
 
@@ -246,8 +239,8 @@ __global__ __launch_bounds__(256) void asp_pool8_kernel(const uint16_t* __restri
     const float var = fmaxf(S2 / S0 - mean * mean, eps);
     const float sd = sqrtf(var);
     // cat((mean, std), 1) -> BatchNorm over 2C channels (ecapatdnn.py:306-308, 427)
-    out[(int64_t)b * 2 * C + c] = e_f2bf(mean * bn_scale[c] + bn_shift[c]);
-    out[(int64_t)b * 2 * C + C + c] = e_f2bf(sd * bn_scale[C + c] + bn_shift[C + c]);
+    out[(int64_t)b * 2 * C + c] = f2bf(mean * bn_scale[c] + bn_shift[c]);
+    out[(int64_t)b * 2 * C + C + c] = f2bf(sd * bn_scale[C + c] + bn_shift[C + c]);
   }
 }
 
@@ -268,10 +261,6 @@ __global__ __launch_bounds__(256) void asp_pool8_kernel(const uint16_t* __restri
 #ifndef ASP_WREG
 #define ASP_WREG 2  // weight fragments (of 4) kept in registers; the rest in LDS (tools/asp_bench.py: 0 / 1 / 2 / 3 measured)
 #endif
-typedef __attribute__((ext_vector_type(8))) __bf16 e_bf16x8;
-typedef __attribute__((ext_vector_type(4))) float e_f32x4;
-typedef __attribute__((ext_vector_type(2))) float e_f32x2;
-typedef __attribute__((ext_vector_type(4))) uint32_t e_u32x4;
 
 __global__ __launch_bounds__(256, 2) void asp_fused_kernel(const uint16_t* __restrict__ a1, int64_t lda, const uint16_t* __restrict__ W,
                                                         const uint16_t* __restrict__ x, int64_t ldx,
@@ -292,20 +281,20 @@ __global__ __launch_bounds__(256, 2) void asp_fused_kernel(const uint16_t* __res
   // (kAspWReg of the four 16-channel fragments stay in registers instead - the LDS pipe was 42 % busy with 16 + 4 fragment reads per
   // tile and wave, SQ_ACTIVE_INST_LDS, beside a VALU pipe at 47 %: with two waves per SIMD their times add more than they overlap)
   constexpr int kAspWReg = ASP_WREG;
-  e_bf16x8 wreg[kAspWReg > 0 ? kAspWReg : 1][4];
+  bf16x8 wreg[kAspWReg > 0 ? kAspWReg : 1][4];
   {
-    e_bf16x8 wt[4][4];
+    bf16x8 wt[4][4];
 #pragma unroll
     for (int j = 0; j < 4; ++j)
 #pragma unroll
       for (int ks = 0; ks < 4; ++ks)
-        wt[j][ks] = *reinterpret_cast<const e_bf16x8*>(W + (int64_t)(c0 + (fi >> 2) * 16 + j * 4 + (fi & 3)) * 128 + ks * 32 + fg * 8);
+        wt[j][ks] = *reinterpret_cast<const bf16x8*>(W + (int64_t)(c0 + (fi >> 2) * 16 + j * 4 + (fi & 3)) * 128 + ks * 32 + fg * 8);
 #pragma unroll
     for (int j = 0; j < 4; ++j)
 #pragma unroll
       for (int ks = 0; ks < 4; ++ks) {
         if (j < kAspWReg) wreg[j][ks] = wt[j][ks];
-        else *reinterpret_cast<e_bf16x8*>(wl + (j * 4 + ks) * 1024 + lane * 16) = wt[j][ks];
+        else *reinterpret_cast<bf16x8*>(wl + (j * 4 + ks) * 1024 + lane * 16) = wt[j][ks];
       }
   }
   // running sums per lane: channel pair p = channels 2p, 2p + 1 of the lane's 16 (float2: the updates are v_pk_* instructions).  m2 is the
@@ -314,30 +303,30 @@ __global__ __launch_bounds__(256, 2) void asp_fused_kernel(const uint16_t* __res
   // the running-maximum form, 15 dependent VALU instructions per element, was 2x the kernel's HBM time).  m2 is always one of the
   // channel's own logits and at most 40 below its maximum, so every weight is finite and the weights that underflow are < 2^-86 of the
   // largest.
-  e_f32x2 n2[8], s0[8], s1[8], s2[8];  // n2 = -m2 (the form the fused multiply-add takes)
+  f32x2 n2[8], s0[8], s1[8], s2[8];  // n2 = -m2 (the form the fused multiply-add takes)
 #pragma unroll
   for (int p = 0; p < 8; ++p) {
-    n2[p] = e_f32x2{3.0e38f, 3.0e38f};  // (finite: -inf - -inf would be NaN)
-    s0[p] = s1[p] = s2[p] = e_f32x2{0.f, 0.f};
+    n2[p] = f32x2{3.0e38f, 3.0e38f};  // (finite: -inf - -inf would be NaN)
+    s0[p] = s1[p] = s2[p] = f32x2{0.f, 0.f};
   }
   const int ntiles = (T + 15) >> 4;
   // tiles in flight: x (HBM) three tiles ahead in four register buffers.  Every wave needs the same 16 x 128 tile of a1: wave w loads
   // k-step w of it (4 VGPRs, three tiles ahead), writes it to the LDS slot of tile i + 1 during tile i, and one barrier per tile hands
   // the slots over.  A SIMD needs ~30 KB in flight (6 KB per ~1 000 cycles x ~5 000 cycles of loaded latency); with the whole a1 tile in
   // registers per wave (64 VGPRs for four buffers) the kernel spilled, and with fewer buffers it waited: 125 us.
-  e_bf16x8 ar[4];
-  e_u32x4 xv[4][2];
+  bf16x8 ar[4];
+  u32x4 xv[4][2];
 #define ASP_ROW(tile_)                                                          \
   int t_ = (tile_) * 16 + fi;                                                   \
   if (t_ >= T) t_ = T - 1; /* frames past the utterance: a valid row, weight 0 below */
 #define ASP_LOAD(buf_, tile_)                                                                                          \
   {                                                                                                                   \
     ASP_ROW(tile_)                                                                                                    \
-    if (!(ASP_X & 8) || (tile_) < 3) ar[buf_] = *reinterpret_cast<const e_bf16x8*>(a1 + (r0 + t_) * lda + wave * 32 + fg * 8); \
+    if (!(ASP_X & 8) || (tile_) < 3) ar[buf_] = *reinterpret_cast<const bf16x8*>(a1 + (r0 + t_) * lda + wave * 32 + fg * 8); \
     const uint16_t* xp_ = x + (r0 + t_) * ldx + c0 + fg * 16;                                                         \
     if (!(ASP_X & 4) || (tile_) < 3) {                                                                                \
-      xv[buf_][0] = *reinterpret_cast<const e_u32x4*>(xp_);                                                           \
-      xv[buf_][1] = *reinterpret_cast<const e_u32x4*>(xp_ + 8);                                                       \
+      xv[buf_][0] = *reinterpret_cast<const u32x4*>(xp_);                                                           \
+      xv[buf_][1] = *reinterpret_cast<const u32x4*>(xp_ + 8);                                                       \
     }                                                                                                                 \
   }
 #ifndef ASP_X
@@ -346,9 +335,9 @@ __global__ __launch_bounds__(256, 2) void asp_fused_kernel(const uint16_t* __res
 #if ASP_X & 1
 #define ASP_W(d_) (d_)
 #else
-#define ASP_W(d_) (e_f32x2{__builtin_amdgcn_exp2f((d_)[0]), __builtin_amdgcn_exp2f((d_)[1])})
+#define ASP_W(d_) (f32x2{__builtin_amdgcn_exp2f((d_)[0]), __builtin_amdgcn_exp2f((d_)[1])})
 #endif
-  const e_f32x2 kL2E = {1.44269504f, 1.44269504f};
+  const f32x2 kL2E = {1.44269504f, 1.44269504f};
   // one tile: logits (no bias: a per-channel constant over the frames does not change the softmax over the frames) as exponents
   // relative to the reference, the rare rescale, then the three sums
 #define ASP_TILE(xb_, tile_)                                                                                           \
@@ -359,28 +348,28 @@ __global__ __launch_bounds__(256, 2) void asp_fused_kernel(const uint16_t* __res
        on the path WITH the load a wait for the load just issued. */                                                   \
     if (!(ASP_X & 8)) {                                                                                               \
       __syncthreads();                                                                                                \
-      *reinterpret_cast<e_bf16x8*>(aring + (((xb_) + 1) & 1) * 4096 + wave * 1024 + lane * 16) = ar[((xb_) + 1) % 4]; \
+      *reinterpret_cast<bf16x8*>(aring + (((xb_) + 1) & 1) * 4096 + wave * 1024 + lane * 16) = ar[((xb_) + 1) % 4]; \
     }                                                                                                                 \
     ASP_LOAD(((xb_) + 3) % 4, (tile_) + 3)                                                                            \
-    e_f32x4 acc[4];                                                                                                   \
-    _Pragma("unroll") for (int j = 0; j < 4; ++j) acc[j] = e_f32x4{0.f, 0.f, 0.f, 0.f};                               \
+    f32x4 acc[4];                                                                                                   \
+    _Pragma("unroll") for (int j = 0; j < 4; ++j) acc[j] = f32x4{0.f, 0.f, 0.f, 0.f};                               \
     _Pragma("unroll") for (int ks = 0; ks < 4; ++ks) {                                                                 \
-      const e_bf16x8 bfr = *reinterpret_cast<const e_bf16x8*>(aring + ((xb_) & 1) * 4096 + ks * 1024 + lane * 16);    \
+      const bf16x8 bfr = *reinterpret_cast<const bf16x8*>(aring + ((xb_) & 1) * 4096 + ks * 1024 + lane * 16);    \
       _Pragma("unroll") for (int j = 0; j < 4; ++j)                                                                    \
         if (!(ASP_X & 2))                                                                                             \
           acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(                                                           \
-              j < kAspWReg ? wreg[j < kAspWReg ? j : 0][ks] : *reinterpret_cast<const e_bf16x8*>(wl + (j * 4 + ks) * 1024 + lane * 16), \
+              j < kAspWReg ? wreg[j < kAspWReg ? j : 0][ks] : *reinterpret_cast<const bf16x8*>(wl + (j * 4 + ks) * 1024 + lane * 16), \
               bfr, acc[j], 0, 0, 0);                                                                                  \
-        else acc[j][0] += __builtin_bit_cast(e_f32x4, bfr)[j];                                                        \
+        else acc[j][0] += __builtin_bit_cast(f32x4, bfr)[j];                                                        \
     }                                                                                                                 \
-    e_f32x2 d[8];                                                                                                     \
+    f32x2 d[8];                                                                                                     \
     _Pragma("unroll") for (int p = 0; p < 8; ++p) {                                                                    \
-      const e_f32x2 l_ = (p & 1) ? e_f32x2{acc[p >> 1][2], acc[p >> 1][3]} : e_f32x2{acc[p >> 1][0], acc[p >> 1][1]}; \
+      const f32x2 l_ = (p & 1) ? f32x2{acc[p >> 1][2], acc[p >> 1][3]} : f32x2{acc[p >> 1][0], acc[p >> 1][1]}; \
       d[p] = __builtin_elementwise_fma(l_, kL2E, n2[p]);                                                              \
     }                                                                                                                 \
     const bool dead_ = (tile_) + 1 >= ntiles && (tile_) * 16 + fi >= T;  /* a frame past the utterance: weight 0 */      \
     if (dead_) {                                                                                                      \
-      _Pragma("unroll") for (int p = 0; p < 8; ++p) d[p] = e_f32x2{-INFINITY, -INFINITY};                             \
+      _Pragma("unroll") for (int p = 0; p < 8; ++p) d[p] = f32x2{-INFINITY, -INFINITY};                             \
     }                                                                                                                 \
     float mx = fmaxf(d[0][0], d[0][1]);                                                                               \
     _Pragma("unroll") for (int p = 1; p < 8; ++p) mx = fmaxf(fmaxf(mx, d[p][0]), d[p][1]);                             \
@@ -399,9 +388,9 @@ __global__ __launch_bounds__(256, 2) void asp_fused_kernel(const uint16_t* __res
     }                                                                                                                 \
     _Pragma("unroll") for (int p = 0; p < 8; ++p) {                                                                    \
       const uint32_t xw = xv[xb_][p >> 2][p & 3];                                                                     \
-      const e_f32x2 xe = {__uint_as_float(xw << 16), __uint_as_float(xw & 0xffff0000u)};                              \
-      const e_f32x2 w = ASP_W(d[p]);                                                                                  \
-      const e_f32x2 wx = w * xe;                                                                                      \
+      const f32x2 xe = {__uint_as_float(xw << 16), __uint_as_float(xw & 0xffff0000u)};                              \
+      const f32x2 w = ASP_W(d[p]);                                                                                  \
+      const f32x2 wx = w * xe;                                                                                      \
       s0[p] += w;                                                                                                     \
       s1[p] += wx;                                                                                                    \
       s2[p] = __builtin_elementwise_fma(wx, xe, s2[p]);                                                               \
@@ -410,7 +399,7 @@ __global__ __launch_bounds__(256, 2) void asp_fused_kernel(const uint16_t* __res
   ASP_LOAD(0, 0)
   ASP_LOAD(1, 1)
   ASP_LOAD(2, 2)
-  *reinterpret_cast<e_bf16x8*>(aring + wave * 1024 + lane * 16) = ar[0];  // tile 0's slot (the first barrier publishes it)
+  *reinterpret_cast<bf16x8*>(aring + wave * 1024 + lane * 16) = ar[0];  // tile 0's slot (the first barrier publishes it)
   int tile = 0;
   for (; tile + 4 <= ntiles; tile += 4) {
     ASP_TILE(0, tile)
@@ -460,8 +449,8 @@ __global__ __launch_bounds__(256, 2) void asp_fused_kernel(const uint16_t* __res
         mv[e] = mean * bn_scale[cb + 2 * p + e] + bn_shift[cb + 2 * p + e];
         sv[e] = sqrtf(var) * bn_scale[C + cb + 2 * p + e] + bn_shift[C + cb + 2 * p + e];
       }
-      mo[p] = (uint32_t)e_f2bf(mv[0]) | ((uint32_t)e_f2bf(mv[1]) << 16);
-      so[p] = (uint32_t)e_f2bf(sv[0]) | ((uint32_t)e_f2bf(sv[1]) << 16);
+      mo[p] = (uint32_t)f2bf(mv[0]) | ((uint32_t)f2bf(mv[1]) << 16);
+      so[p] = (uint32_t)f2bf(sv[0]) | ((uint32_t)f2bf(sv[1]) << 16);
     }
     uint16_t* om = out + (int64_t)b * 2 * C + cb;
     *reinterpret_cast<uint4*>(om) = make_uint4(mo[0], mo[1], mo[2], mo[3]);
@@ -496,13 +485,13 @@ __global__ __launch_bounds__(512) void se_gate_kernel(const uint16_t* __restrict
     for (int e = 0; e < 4; ++e) { xs[kc][2 * e] = __uint_as_float(w[e] << 16); xs[kc][2 * e + 1] = __uint_as_float(w[e] & 0xffff0000u); }
   }
   const int rows = S >> 3;  // per wave (<= 16)
-  e_u32x4 wv[16][KC];
+  u32x4 wv[16][KC];
 #pragma unroll
   for (int r = 0; r < 16; ++r)
 #pragma unroll
     for (int kc = 0; kc < KC; ++kc) {
       const int j = wave * rows + (r < rows ? r : rows - 1);
-      wv[r][kc] = *reinterpret_cast<const e_u32x4*>(W1 + (int64_t)j * C + kc * 512 + lane * 8);
+      wv[r][kc] = *reinterpret_cast<const u32x4*>(W1 + (int64_t)j * C + kc * 512 + lane * 8);
     }
   // every load of the kernel whose address does not depend on h is issued here, before the first wait (five dependent round trips
   // otherwise: mean, W1, b1, W2, b2)
@@ -512,12 +501,12 @@ __global__ __launch_bounds__(512) void se_gate_kernel(const uint16_t* __restrict
   const int kl = (lane & 15) * 8;
   const bool kin = kl < S;
   constexpr int kInst = C / 32;  // phase 2, per wave: C / 8 rows, four per instruction
-  e_u32x4 w2[kInst];
+  u32x4 w2[kInst];
   float b2v[kInst];
 #pragma unroll
   for (int i = 0; i < kInst; ++i) {
     const int c = wave * (C / 8) + 4 * i + (lane >> 4);
-    if constexpr (KC == 1) w2[i] = *reinterpret_cast<const e_u32x4*>(W2 + (int64_t)c * S + (kin ? kl : 0));  // (KC = 2: no registers left)
+    if constexpr (KC == 1) w2[i] = *reinterpret_cast<const u32x4*>(W2 + (int64_t)c * S + (kin ? kl : 0));  // (KC = 2: no registers left)
     b2v[i] = b2[c];
   }
 #pragma unroll
@@ -539,7 +528,7 @@ __global__ __launch_bounds__(512) void se_gate_kernel(const uint16_t* __restrict
   if constexpr (KC != 1) {
 #pragma unroll
     for (int i = 0; i < kInst; ++i)
-      w2[i] = *reinterpret_cast<const e_u32x4*>(W2 + (int64_t)(wave * (C / 8) + 4 * i + (lane >> 4)) * S + (kin ? kl : 0));
+      w2[i] = *reinterpret_cast<const u32x4*>(W2 + (int64_t)(wave * (C / 8) + 4 * i + (lane >> 4)) * S + (kin ? kl : 0));
   }
   float hs[8];
 #pragma unroll
@@ -553,7 +542,7 @@ __global__ __launch_bounds__(512) void se_gate_kernel(const uint16_t* __restrict
     for (int o = 8; o > 0; o >>= 1) a += __shfl_xor(a, o, 64);
     if ((lane & 15) == 0) {
       const int c = wave * (C / 8) + 4 * i + (lane >> 4);
-      gate[b * C + c] = e_f2bf(1.0f / (1.0f + __expf(-(a + b2v[i]))));
+      gate[b * C + c] = f2bf(1.0f / (1.0f + __expf(-(a + b2v[i]))));
     }
   }
 }
@@ -585,13 +574,13 @@ __global__ __launch_bounds__(1024) void se_block_kernel(const uint16_t* __restri
   const int64_t b = blockIdx.x;
   const uint16_t* xb = x + (b * Tp + H) * ldx + cg * 8;
   // ---- squeeze -----------------------------------------------------------------------------------------------------------------------
-  e_u32x4 keep[kRows > 0 ? kRows : 1];
+  u32x4 keep[kRows > 0 ? kRows : 1];
   float a[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
   if constexpr (KEEP) {
 #pragma unroll
     for (int i = 0; i < kRows; ++i) {
       const int t = sl + kNS * i;
-      keep[i] = t < T ? *reinterpret_cast<const e_u32x4*>(xb + (int64_t)t * ldx) : e_u32x4{0u, 0u, 0u, 0u};
+      keep[i] = t < T ? *reinterpret_cast<const u32x4*>(xb + (int64_t)t * ldx) : u32x4{0u, 0u, 0u, 0u};
     }
 #pragma unroll
     for (int i = 0; i < kRows; ++i)
@@ -605,7 +594,7 @@ __global__ __launch_bounds__(1024) void se_block_kernel(const uint16_t* __restri
     for (int i = 0; i < kRows; ++i) asm volatile("" : "+v"(keep[i]));
   }
   for (int t = sl + kNS * kRows; t < T; t += kNS) {
-    const e_u32x4 v = *reinterpret_cast<const e_u32x4*>(xb + (int64_t)t * ldx);
+    const u32x4 v = *reinterpret_cast<const u32x4*>(xb + (int64_t)t * ldx);
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       a[2 * e] += __uint_as_float(v[e] << 16);
@@ -621,7 +610,7 @@ __global__ __launch_bounds__(1024) void se_block_kernel(const uint16_t* __restri
 #pragma unroll
     for (int k = 0; k < kNS; ++k) m += sums[k][c];
     // (the separate launches hand the mean over as bf16; rounded here too so that both forms see the same excitation input)
-    smean[c] = e_bf2f(e_f2bf(m / (float)T));
+    smean[c] = bf2f(f2bf(m / (float)T));
   }
   __syncthreads();
   __builtin_amdgcn_sched_barrier(0);  // (phases are not interleaved: the kept rows leave few registers)
@@ -637,12 +626,12 @@ __global__ __launch_bounds__(1024) void se_block_kernel(const uint16_t* __restri
     const uint32_t woff = (uint32_t)(wave * rows) * C + lane * 8;
 #pragma unroll
     for (int r0 = 0; r0 < 8; r0 += 4) {
-      e_u32x4 wv[4][KC];
+      u32x4 wv[4][KC];
 #pragma unroll
       for (int r = 0; r < 4; ++r)
 #pragma unroll
         for (int kc = 0; kc < KC; ++kc)
-          wv[r][kc] = *reinterpret_cast<const e_u32x4*>(W1 + woff + (uint32_t)(r0 + r < rows ? r0 + r : rows - 1) * C + kc * 512);
+          wv[r][kc] = *reinterpret_cast<const u32x4*>(W1 + woff + (uint32_t)(r0 + r < rows ? r0 + r : rows - 1) * C + kc * 512);
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         float acc = 0.0f;
@@ -671,9 +660,9 @@ __global__ __launch_bounds__(1024) void se_block_kernel(const uint16_t* __restri
     const uint32_t w2off = (uint32_t)(wave * (C / 16) + (lane >> 4)) * S + (kin ? kl : 0);
 #pragma unroll
     for (int i0 = 0; i0 < kInst; i0 += 4) {
-      e_u32x4 w2[4];
+      u32x4 w2[4];
 #pragma unroll
-      for (int i = 0; i < 4; ++i) w2[i] = *reinterpret_cast<const e_u32x4*>(W2 + w2off + (uint32_t)(4 * (i0 + i)) * S);
+      for (int i = 0; i < 4; ++i) w2[i] = *reinterpret_cast<const u32x4*>(W2 + w2off + (uint32_t)(4 * (i0 + i)) * S);
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         float acc = 0.0f;
@@ -684,7 +673,7 @@ __global__ __launch_bounds__(1024) void se_block_kernel(const uint16_t* __restri
         if ((lane & 15) == 0) {
           const int c = wave * (C / 16) + 4 * (i0 + i) + (lane >> 4);
           // (the separate launches hand the gate over as bf16)
-          sgate[c] = e_bf2f(e_f2bf(1.0f / (1.0f + __expf(-(acc + b2[c])))));
+          sgate[c] = bf2f(f2bf(1.0f / (1.0f + __expf(-(acc + b2[c])))));
         }
       }
       __builtin_amdgcn_sched_barrier(0);
@@ -698,42 +687,42 @@ __global__ __launch_bounds__(1024) void se_block_kernel(const uint16_t* __restri
   for (int e = 0; e < 8; ++e) gt[e] = sgate[cg * 8 + e];
   const uint16_t* rb = res + (b * Tp + H) * ldr + cg * 8;
   uint16_t* ob = out + (b * Tp + H) * ldo + cg * 8;
-  auto apply = [&](const e_u32x4& xv, const e_u32x4& rv) __attribute__((always_inline)) {
-    e_u32x4 o;
+  auto apply = [&](const u32x4& xv, const u32x4& rv) __attribute__((always_inline)) {
+    u32x4 o;
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       const float lo = __uint_as_float(xv[e] << 16) * gt[2 * e] + __uint_as_float(rv[e] << 16);
       const float hi = __uint_as_float(xv[e] & 0xffff0000u) * gt[2 * e + 1] + __uint_as_float(rv[e] & 0xffff0000u);
-      o[e] = (uint32_t)e_f2bf(lo) | ((uint32_t)e_f2bf(hi) << 16);
+      o[e] = (uint32_t)f2bf(lo) | ((uint32_t)f2bf(hi) << 16);
     }
     return o;
   };
   if constexpr (KEEP) {
 #pragma unroll
     for (int i0 = 0; i0 < kRows; i0 += 4) {  // (four residual rows in flight at a time: registers)
-      e_u32x4 rv[4];
+      u32x4 rv[4];
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         const int t = sl + kNS * (i0 + i);
-        rv[i] = t < T ? *reinterpret_cast<const e_u32x4*>(rb + (int64_t)t * ldr) : e_u32x4{0u, 0u, 0u, 0u};
+        rv[i] = t < T ? *reinterpret_cast<const u32x4*>(rb + (int64_t)t * ldr) : u32x4{0u, 0u, 0u, 0u};
       }
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         const int t = sl + kNS * (i0 + i);
-        if (t < T) *reinterpret_cast<e_u32x4*>(ob + (int64_t)t * ldo) = apply(keep[i0 + i], rv[i]);
+        if (t < T) *reinterpret_cast<u32x4*>(ob + (int64_t)t * ldo) = apply(keep[i0 + i], rv[i]);
       }
     }
   }
   for (int t = sl + kNS * kRows; t < T; t += kNS) {
-    const e_u32x4 xv = *reinterpret_cast<const e_u32x4*>(xb + (int64_t)t * ldx);
-    const e_u32x4 rv = *reinterpret_cast<const e_u32x4*>(rb + (int64_t)t * ldr);
-    *reinterpret_cast<e_u32x4*>(ob + (int64_t)t * ldo) = apply(xv, rv);
+    const u32x4 xv = *reinterpret_cast<const u32x4*>(xb + (int64_t)t * ldx);
+    const u32x4 rv = *reinterpret_cast<const u32x4*>(rb + (int64_t)t * ldr);
+    *reinterpret_cast<u32x4*>(ob + (int64_t)t * ldo) = apply(xv, rv);
   }
   // halo frames of the output stay zero (the taps of the next convolution read them)
   for (int i = tid; i < 2 * H * kCG; i += 1024) {
     const int r = i / kCG, g8 = i - r * kCG;
     const int tp = r < H ? r : T + r;  // rows 0 .. H-1 and H+T .. Tp-1
-    *reinterpret_cast<e_u32x4*>(out + (b * Tp + tp) * ldo + g8 * 8) = e_u32x4{0u, 0u, 0u, 0u};
+    *reinterpret_cast<u32x4*>(out + (b * Tp + tp) * ldo + g8 * 8) = u32x4{0u, 0u, 0u, 0u};
   }
 }
 
@@ -751,13 +740,13 @@ __global__ __launch_bounds__(512) void linear_small_kernel(const uint16_t* __res
   const int kw = K / 8;  // this wave's slice of K (a multiple of 32)
   const uint16_t* ap = A + (int64_t)(m0 + fi) * lda + wave * kw + fg * 8;
   const uint16_t* wp = W + (int64_t)(n0 + fi) * ldw + wave * kw + fg * 8;
-  e_f32x4 acc[2] = {e_f32x4{0.f, 0.f, 0.f, 0.f}, e_f32x4{0.f, 0.f, 0.f, 0.f}};
+  f32x4 acc[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
   for (int k0 = 0; k0 < kw; k0 += 384) {  // twelve k-steps at a time: 24 loads in flight, then 12 MFMAs (kw % 384 == 0)
-    e_bf16x8 af[12], wf[12];
+    bf16x8 af[12], wf[12];
 #pragma unroll
     for (int i = 0; i < 12; ++i) {
-      af[i] = *reinterpret_cast<const e_bf16x8*>(ap + k0 + 32 * i);
-      wf[i] = *reinterpret_cast<const e_bf16x8*>(wp + k0 + 32 * i);
+      af[i] = *reinterpret_cast<const bf16x8*>(ap + k0 + 32 * i);
+      wf[i] = *reinterpret_cast<const bf16x8*>(wp + k0 + 32 * i);
     }
 #pragma unroll
     for (int i = 0; i < 12; ++i) acc[i & 1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[i], af[i], acc[i & 1], 0, 0, 0);  // rows 4 fg + r = n, column fi = m

@@ -24,6 +24,7 @@
 #include <type_traits>
 
 #include "../../include/mindaudio_amd.h"
+#include "device_common.h"
 #include "features_common.h"
 #include "fft400.h"
 #include "fft512.h"
@@ -98,18 +99,9 @@ extern "C" void ma_debug_set_flags(int f) { g_debug = f; }
 
 namespace ma {
 
-__device__ __forceinline__ float wave_reduce(float v, bool is_max) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    const float o = __shfl_xor(v, off, 64);
-    v = is_max ? fmaxf(v, o) : fminf(v, o);
-  }
-  return v;
-}
-
 template <int NW = kWaves>
 __device__ __forceinline__ float block_reduce(float v, float* red, bool is_max) {
-  v = wave_reduce(v, is_max);
+  v = wave_minmax(v, is_max);
   const int wave = threadIdx.x >> 6;
   if ((threadIdx.x & 63) == 0) red[wave] = v;
   __syncthreads();
@@ -142,9 +134,6 @@ static_assert(kSlotFloats <= kSlotStride && kUnitFrames * kPStride <= kPwFloats 
 static_assert(kOffP % 16 == 0 && (kPwFloats * 4) % 16 == 0, "LDS alignment");
 
 __device__ __forceinline__ float fast_log2(float x) { return __builtin_amdgcn_logf(x); }  // v_log_f32, 1 ulp
-
-typedef __attribute__((address_space(3))) void lds_void_t;
-typedef __attribute__((address_space(1))) const void gl_void_t;
 
 // Work decomposition, round 2 (n_fft == 512):
 //   NW = waves per workgroup (they share the tables), OCC = waves per SIMD the register allocation is held to.
@@ -240,7 +229,7 @@ __global__ __launch_bounds__(NW * 64, OCC) void feat512_kernel(const FeatParams 
       const float* __restrict__ src = g.xb + s_lo + lane * 4;
       for (int c = 0; c * 256 < span; ++c)
         if (c * 256 + lane * 4 < span)
-          __builtin_amdgcn_global_load_lds((gl_void_t*)(src + c * 256), (lds_void_t*)(Pw + c * 256), 16, 0, 0);
+          __builtin_amdgcn_global_load_lds((gl_cvoid_t*)(src + c * 256), (lds_void_t*)(Pw + c * 256), 16, 0, 0);
     } else {
       // edge / unaligned / ragged spans (a few units per utterance): element-wise gather with np.pad semantics
       for (int i = lane; i < span; i += 64) {
@@ -533,7 +522,7 @@ __global__ __launch_bounds__(NW * 64, OCC) void feat512_kernel(const FeatParams 
           }
           MA_PROF(4);
           if (p.apply_db) {
-            vmin = wave_reduce(vmin, false);
+            vmin = wave_minmax(vmin, false);
             if (lane == 0 && !MA_DBG(64)) p.unit_min[unit] = vmin;
           }
           wave_lds_sync();  // the tile is restaged by the next unit

@@ -11,6 +11,7 @@
 // At cfg-2 size and n_fft = 400 this path is ~4x slower than the 512-point FFT path; it exists for coverage.
 #include "features_common.h"
 
+#include "device_common.h"
 #include "launch.h"
 
 namespace ma {
@@ -21,15 +22,6 @@ constexpr int kGTile = 32;       // frames per tile (= MFMA M)
 constexpr int kGChunk = 256;     // samples per n-chunk (keeps N = 1024 + an 80-mel bank inside 160 KB of LDS)
 constexpr int kGMaxTiles = 5;    // frequency tiles per wave: n_freq <= 5 * 4 * 32 = 640 >= 513
 constexpr int kGMaxRows = 16;
-
-__device__ __forceinline__ float g_wave_reduce(float v, bool is_max) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    const float o = __shfl_xor(v, off, 64);
-    v = is_max ? fmaxf(v, o) : fminf(v, o);
-  }
-  return v;
-}
 
 struct GenericGeom {
   int N;        // n_fft
@@ -214,7 +206,7 @@ __global__ __launch_bounds__(256, 1) void feat_generic_kernel(const FeatParams p
   }
   if (MODE == kModeMel && p.apply_db) {
     __shared__ float red[4];
-    const float wm = g_wave_reduce(wmax, true);
+    const float wm = wave_minmax(wmax, true);
     if (lane == 0) red[wave] = wm;
     __syncthreads();
     if (tid == 0) p.wg_max[blockIdx.x] = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));

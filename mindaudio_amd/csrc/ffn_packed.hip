@@ -23,29 +23,14 @@
 #include <stdlib.h>
 
 #include <type_traits>
-#include <utility>
 
 #include "../../include/mindaudio_amd.h"
 
 #include "ffn_packed.h"
+#include "device_common.h"
 #include "launch.h"
 
 namespace ma {
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((address_space(1))) void pk_gl_void_t;
-typedef __attribute__((address_space(3))) void pk_lds_void_t;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-
-template <int... Is, class F>
-__device__ __forceinline__ void pk_static_for_impl(std::integer_sequence<int, Is...>, F&& f) {
-  (f(std::integral_constant<int, Is>{}), ...);
-}
-// compile-time loop: every index inside f is a constant expression, so register arrays never need dynamic indexing
-template <int N, class F>
-__device__ __forceinline__ void pk_static_for(F&& f) {
-  pk_static_for_impl(std::make_integer_sequence<int, N>{}, f);
-}
 
 constexpr int kPkRows = 64, kPkD = 256, kPkThreads = 256;
 constexpr int kPkPitch = 544;                // LDS row pitch of the activation tile (bytes)
@@ -61,33 +46,6 @@ constexpr int kPkOffQb = kPkOffBias + 1024;  // bias of the qkv tail (<= 1024 fl
 constexpr int kPkLds = kPkOffQb + 4096;  // a tile (34 KiB) during the main loop, 8 x 16 KiB exchange slots at the end
 constexpr int kPkMaxHidden = 8192;
 
-
-typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
-typedef __attribute__((ext_vector_type(2))) float f32x2;
-__device__ __forceinline__ uint32_t pk_pack_bf16(float lo, float hi) {
-  const bf16x2 r = __builtin_convertvector((f32x2){lo, hi}, bf16x2);  // v_cvt_pk_bf16_f32 (round to nearest even)
-  return *reinterpret_cast<const uint32_t*>(&r);
-}
-// Cross-lane sums without the LDS crossbar (ds_bpermute costs an LDS round trip, ~100 ns each, eight of them in a row per
-// LayerNorm): lanes {c, c + 16, c + 32, c + 48} through gfx950's row swaps - with both operands a copy of x,
-// v_permlane16_swap leaves (x[row 0], x[row 0], x[row 2], x[row 2]) and (x[row 1], x[row 1], x[row 3], x[row 3]), whose sum is
-// x[l] + x[l ^ 16] in every lane (tools/ubench/permlane_test.hip); v_permlane32_swap does the same with the 32-lane halves.
-// (asm: the builtin with two identical operands is folded to 2 x by this hipcc.)  Quads through DPP.
-__device__ __forceinline__ float pk_sum_xor16(float x) {
-  float a = x, b = x;
-  asm volatile("s_nop 1\n\tv_permlane16_swap_b32 %0, %1" : "+v"(a), "+v"(b));
-  return a + b;
-}
-__device__ __forceinline__ float pk_sum_xor32(float x) {
-  float a = x, b = x;
-  asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(a), "+v"(b));
-  return a + b;
-}
-__device__ __forceinline__ float pk_sum_quad(float x) {  // x[l] + x[l ^ 1] + x[l ^ 2] + x[l ^ 3]
-  x += __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, x), 0xB1, 0xf, 0xf, true));
-  x += __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, x), 0x4E, 0xf, 0xf, true));
-  return x;
-}
 #ifndef MA_FFN_WT
 #define MA_FFN_WT 0
 #endif
@@ -119,7 +77,6 @@ __device__ unsigned long long g_ffn_prof[3 * 32];
 // write-back
 template <int WT>
 __device__ __forceinline__ void pk_store16(void* ptr, uint4 v4) {
-  typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
   const u32x4 v = {v4.x, v4.y, v4.z, v4.w};
   if constexpr (WT == 1) asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1" ::"v"(ptr), "v"(v) : "memory");
   else if constexpr (WT == 2) asm volatile("global_store_dwordx4 %0, %1, off nt" ::"v"(ptr), "v"(v) : "memory");
@@ -293,7 +250,7 @@ __global__ __launch_bounds__(kPkThreads, 1) void ffn_packed_kernel(const FfnPack
       PK_WAIT(blo, kWait + 1);
       PK_WAIT(bhi, kWait + 1);
     }
-    pk_static_for<64>([&](auto ic) __attribute__((always_inline)) {
+    static_for<64>([&](auto ic) __attribute__((always_inline)) {
       constexpr int i = decltype(ic)::value;
       constexpr int ks = i >> 3, t = (i >> 2) & 1, s = i & 3;
       if constexpr ((i & 7) == 0) {
@@ -341,7 +298,7 @@ __global__ __launch_bounds__(kPkThreads, 1) void ffn_packed_kernel(const FfnPack
   // nano-slots 1..64 of the Swish of Snext (the S tiles the first product has just finished) -------------------------------------
   auto product2 = [&](const char* refill, int b1_blk, f32x4 (&Snext)[2][4]) __attribute__((always_inline)) {
     bf16x8 hf[4];
-    pk_static_for<4>([&](auto sc) __attribute__((always_inline)) {
+    static_for<4>([&](auto sc) __attribute__((always_inline)) {
       constexpr int s = decltype(sc)::value;
       const uint4 hv = make_uint4(hfw[s][0], hfw[s][1], hfw[s][2], hfw[s][3]);
       hf[s] = *reinterpret_cast<const bf16x8*>(&hv);
@@ -349,7 +306,7 @@ __global__ __launch_bounds__(kPkThreads, 1) void ffn_packed_kernel(const FfnPack
     nano(std::integral_constant<int, 0>{}, Snext);
     asm volatile("s_nop 3" : "+v"(hf[0]), "+v"(hf[1]), "+v"(hf[2]), "+v"(hf[3]));  // VALU write -> MFMA operand read
     PK_LOAD_B1(b1_blk);
-    pk_static_for<16>([&](auto jc) __attribute__((always_inline)) {
+    static_for<16>([&](auto jc) __attribute__((always_inline)) {
       constexpr int j = decltype(jc)::value;
       PK_WAIT(ring[j], 17);
       PK_MFMA_O(O[j][0], ring[j], hf[0]);
@@ -406,7 +363,7 @@ __global__ __launch_bounds__(kPkThreads, 1) void ffn_packed_kernel(const FfnPack
                    : "=v"(ring[q]) : "v"(PK_VOFF(q)), "s"(w0), "n"((((q) & 7) - 4) * 1024) : "memory");
     const int l = tidv & 63;
     const float* bsrc = b1_cur + (l < 32 ? block_of(0) : block_of(blk_wrap(1))) * kPkBlock + (l & 31);
-    __builtin_amdgcn_global_load_lds((pk_gl_void_t*)bsrc, (pk_lds_void_t*)(smem + kPkOffBias + wave * 256), 4, 0, 0);
+    __builtin_amdgcn_global_load_lds((gl_void_t*)bsrc, (lds_void_t*)(smem + kPkOffBias + wave * 256), 4, 0, 0);
   }
   // ---- activation tile -> LDS: [64 rows][544 B] (512 + 32 of padding).  A ds_read_b128 serves lanes in groups of 16
   // ({0-3,12-15,20-27}, ...); with this pitch the 16-byte slot of lane (c, g) is (2 c + g + 4 ks) mod 16, distinct inside every
@@ -420,11 +377,11 @@ __global__ __launch_bounds__(kPkThreads, 1) void ffn_packed_kernel(const FfnPack
 #pragma unroll
     for (int k = 0; k < 10; ++k)
       if (srcs[k])
-        __builtin_amdgcn_global_load_lds((pk_gl_void_t*)(srcs[k] + tid), (pk_lds_void_t*)(par_w + k * 1024), 4, 0, 0);
+        __builtin_amdgcn_global_load_lds((gl_void_t*)(srcs[k] + tid), (lds_void_t*)(par_w + k * 1024), 4, 0, 0);
     if (p.qkv_wp) {
       char* qb_w = smem + kPkOffQb + (tid >> 6) * 256;
       for (int k = 0; k * 256 < p.qkv_n; ++k)
-        __builtin_amdgcn_global_load_lds((pk_gl_void_t*)(p.qkv_b + k * 256 + tid), (pk_lds_void_t*)(qb_w + k * 1024), 4, 0, 0);
+        __builtin_amdgcn_global_load_lds((gl_void_t*)(p.qkv_b + k * 256 + tid), (lds_void_t*)(qb_w + k * 1024), 4, 0, 0);
     }
   }
   if (p.g0) {
@@ -456,7 +413,7 @@ __global__ __launch_bounds__(kPkThreads, 1) void ffn_packed_kernel(const FfnPack
 #pragma unroll
       for (int i = 0; i < 16; ++i) pk[(2 * (i >> 1) + (part >> 1)) * 64 + (2 * (part & 1) + (i & 1)) * 16] = xv[i];
     }
-    sum = pk_sum_quad(sum);
+    sum = sum_quad(sum);
     const float mean = sum * (1.0f / 256.0f);
     float q = 0.f;
 #pragma unroll
@@ -464,7 +421,7 @@ __global__ __launch_bounds__(kPkThreads, 1) void ffn_packed_kernel(const FfnPack
       xv[i] -= mean;
       q += (xv[i][0] * xv[i][0] + xv[i][1] * xv[i][1]) + (xv[i][2] * xv[i][2] + xv[i][3] * xv[i][3]);
     }
-    q = pk_sum_quad(q);
+    q = sum_quad(q);
     const float inv = 1.0f / sqrtf(q * (1.0f / 256.0f) + p.eps);
     __syncthreads();  // gamma0 / beta0 (all four waves' quarters) are in LDS
     const f32x4* g0l = reinterpret_cast<const f32x4*>(smem + kPkOffPar0) + part * 2;
@@ -474,10 +431,10 @@ __global__ __launch_bounds__(kPkThreads, 1) void ffn_packed_kernel(const FfnPack
       const f32x4 ga = g0l[8 * j], gb = g0l[8 * j + 1], ba = g0l[64 + 8 * j], bb = g0l[64 + 8 * j + 1];
       const f32x4 a0 = xv[2 * j], a1 = xv[2 * j + 1];
       *reinterpret_cast<uint4*>(dst + 64 * j) =
-          make_uint4(pk_pack_bf16(a0[0] * inv * ga[0] + ba[0], a0[1] * inv * ga[1] + ba[1]),
-                     pk_pack_bf16(a0[2] * inv * ga[2] + ba[2], a0[3] * inv * ga[3] + ba[3]),
-                     pk_pack_bf16(a1[0] * inv * gb[0] + bb[0], a1[1] * inv * gb[1] + bb[1]),
-                     pk_pack_bf16(a1[2] * inv * gb[2] + bb[2], a1[3] * inv * gb[3] + bb[3]));
+          make_uint4(pack2_bf16(a0[0] * inv * ga[0] + ba[0], a0[1] * inv * ga[1] + ba[1]),
+                     pack2_bf16(a0[2] * inv * ga[2] + ba[2], a0[3] * inv * ga[3] + ba[3]),
+                     pack2_bf16(a1[0] * inv * gb[0] + bb[0], a1[1] * inv * gb[1] + bb[1]),
+                     pack2_bf16(a1[2] * inv * gb[2] + bb[2], a1[3] * inv * gb[3] + bb[3]));
     }
   } else {
     f32x4 av[8];  // (16 raw bytes each; a native vector type: arrays of HIP's uint4 struct stay in scratch)
@@ -530,7 +487,7 @@ __global__ __launch_bounds__(kPkThreads, 1) void ffn_packed_kernel(const FfnPack
              b0lo, b0hi);
     asm volatile("s_nop 15\n\ts_nop 3" : "+v"(SA[0][0]), "+v"(SA[0][1]), "+v"(SA[0][2]), "+v"(SA[0][3]), "+v"(SA[1][0]),
                  "+v"(SA[1][1]), "+v"(SA[1][2]), "+v"(SA[1][3]));  // MFMA result -> VALU read
-    pk_static_for<65>([&](auto nc) __attribute__((always_inline)) { nano(nc, SA); });  // first half of block 0's Swish, exposed
+    static_for<65>([&](auto nc) __attribute__((always_inline)) { nano(nc, SA); });  // first half of block 0's Swish, exposed
     // (no second product ran to fetch k-step 1)
     PK_LDS(af[1][0], a_addr[0], 1 << 6);
     PK_LDS(af[1][1], a_addr[1], 1 << 6);
@@ -640,8 +597,8 @@ __global__ __launch_bounds__(kPkThreads, 1) void ffn_packed_kernel(const FfnPack
   // A row lives in the 4 lanes {c, c + 16, c + 32, c + 48} of one wave: two shuffles, no LDS.
   // (the statistics come in as s, q; the normalised values' own statistics go out the same way, for a LayerNorm chained behind)
   auto layer_norm = [&](const float* gam, const float* bet, float& s, float& q) __attribute__((always_inline)) {
-    s = pk_sum_xor32(pk_sum_xor16(s));
-    q = pk_sum_xor32(pk_sum_xor16(q));
+    s = sum_xor32(sum_xor16(s));
+    q = sum_xor32(sum_xor16(q));
     const float mean = s * (1.0f / 256.0f);
     const float var = fmaxf(q * (1.0f / 256.0f) - mean * mean, 0.0f);
     const float rstd = 1.0f / sqrtf(var + p.eps);
@@ -670,7 +627,7 @@ __global__ __launch_bounds__(kPkThreads, 1) void ffn_packed_kernel(const FfnPack
     char* arow = smem + wave * kPkTileStride + c * kPkPitch + 8 * g;
 #pragma unroll
     for (int j = 0; j < 16; ++j)
-      *reinterpret_cast<uint2*>(arow + 32 * j) = make_uint2(pk_pack_bf16(v[4 * j], v[4 * j + 1]), pk_pack_bf16(v[4 * j + 2], v[4 * j + 3]));
+      *reinterpret_cast<uint2*>(arow + 32 * j) = make_uint2(pack2_bf16(v[4 * j], v[4 * j + 1]), pack2_bf16(v[4 * j + 2], v[4 * j + 3]));
     PK_STAMP(6);
     PK_STAMP_FLUSH(0, 7);
     continue;
@@ -686,7 +643,7 @@ __global__ __launch_bounds__(kPkThreads, 1) void ffn_packed_kernel(const FfnPack
     char* arow = smem + wave * kPkTileStride + c * kPkPitch + 8 * g;
 #pragma unroll
     for (int j = 0; j < 16; ++j)
-      *reinterpret_cast<uint2*>(arow + 32 * j) = make_uint2(pk_pack_bf16(v[4 * j], v[4 * j + 1]), pk_pack_bf16(v[4 * j + 2], v[4 * j + 3]));
+      *reinterpret_cast<uint2*>(arow + 32 * j) = make_uint2(pack2_bf16(v[4 * j], v[4 * j + 1]), pack2_bf16(v[4 * j + 2], v[4 * j + 3]));
   } else if (p.ln_out_bf16) {
     // A 16-feature tile is 32 B of bf16: storing from the accumulator layout writes 32-byte fragments (measured: +5 us per
     // launch).  Stage the wave's 16 x 256 tile in its private exchange slot (owner = wave, k = 1: nobody else touches it after
@@ -696,7 +653,7 @@ __global__ __launch_bounds__(kPkThreads, 1) void ffn_packed_kernel(const FfnPack
 #pragma unroll
     for (int j = 0; j < 16; ++j)
       *reinterpret_cast<uint2*>(stage + c * kPitch + 32 * j + 8 * g) =
-          make_uint2(pk_pack_bf16(v[4 * j], v[4 * j + 1]), pk_pack_bf16(v[4 * j + 2], v[4 * j + 3]));
+          make_uint2(pack2_bf16(v[4 * j], v[4 * j + 1]), pack2_bf16(v[4 * j + 2], v[4 * j + 3]));
     uint16_t* obase = reinterpret_cast<uint16_t*>(p.ln_out) + (int64_t)(m0 + 16 * wave) * p.ld_ln + (lane & 31) * 8;
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
@@ -758,11 +715,11 @@ __global__ __launch_bounds__(kPkThreads, 1) void ffn_packed_kernel(const FfnPack
     auto store_s = [&](f32x4 (&S)[2][4], int blk) __attribute__((always_inline)) {
       asm volatile("s_nop 15\n\ts_nop 3" : "+v"(S[0][0]), "+v"(S[0][1]), "+v"(S[0][2]), "+v"(S[0][3]), "+v"(S[1][0]), "+v"(S[1][1]),
                    "+v"(S[1][2]), "+v"(S[1][3]));  // MFMA result -> VALU read
-      pk_static_for<4>([&](auto sc) __attribute__((always_inline)) {
+      static_for<4>([&](auto sc) __attribute__((always_inline)) {
         constexpr int sI = decltype(sc)::value;
         const int row = m0 + 16 * ((sI + wave) & 3) + cq;
-        const uint4 pk = make_uint4(pk_pack_bf16(S[0][sI][0], S[0][sI][1]), pk_pack_bf16(S[0][sI][2], S[0][sI][3]),
-                                    pk_pack_bf16(S[1][sI][0], S[1][sI][1]), pk_pack_bf16(S[1][sI][2], S[1][sI][3]));
+        const uint4 pk = make_uint4(pack2_bf16(S[0][sI][0], S[0][sI][1]), pack2_bf16(S[0][sI][2], S[0][sI][3]),
+                                    pack2_bf16(S[1][sI][0], S[1][sI][1]), pack2_bf16(S[1][sI][2], S[1][sI][3]));
         if (row < p.M) pk_store16<(MA_FFN_WT >> 3) & 7>(p.qkv_out + (int64_t)row * p.ld_qkv + blk * kPkBlock + 8 * gq, pk);
       });
     };

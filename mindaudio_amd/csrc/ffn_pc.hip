@@ -37,30 +37,14 @@
 #include <stdlib.h>
 
 #include <type_traits>
-#include <utility>
 
 #include "../../include/mindaudio_amd.h"
 
 #include "ffn_packed.h"
+#include "device_common.h"
 #include "launch.h"
 
 namespace ma {
-
-typedef __attribute__((ext_vector_type(8))) __bf16 pc_bf16x8;
-typedef __attribute__((ext_vector_type(4))) float pc_f32x4;
-typedef __attribute__((ext_vector_type(2))) __bf16 pc_bf16x2;
-typedef __attribute__((ext_vector_type(2))) float pc_f32x2;
-typedef __attribute__((address_space(1))) void pc_gl_void_t;
-typedef __attribute__((address_space(3))) void pc_lds_void_t;
-
-template <int... Is, class F>
-__device__ __forceinline__ void pc_static_for_impl(std::integer_sequence<int, Is...>, F&& f) {
-  (f(std::integral_constant<int, Is>{}), ...);
-}
-template <int N, class F>
-__device__ __forceinline__ void pc_static_for(F&& f) {
-  pc_static_for_impl(std::make_integer_sequence<int, N>{}, f);
-}
 
 constexpr int kPcRows = 64, kPcD = 256, kPcThreads = 512;
 constexpr int kPcPitch = 544;                          // a tile: 512 B rows + 32 (conflict-free ds_read_b128, k-step = +64 B immediate)
@@ -74,21 +58,6 @@ constexpr int kPcOffQb = kPcOffPar + 10 * 1024;        // bias of the qkv tail (
 constexpr int kPcOffRed = kPcOffQb + 4096;             // LayerNorm exchange: 2 regions x (sum | sum of squares) x 4 waves x 64 rows
 constexpr int kPcLds = kPcOffRed + 4096;               // 156 672 B: one workgroup per CU (8 waves at <= 256 registers)
 
-__device__ __forceinline__ uint32_t pc_pack_bf16(float lo, float hi) {
-  const pc_bf16x2 r = __builtin_convertvector((pc_f32x2){lo, hi}, pc_bf16x2);  // v_cvt_pk_bf16_f32 (round to nearest even)
-  return *reinterpret_cast<const uint32_t*>(&r);
-}
-// x[l] + x[l ^ 16] and x[l] + x[l ^ 32] in every lane through gfx950's row swaps (ffn_packed.hip; tools/ubench/permlane_test.hip)
-__device__ __forceinline__ float pc_sum_xor16(float x) {
-  float a = x, b = x;
-  asm volatile("s_nop 1\n\tv_permlane16_swap_b32 %0, %1" : "+v"(a), "+v"(b));
-  return a + b;
-}
-__device__ __forceinline__ float pc_sum_xor32(float x) {
-  float a = x, b = x;
-  asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(a), "+v"(b));
-  return a + b;
-}
 // a wave-uniform pointer, provably so for the compiler ("s" asm operands; free when the value already lives in SGPRs)
 template <class T>
 __device__ __forceinline__ const T* pc_uniform(const T* p) {
@@ -145,7 +114,7 @@ __global__ __launch_bounds__(kPcThreads, 2) void ffn_pc_kernel(const FfnPackedPa
     return 4 * r + k;
   };
   const uint32_t voff0 = lane * 16 + 4096, voff1 = voff0 + 8192, voffo = lane * 16;
-  pc_bf16x8 ring[16];
+  bf16x8 ring[16];
 #define PC_WAIT(reg, n) asm volatile("s_waitcnt vmcnt(%1)" : "+v"(reg) : "n"(n) : "memory")
 
   // ---- weight fragments ---------------------------------------------------------------------------------------------------------------
@@ -172,7 +141,7 @@ __global__ __launch_bounds__(kPcThreads, 2) void ffn_pc_kernel(const FfnPackedPa
   // job (before its refills), so when slot q is consumed the younger loads are slots q+1..15, the 2 bias loads and slots 0..q-1 of the
   // next job -> vmcnt(17); the bias itself is followed by the 16 refills issued during the previous job -> vmcnt(16).
   const uint32_t boff = g * 32;
-  pc_f32x4 bcur[2], bnext[2];
+  f32x4 bcur[2], bnext[2];
 #define PC_LOAD_B1(dst, bptr)                                                                                       \
   do {                                                                                                             \
   const uint32_t bo_ = boff;                                                                                     \
@@ -191,11 +160,11 @@ __global__ __launch_bounds__(kPcThreads, 2) void ffn_pc_kernel(const FfnPackedPa
       char* par_w = smem + kPcOffPar + wave * 256;
 #pragma unroll
       for (int k = 0; k < 10; ++k)
-        if (srcs[k]) __builtin_amdgcn_global_load_lds((pc_gl_void_t*)(srcs[k] + tid), (pc_lds_void_t*)(par_w + k * 1024), 4, 0, 0);
+        if (srcs[k]) __builtin_amdgcn_global_load_lds((gl_void_t*)(srcs[k] + tid), (lds_void_t*)(par_w + k * 1024), 4, 0, 0);
     }
     if (p.qkv_wp)
       for (int k = 0; k * kPcThreads + wave * 64 < p.qkv_n; ++k)
-        __builtin_amdgcn_global_load_lds((pc_gl_void_t*)(p.qkv_b + k * kPcThreads + tid), (pc_lds_void_t*)(smem + kPcOffQb + (k * kPcThreads + wave * 64) * 4), 4, 0, 0);
+        __builtin_amdgcn_global_load_lds((gl_void_t*)(p.qkv_b + k * kPcThreads + tid), (lds_void_t*)(smem + kPcOffQb + (k * kPcThreads + wave * 64) * 4), 4, 0, 0);
   }
 
   // ---- activation tile -> LDS [64 rows][544 B] bf16, residual rows -> the park (float32): 8 threads per row, float4 i of thread
@@ -205,17 +174,17 @@ __global__ __launch_bounds__(kPcThreads, 2) void ffn_pc_kernel(const FfnPackedPa
     const int row = tid >> 3, part = tid & 7;
     int m = m0 + row;
     if (m >= p.M) m = p.M - 1;
-    const pc_f32x4* xr = reinterpret_cast<const pc_f32x4*>(p.x + (int64_t)m * p.ldx + part * 4);
-    pc_f32x4 xv[8], av[4];
+    const f32x4* xr = reinterpret_cast<const f32x4*>(p.x + (int64_t)m * p.ldx + part * 4);
+    f32x4 xv[8], av[4];
 #pragma unroll
     for (int i = 0; i < 8; ++i) xv[i] = xr[8 * i];
     if (!p.g0) {
 #pragma unroll
-      for (int i = 0; i < 4; ++i) av[i] = *reinterpret_cast<const pc_f32x4*>(p.a + (int64_t)m * p.lda + (part + 8 * i) * 8);  // 16 raw bytes
+      for (int i = 0; i < 4; ++i) av[i] = *reinterpret_cast<const f32x4*>(p.a + (int64_t)m * p.lda + (part + 8 * i) * 8);  // 16 raw bytes
     }
     __builtin_amdgcn_sched_barrier(0);
     {  // the same rows are the first stage's residual: parked for the O-waves' epilogue
-      pc_f32x4* pk = reinterpret_cast<pc_f32x4*>(smem + kPcOffPark + row * kPcParkPitch) + part;
+      f32x4* pk = reinterpret_cast<f32x4*>(smem + kPcOffPark + row * kPcParkPitch) + part;
 #pragma unroll
       for (int i = 0; i < 8; ++i) pk[8 * i] = xv[i];
     }
@@ -238,24 +207,24 @@ __global__ __launch_bounds__(kPcThreads, 2) void ffn_pc_kernel(const FfnPackedPa
       q += __shfl_xor(q, 4);
       const float inv = 1.0f / sqrtf(q * (1.0f / 256.0f) + p.eps);
       __syncthreads();  // gamma0 / beta0 (and every other parameter vector) are in LDS
-      const pc_f32x4* g0l = reinterpret_cast<const pc_f32x4*>(smem + kPcOffPar + 8 * 1024) + part;
+      const f32x4* g0l = reinterpret_cast<const f32x4*>(smem + kPcOffPar + 8 * 1024) + part;
       char* dst = smem + row * kPcPitch + part * 8;
 #pragma unroll
       for (int i = 0; i < 8; ++i) {
-        const pc_f32x4 ga = g0l[8 * i], be = g0l[64 + 8 * i], a = xv[i];
-        *reinterpret_cast<uint2*>(dst + 64 * i) = make_uint2(pc_pack_bf16(a[0] * inv * ga[0] + be[0], a[1] * inv * ga[1] + be[1]),
-                                                             pc_pack_bf16(a[2] * inv * ga[2] + be[2], a[3] * inv * ga[3] + be[3]));
+        const f32x4 ga = g0l[8 * i], be = g0l[64 + 8 * i], a = xv[i];
+        *reinterpret_cast<uint2*>(dst + 64 * i) = make_uint2(pack2_bf16(a[0] * inv * ga[0] + be[0], a[1] * inv * ga[1] + be[1]),
+                                                             pack2_bf16(a[2] * inv * ga[2] + be[2], a[3] * inv * ga[3] + be[3]));
       }
     } else {
       __syncthreads();  // (the parameter vectors are in LDS)
 #pragma unroll
-      for (int i = 0; i < 4; ++i) *reinterpret_cast<pc_f32x4*>(smem + row * kPcPitch + (part + 8 * i) * 16) = av[i];
+      for (int i = 0; i < 4; ++i) *reinterpret_cast<f32x4*>(smem + row * kPcPitch + (part + 8 * i) * 16) = av[i];
     }
   }
   __syncthreads();  // the a tile is complete
   PC_STAMP(1);
 
-  const uint32_t a_base = (uint32_t)(uintptr_t)(pc_lds_void_t*)(smem + c * kPcPitch + g * 16);  // a fragment of row tile rt, k-step ks: + rt * 16 * 544 + ks * 64
+  const uint32_t a_base = (uint32_t)(uintptr_t)(lds_void_t*)(smem + c * kPcPitch + g * 16);  // a fragment of row tile rt, k-step ks: + rt * 16 * 544 + ks * 64
 
   if (wave >= 4) {
     // ===================================== S-waves =======================================================================================
@@ -266,8 +235,8 @@ __global__ __launch_bounds__(kPcThreads, 2) void ffn_pc_kernel(const FfnPackedPa
       PC_LOAD_B1(bcur, p.b1 + block_of(0, sw) * 32);  // (in front of the fragments: see the counts at PC_LOAD_B1)
       PC_LOAD_S16(w0);
     }
-    pc_f32x4 SA[2][4], SB[2][4];
-    pc_bf16x8 af[4][4];
+    f32x4 SA[2][4], SB[2][4];
+    bf16x8 af[4][4];
 #define PC_AF(buf, ks)                                                                                                                \
   do { const uint32_t ab_ = a_base; asm volatile("ds_read_b128 %0, %4 offset:%5\n\tds_read_b128 %1, %4 offset:%6\n\tds_read_b128 %2, %4 offset:%7\n\tds_read_b128 %3, %4 offset:%8" \
                : "=&v"(af[buf][0]), "=&v"(af[buf][1]), "=&v"(af[buf][2]), "=&v"(af[buf][3])                                            \
@@ -282,8 +251,8 @@ __global__ __launch_bounds__(kPcThreads, 2) void ffn_pc_kernel(const FfnPackedPa
     // by the job itself otherwise.  The Swish of the previous tile is cut into 8 pieces of 4 values, half a piece behind each group of
     // 4 MFMAs: the transcendentals run while the matrix pipe works off this wave's (and the O-wave's) MFMAs.
     // Fragment loads younger than slot q when it is consumed: slots q+1..15 of this job, the 2 bias loads, 0..q-1 of the next -> vmcnt(17).
-    auto s_job = [&](auto swc, auto prec, auto nextc, pc_f32x4 (&Sn)[2][4], pc_f32x4 (&Sp)[2][4], const char* refill, pc_f32x4 (&bc)[2],
-                     pc_f32x4 (&bn)[2], const float* bnext_ptr, char* hdst) __attribute__((always_inline)) {
+    auto s_job = [&](auto swc, auto prec, auto nextc, f32x4 (&Sn)[2][4], f32x4 (&Sp)[2][4], const char* refill, f32x4 (&bc)[2],
+                     f32x4 (&bn)[2], const float* bnext_ptr, char* hdst) __attribute__((always_inline)) {
       constexpr bool SW = decltype(swc)::value, PRE = decltype(prec)::value, NEXT = decltype(nextc)::value;
       uint32_t hp[2][4][2];
       // (this job's bias was requested at the start of the previous job, in front of its 16 refills)
@@ -293,7 +262,7 @@ __global__ __launch_bounds__(kPcThreads, 2) void ffn_pc_kernel(const FfnPackedPa
         PC_AF(0, 0);
         PC_AF(1, 1);
       }
-      pc_static_for<8>([&](auto kc) __attribute__((always_inline)) {
+      static_for<8>([&](auto kc) __attribute__((always_inline)) {
         constexpr int ks = decltype(kc)::value;
         if (!(PC_X & 4)) {
           if constexpr (ks < 6) PC_AF((ks + 2) & 3, ks + 2);
@@ -303,7 +272,7 @@ __global__ __launch_bounds__(kPcThreads, 2) void ffn_pc_kernel(const FfnPackedPa
           else if constexpr (ks == 6) PC_AF_WAIT(ks & 3, 4);
           else PC_AF_WAIT(ks & 3, 0);
         }
-        pc_static_for<2>([&](auto tc) __attribute__((always_inline)) {
+        static_for<2>([&](auto tc) __attribute__((always_inline)) {
           constexpr int t = decltype(tc)::value;
           constexpr int q = 2 * ks + t;
           constexpr int st = ks >> 2, srt = ks & 3;  // the previous block's accumulator tile whose values 2 t, 2 t + 1 ride in this group
@@ -314,7 +283,7 @@ __global__ __launch_bounds__(kPcThreads, 2) void ffn_pc_kernel(const FfnPackedPa
           // the O-wave's MFMAs and this wave's own VALU work have had time to free.  (asm: hipcc moves plain arithmetic across
           // sched_barriers at instruction selection.)
           float m0, m1;
-          pc_static_for<4>([&](auto rc) __attribute__((always_inline)) {
+          static_for<4>([&](auto rc) __attribute__((always_inline)) {
             constexpr int rt = decltype(rc)::value;
             if constexpr (ks == 0) Sn[t][rt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ring[q], af[ks & 3][rt], bc[t], 0, 0, 0);
             else if (!(PC_X & 16)) Sn[t][rt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ring[q], af[ks & 3][rt], Sn[t][rt], 0, 0, 0);
@@ -339,7 +308,7 @@ __global__ __launch_bounds__(kPcThreads, 2) void ffn_pc_kernel(const FfnPackedPa
             if constexpr (!(PC_X & 1)) {
               asm volatile("v_mul_f32 %1, %1, %2\n\tv_cvt_pk_bf16_f32 %0, %3, %1" : "=v"(hp[st][srt][t]), "+v"(m1) : "v"(v1), "v"(m0));
             } else {
-              hp[st][srt][t] = pc_pack_bf16(v0, v1);
+              hp[st][srt][t] = pack2_bf16(v0, v1);
             }
           }
           __builtin_amdgcn_sched_barrier(0);
@@ -352,13 +321,13 @@ __global__ __launch_bounds__(kPcThreads, 2) void ffn_pc_kernel(const FfnPackedPa
               make_uint4(hp[0][rt][0], hp[0][rt][1], hp[1][rt][0], hp[1][rt][1]);
       }
     };
-    auto s_swish_only = [&](pc_f32x4 (&Sp)[2][4], char* hdst) __attribute__((always_inline)) {
+    auto s_swish_only = [&](f32x4 (&Sp)[2][4], char* hdst) __attribute__((always_inline)) {
 #pragma unroll
       for (int rt = 0; rt < 4; ++rt) {
-        const pc_f32x4 v0 = Sp[0][rt], v1 = Sp[1][rt];
+        const f32x4 v0 = Sp[0][rt], v1 = Sp[1][rt];
         *reinterpret_cast<uint4*>(hdst + (16 * rt + c) * kPcHPitch + (32 * sw + 8 * g) * 2) =
-            make_uint4(pc_pack_bf16(pc_swish(v0[0]), pc_swish(v0[1])), pc_pack_bf16(pc_swish(v0[2]), pc_swish(v0[3])),
-                       pc_pack_bf16(pc_swish(v1[0]), pc_swish(v1[1])), pc_pack_bf16(pc_swish(v1[2]), pc_swish(v1[3])));
+            make_uint4(pack2_bf16(pc_swish(v0[0]), pc_swish(v0[1])), pack2_bf16(pc_swish(v0[2]), pc_swish(v0[3])),
+                       pack2_bf16(pc_swish(v1[0]), pc_swish(v1[1])), pack2_bf16(pc_swish(v1[2]), pc_swish(v1[3])));
       }
     };
     char* h0 = smem + kPcOffH;
@@ -421,9 +390,9 @@ __global__ __launch_bounds__(kPcThreads, 2) void ffn_pc_kernel(const FfnPackedPa
 #undef PC_AF_WAIT
   } else {
     // ===================================== O-waves =======================================================================================
-    pc_f32x4 O[4][4];  // [column tile][row tile]: lane (c, g) = row 16 rt + c, columns 64 o + 16 ct + 4 g + r
-    pc_bf16x8 hf[4][4];
-    const uint32_t h_base = (uint32_t)(uintptr_t)(pc_lds_void_t*)(smem + kPcOffH + c * kPcHPitch + g * 16);
+    f32x4 O[4][4];  // [column tile][row tile]: lane (c, g) = row 16 rt + c, columns 64 o + 16 ct + 4 g + r
+    bf16x8 hf[4][4];
+    const uint32_t h_base = (uint32_t)(uintptr_t)(lds_void_t*)(smem + kPcOffH + c * kPcHPitch + g * 16);
 #define PC_HF(buf, HB, k)                                                                                                             \
   do { const uint32_t hb_ = h_base; asm volatile("ds_read_b128 %0, %4 offset:%5\n\tds_read_b128 %1, %4 offset:%6\n\tds_read_b128 %2, %4 offset:%7\n\tds_read_b128 %3, %4 offset:%8" \
                : "=&v"(hf[buf][0]), "=&v"(hf[buf][1]), "=&v"(hf[buf][2]), "=&v"(hf[buf][3])                                            \
@@ -442,12 +411,12 @@ __global__ __launch_bounds__(kPcThreads, 2) void ffn_pc_kernel(const FfnPackedPa
         PC_HF(2, HB, 2);
         PC_HF(3, HB, 3);
       }
-      pc_static_for<4>([&](auto kc) __attribute__((always_inline)) {
+      static_for<4>([&](auto kc) __attribute__((always_inline)) {
         constexpr int k = decltype(kc)::value;
         if (!(PC_X & 4)) PC_HF_WAIT(k, 12 - 4 * k);
         else if constexpr (k == 0) PC_HF_WAIT(0, 0);
         const char* wn = obase(nstg_, npd_, k);
-        pc_static_for<4>([&](auto cc) __attribute__((always_inline)) {
+        static_for<4>([&](auto cc) __attribute__((always_inline)) {
           constexpr int ct = decltype(cc)::value;
           constexpr int q = 4 * k + ct;
           PC_WAIT(ring[q], 15);
@@ -466,7 +435,7 @@ __global__ __launch_bounds__(kPcThreads, 2) void ffn_pc_kernel(const FfnPackedPa
     float* red = reinterpret_cast<float*>(smem + kPcOffRed);
     int nred = 0;
     // LayerNorm of the rows held as v[ct][rt] across the four O-waves (every wave of the workgroup meets the barrier inside)
-    auto layer_norm = [&](pc_f32x4 (&v)[4][4], const float* gam, const float* bet) __attribute__((always_inline)) {
+    auto layer_norm = [&](f32x4 (&v)[4][4], const float* gam, const float* bet) __attribute__((always_inline)) {
       float* rr = red + (nred & 1) * 512;
       ++nred;
 #pragma unroll
@@ -477,8 +446,8 @@ __global__ __launch_bounds__(kPcThreads, 2) void ffn_pc_kernel(const FfnPackedPa
           s += (v[ct][rt][0] + v[ct][rt][1]) + (v[ct][rt][2] + v[ct][rt][3]);
           q += (v[ct][rt][0] * v[ct][rt][0] + v[ct][rt][1] * v[ct][rt][1]) + (v[ct][rt][2] * v[ct][rt][2] + v[ct][rt][3] * v[ct][rt][3]);
         }
-        s = pc_sum_xor32(pc_sum_xor16(s));
-        q = pc_sum_xor32(pc_sum_xor16(q));
+        s = sum_xor32(sum_xor16(s));
+        q = sum_xor32(sum_xor16(q));
         if (g == 0) {
           rr[sw * 64 + 16 * rt + c] = s;
           rr[256 + sw * 64 + 16 * rt + c] = q;
@@ -504,21 +473,21 @@ __global__ __launch_bounds__(kPcThreads, 2) void ffn_pc_kernel(const FfnPackedPa
         }
       }
     };
-    auto tile_out = [&](pc_f32x4 (&v)[4][4]) __attribute__((always_inline)) {  // bf16 rows of the next activation tile
+    auto tile_out = [&](f32x4 (&v)[4][4]) __attribute__((always_inline)) {  // bf16 rows of the next activation tile
 #pragma unroll
       for (int rt = 0; rt < 4; ++rt)
 #pragma unroll
         for (int ct = 0; ct < 4; ++ct)
           *reinterpret_cast<uint2*>(smem + (16 * rt + c) * kPcPitch + (ncol + 16 * ct) * 2) =
-              make_uint2(pc_pack_bf16(v[ct][rt][0], v[ct][rt][1]), pc_pack_bf16(v[ct][rt][2], v[ct][rt][3]));
+              make_uint2(pack2_bf16(v[ct][rt][0], v[ct][rt][1]), pack2_bf16(v[ct][rt][2], v[ct][rt][3]));
     };
-    auto store_rows = [&](pc_f32x4 (&v)[4][4], float* dst, int64_t ld) __attribute__((always_inline)) {
+    auto store_rows = [&](f32x4 (&v)[4][4], float* dst, int64_t ld) __attribute__((always_inline)) {
 #pragma unroll
       for (int rt = 0; rt < 4; ++rt) {
         const int m = m0 + 16 * rt + c;
         if (m < p.M) {
 #pragma unroll
-          for (int ct = 0; ct < 4; ++ct) *reinterpret_cast<pc_f32x4*>(dst + (int64_t)m * ld + ncol + 16 * ct) = v[ct][rt];
+          for (int ct = 0; ct < 4; ++ct) *reinterpret_cast<f32x4*>(dst + (int64_t)m * ld + ncol + 16 * ct) = v[ct][rt];
         }
       }
     };
@@ -536,7 +505,7 @@ __global__ __launch_bounds__(kPcThreads, 2) void ffn_pc_kernel(const FfnPackedPa
 #pragma unroll
       for (int ct = 0; ct < 4; ++ct)
 #pragma unroll
-        for (int rt = 0; rt < 4; ++rt) O[ct][rt] = pc_f32x4{0.f, 0.f, 0.f, 0.f};
+        for (int rt = 0; rt < 4; ++rt) O[ct][rt] = f32x4{0.f, 0.f, 0.f, 0.f};
       PC_STAMP(2 + 8 * stg);
 #pragma unroll 1
       for (int pd = 0; pd < NP; pd += 2) {
@@ -577,7 +546,7 @@ __global__ __launch_bounds__(kPcThreads, 2) void ffn_pc_kernel(const FfnPackedPa
         const float4 bv = *reinterpret_cast<const float4*>(b2l + ncol + 16 * ct);
 #pragma unroll
         for (int rt = 0; rt < 4; ++rt) {
-          const pc_f32x4 xr = *reinterpret_cast<const pc_f32x4*>(park + rt * 16 * kPcParkPitch + ct * 64);
+          const f32x4 xr = *reinterpret_cast<const f32x4*>(park + rt * 16 * kPcParkPitch + ct * 64);
           O[ct][rt][0] = xr[0] + p.alpha * (O[ct][rt][0] + bv.x);
           O[ct][rt][1] = xr[1] + p.alpha * (O[ct][rt][1] + bv.y);
           O[ct][rt][2] = xr[2] + p.alpha * (O[ct][rt][2] + bv.z);
@@ -589,13 +558,13 @@ __global__ __launch_bounds__(kPcThreads, 2) void ffn_pc_kernel(const FfnPackedPa
 #pragma unroll
         for (int ct = 0; ct < 4; ++ct)
 #pragma unroll
-          for (int rt = 0; rt < 4; ++rt) *reinterpret_cast<pc_f32x4*>(park + rt * 16 * kPcParkPitch + ct * 64) = O[ct][rt];
+          for (int rt = 0; rt < 4; ++rt) *reinterpret_cast<f32x4*>(park + rt * 16 * kPcParkPitch + ct * 64) = O[ct][rt];
         layer_norm(O, par + 3 * 256, par + 4 * 256);  // a' = norm_ff_macaron'(x2): the next activation tile
         tile_out(O);
         __syncthreads();
       } else {
         const int mode = p.pair ? 1 : p.ln_mode;
-        auto emit = [&](pc_f32x4 (&v)[4][4]) __attribute__((always_inline)) {  // the launch's LayerNorm output
+        auto emit = [&](f32x4 (&v)[4][4]) __attribute__((always_inline)) {  // the launch's LayerNorm output
           if (p.qkv_wp) {
             tile_out(v);  // -> the tile of the linear_q/k/v tail
             __syncthreads();
@@ -607,7 +576,7 @@ __global__ __launch_bounds__(kPcThreads, 2) void ffn_pc_kernel(const FfnPackedPa
 #pragma unroll
                 for (int ct = 0; ct < 4; ++ct)
                   *reinterpret_cast<uint2*>(reinterpret_cast<uint16_t*>(p.ln_out) + (int64_t)m * p.ld_ln + ncol + 16 * ct) =
-                      make_uint2(pc_pack_bf16(v[ct][rt][0], v[ct][rt][1]), pc_pack_bf16(v[ct][rt][2], v[ct][rt][3]));
+                      make_uint2(pack2_bf16(v[ct][rt][0], v[ct][rt][1]), pack2_bf16(v[ct][rt][2], v[ct][rt][3]));
               }
             }
           } else {
@@ -656,7 +625,7 @@ __global__ __launch_bounds__(kPcThreads, 2) void ffn_pc_kernel(const FfnPackedPa
       const char* w0 = qbase(0);
       PC_LOAD_S16(w0);
     }
-    pc_bf16x8 af[2][4];
+    bf16x8 af[2][4];
 #define PC_AF(buf, ks)                                                                                                                \
   do { const uint32_t ab_ = a_base; asm volatile("ds_read_b128 %0, %4 offset:%5\n\tds_read_b128 %1, %4 offset:%6\n\tds_read_b128 %2, %4 offset:%7\n\tds_read_b128 %3, %4 offset:%8" \
                : "=&v"(af[buf][0]), "=&v"(af[buf][1]), "=&v"(af[buf][2]), "=&v"(af[buf][3])                                            \
@@ -669,9 +638,9 @@ __global__ __launch_bounds__(kPcThreads, 2) void ffn_pc_kernel(const FfnPackedPa
     for (int j = 0; j < nq; ++j) {
       const int blk = qblk(j);
       const char* refill = qbase(j + 1);
-      pc_f32x4 S[2][4];
+      f32x4 S[2][4];
       PC_AF(0, 0);
-      pc_static_for<8>([&](auto kc) __attribute__((always_inline)) {
+      static_for<8>([&](auto kc) __attribute__((always_inline)) {
         constexpr int ks = decltype(kc)::value;
         if constexpr (ks < 7) {
           if constexpr ((ks & 1) == 0) PC_AF(1, ks + 1);
@@ -680,12 +649,12 @@ __global__ __launch_bounds__(kPcThreads, 2) void ffn_pc_kernel(const FfnPackedPa
         } else {
           PC_AF_WAIT(ks & 1, 0);
         }
-        pc_static_for<2>([&](auto tc) __attribute__((always_inline)) {
+        static_for<2>([&](auto tc) __attribute__((always_inline)) {
           constexpr int t = decltype(tc)::value;
           constexpr int q = 2 * ks + t;
           PC_WAIT(ring[q], 15);
           if constexpr (ks == 0) {
-            const pc_f32x4 bias = *reinterpret_cast<const pc_f32x4*>(qbl + 32 * blk + 8 * g + 4 * t);
+            const f32x4 bias = *reinterpret_cast<const f32x4*>(qbl + 32 * blk + 8 * g + 4 * t);
 #pragma unroll
             for (int rt = 0; rt < 4; ++rt) S[t][rt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ring[q], af[ks & 1][rt], bias, 0, 0, 0);
           } else {
@@ -699,8 +668,8 @@ __global__ __launch_bounds__(kPcThreads, 2) void ffn_pc_kernel(const FfnPackedPa
 #pragma unroll
       for (int rt = 0; rt < 4; ++rt) {
         const int m = m0 + 16 * rt + c;
-        const uint4 pk = make_uint4(pc_pack_bf16(S[0][rt][0], S[0][rt][1]), pc_pack_bf16(S[0][rt][2], S[0][rt][3]),
-                                    pc_pack_bf16(S[1][rt][0], S[1][rt][1]), pc_pack_bf16(S[1][rt][2], S[1][rt][3]));
+        const uint4 pk = make_uint4(pack2_bf16(S[0][rt][0], S[0][rt][1]), pack2_bf16(S[0][rt][2], S[0][rt][3]),
+                                    pack2_bf16(S[1][rt][0], S[1][rt][1]), pack2_bf16(S[1][rt][2], S[1][rt][3]));
         if (m < p.M) *reinterpret_cast<uint4*>(p.qkv_out + (int64_t)m * p.ld_qkv + 32 * blk + 8 * g) = pk;
       }
     }

@@ -35,7 +35,6 @@
 #include <stdlib.h>
 
 #include <type_traits>
-#include <utility>
 
 #include "../../include/mindaudio_amd.h"
 #include "train_common.h"
@@ -43,21 +42,6 @@
 #include "launch.h"
 
 namespace ma {
-
-typedef __attribute__((ext_vector_type(8))) __bf16 ft_bf16x8;
-typedef __attribute__((address_space(1))) void ft_gl_void_t;
-typedef __attribute__((address_space(3))) void ft_lds_void_t;
-typedef __attribute__((ext_vector_type(4))) float ft_f32x4;
-typedef __attribute__((ext_vector_type(4))) uint32_t ft_u32x4;
-
-template <int... Is, class F>
-__device__ __forceinline__ void ft_static_for_impl(std::integer_sequence<int, Is...>, F&& f) {
-  (f(std::integral_constant<int, Is>{}), ...);
-}
-template <int N, class F>
-__device__ __forceinline__ void ft_static_for(F&& f) {
-  ft_static_for_impl(std::make_integer_sequence<int, N>{}, f);
-}
 
 #ifndef FT_X
 #define FT_X 0  // development ablations (tools/ffn_variants.sh): 1 = no u / h stores, 2 = no dropout hash (everything kept)
@@ -77,12 +61,7 @@ constexpr int kFtLds = kFtOffRed2 + 8 * 16 * kFtMT * 4;
 // workgroups 0, 97 and 200 writes wall_clock64() (100 MHz) at the phase boundaries; stamps stay in SGPRs until the end.
 #ifdef FT_PROF
 __device__ unsigned long long g_ft_prof[3 * 16];
-#define FT_STAMP(k)                                   \
-  do {                                                \
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); \
-    ft_ts[(k)] = wall_clock64();                      \
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); \
-  } while (0)
+#define FT_STAMP(k) MA_PHASE_STAMP(ft_ts, k)
 #else
 #define FT_STAMP(k) do { } while (0)
 #endif
@@ -165,11 +144,11 @@ __global__ __launch_bounds__(kFtThreads, 1) void ffn_train_kernel(const FfnTrain
 #define FT_MFMA_O(acc, wf, hf) asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+a"(acc) : "v"(wf), "v"(hf))
 #define FT_LDS(dst, addr, imm) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(imm) : "memory")
 
-  ft_f32x4 O[16][MT];     // accumulator slots (AGPRs)
-  ft_bf16x8 ring[16];     // W1 of block b+1 / W2 of block b / W1 of block b+2 ... rotate through the same 16 registers
-  ft_bf16x8 af[3][MT];    // activation fragments of k-step ks live in af[ks % 3]; fetched two k-steps ahead
-  ft_f32x4 b1lo, b1hi;    // bias of the block whose first product comes next: b1[8 g + 0..3], b1[8 g + 4..7]
-  ft_f32x4 SA[2][MT], SB[2][MT];
+  f32x4 O[16][MT];     // accumulator slots (AGPRs)
+  bf16x8 ring[16];     // W1 of block b+1 / W2 of block b / W1 of block b+2 ... rotate through the same 16 registers
+  bf16x8 af[3][MT];    // activation fragments of k-step ks live in af[ks % 3]; fetched two k-steps ahead
+  f32x4 b1lo, b1hi;    // bias of the block whose first product comes next: b1[8 g + 0..3], b1[8 g + 4..7]
+  f32x4 SA[2][MT], SB[2][MT];
   uint32_t hfw[MT][4];
   float tm[NE], hh[NE];
 
@@ -178,7 +157,7 @@ __global__ __launch_bounds__(kFtThreads, 1) void ffn_train_kernel(const FfnTrain
   //     4k+6: Swish' = r + h (1 - r) in r's place (tm)
   // nano 0 runs exposed in front of the second product of the PREVIOUS block, 1..P ride on it, P+1..2P on the next first product;
   // hh[] is complete (float32, no dropout yet) when that product ends, tm[] (Swish') but for its last element (train_post).
-  auto nano = [&](auto nc, ft_f32x4 (&So)[2][MT]) __attribute__((always_inline)) {
+  auto nano = [&](auto nc, f32x4 (&So)[2][MT]) __attribute__((always_inline)) {
     constexpr int n = decltype(nc)::value;
     constexpr int k = n >> 2, q = n & 3;
     auto val = [&](auto kc) __attribute__((always_inline)) -> float {
@@ -213,14 +192,14 @@ __global__ __launch_bounds__(kFtThreads, 1) void ffn_train_kernel(const FfnTrain
   // `refill` once consumed: item0 = 0 -> W1 items (the prologue), 16 -> this wave's W2 items.  With sw_tag: nano-slots P+1..2P of So.
   // LDS reads of k-step ks + 2 are issued during k-step ks; outstanding at the start of k-step ks: the MT reads of k-step ks + 1
   // (none before k-step 7, whose successor is fetched later).
-  auto product1 = [&](auto sw_tag, auto wait_tag, ft_f32x4 (&Sn)[2][MT], ft_f32x4 (&So)[2][MT], const char* refill, auto item0_tag,
-                      ft_f32x4& blo, ft_f32x4& bhi) __attribute__((always_inline)) {
+  auto product1 = [&](auto sw_tag, auto wait_tag, f32x4 (&Sn)[2][MT], f32x4 (&So)[2][MT], const char* refill, auto item0_tag,
+                      f32x4& blo, f32x4& bhi) __attribute__((always_inline)) {
     constexpr bool kSw = decltype(sw_tag)::value;
     constexpr int kWait = decltype(wait_tag)::value;
     constexpr int kItem0 = decltype(item0_tag)::value;
     FT_WAIT(blo, kWait + 1);
     FT_WAIT(bhi, kWait + 1);
-    ft_static_for<P>([&](auto ic) __attribute__((always_inline)) {
+    static_for<P>([&](auto ic) __attribute__((always_inline)) {
       constexpr int i = decltype(ic)::value;
       constexpr int ks = i / (2 * MT), t = (i / MT) & 1, s = i % MT;
       if constexpr (i % (2 * MT) == 0) {
@@ -268,7 +247,7 @@ __global__ __launch_bounds__(kFtThreads, 1) void ffn_train_kernel(const FfnTrain
   // phases on).  Outstanding when ring slot j is consumed, oldest first: W2[j..15], the block's stores (2 MT of u and h / MT of du),
   // the 2 bias loads / MT gk loads, W1''[0..j-1] -> vmcnt(15 + stores + those) (loads and stores retire in issue order on
   // gfx9-family parts).
-  ft_u32x4 gkr[BWD ? MT : 1];
+  u32x4 gkr[BWD ? MT : 1];
   uint32_t st_off[MT];
 #define FT_LOAD_GK(blk)                                                                                                \
   do {                                                                                                                 \
@@ -277,21 +256,21 @@ __global__ __launch_bounds__(kFtThreads, 1) void ffn_train_kernel(const FfnTrain
         asm volatile("global_load_dwordx4 %0, %1, %2" : "=v"(gkr[s_]) : "v"(st_off[s_]), "s"(gsrc) : "memory");        \
   } while (0)
   constexpr int kWait2 = 15 + (BWD ? (kFtStores / 2) * MT + MT : kFtStores * MT + 2);
-  auto product2 = [&](const char* refill, int next_blk, ft_f32x4 (&Snext)[2][MT]) __attribute__((always_inline)) {
-    ft_bf16x8 hf[MT];
-    ft_static_for<MT>([&](auto sc) __attribute__((always_inline)) {
+  auto product2 = [&](const char* refill, int next_blk, f32x4 (&Snext)[2][MT]) __attribute__((always_inline)) {
+    bf16x8 hf[MT];
+    static_for<MT>([&](auto sc) __attribute__((always_inline)) {
       constexpr int s = decltype(sc)::value;
-      const ft_u32x4 hv = {hfw[s][0], hfw[s][1], hfw[s][2], hfw[s][3]};
-      hf[s] = __builtin_bit_cast(ft_bf16x8, hv);
+      const u32x4 hv = {hfw[s][0], hfw[s][1], hfw[s][2], hfw[s][3]};
+      hf[s] = __builtin_bit_cast(bf16x8, hv);
     });
     if constexpr (!BWD) nano(std::integral_constant<int, 0>{}, Snext);
     asm volatile("s_nop 3" : "+v"(hf[0]), "+v"(hf[1]), "+v"(hf[2]));  // VALU write -> MFMA operand read
     if constexpr (BWD) FT_LOAD_GK(next_blk);
     else FT_LOAD_B1(next_blk);
-    ft_static_for<16>([&](auto jc) __attribute__((always_inline)) {
+    static_for<16>([&](auto jc) __attribute__((always_inline)) {
       constexpr int j = decltype(jc)::value;
       FT_WAIT(ring[j], kWait2);
-      ft_static_for<MT>([&](auto sc) __attribute__((always_inline)) {
+      static_for<MT>([&](auto sc) __attribute__((always_inline)) {
         constexpr int s = decltype(sc)::value;
         FT_MFMA_O(O[j][s], ring[j], hf[s]);
         if constexpr (s == 1 && j < MT) FT_LDS(af[1][j], a_addr[j], 1 << 6);  // k-step 1 of the next first product
@@ -321,7 +300,7 @@ __global__ __launch_bounds__(kFtThreads, 1) void ffn_train_kernel(const FfnTrain
   // not look inside inline asm)
 #define FT_ST "global_store_dwordx4 %0, %1, %2\n\ts_nop 0"
   // forward: dropout of h, u or gk, both stored
-  auto train_post = [&](int blk, ft_f32x4 (&So)[2][MT]) __attribute__((always_inline)) {
+  auto train_post = [&](int blk, f32x4 (&So)[2][MT]) __attribute__((always_inline)) {
     const char* ub = uniform(reinterpret_cast<const char*>(p.u) + ((FT_X & 4) ? 0 : blk) * (kFtBlock * 2));
     const char* hb = uniform(reinterpret_cast<const char*>(p.h) + ((FT_X & 4) ? 0 : blk) * (kFtBlock * 2));
     {  // Swish' of the last element (its nano-slot would be 2 P + 2)
@@ -331,7 +310,7 @@ __global__ __launch_bounds__(kFtThreads, 1) void ffn_train_kernel(const FfnTrain
     }
 #pragma unroll
     for (int s = 0; s < MT; ++s) {
-      ft_u32x4 uw;
+      u32x4 uw;
 #pragma unroll
       for (int t = 0; t < 2; ++t) {
         uint32_t x = (q0[s] + (uint32_t)blk * 8u + t) ^ hseed;
@@ -356,7 +335,7 @@ __global__ __launch_bounds__(kFtThreads, 1) void ffn_train_kernel(const FfnTrain
           uw[2 * t + 1] = pack2_bf16(So[t][s][2], So[t][s][3]);
         }
       }
-      const ft_u32x4 hw = {hfw[s][0], hfw[s][1], hfw[s][2], hfw[s][3]};
+      const u32x4 hw = {hfw[s][0], hfw[s][1], hfw[s][2], hfw[s][3]};
       if constexpr (kFtStores) {
         asm volatile(FT_ST ::"v"(st_off[s]), "v"(uw), "s"(ub) : "memory");
         asm volatile(FT_ST ::"v"(st_off[s]), "v"(hw), "s"(hb) : "memory");
@@ -368,7 +347,7 @@ __global__ __launch_bounds__(kFtThreads, 1) void ffn_train_kernel(const FfnTrain
   // backward: du = bf16(bf16(dh) * gk) -> the second product's operand and HBM.  gk of this block was requested at the start of the
   // PREVIOUS second product; 16 W1'' and 16 W2 loads were issued behind it, and the first product that has just ended has already
   // waited for loads younger than it: the wait is a formality that ties the registers to the loads.
-  auto bwd_post = [&](int blk, ft_f32x4 (&So)[2][MT]) __attribute__((always_inline)) {
+  auto bwd_post = [&](int blk, f32x4 (&So)[2][MT]) __attribute__((always_inline)) {
     const char* db = uniform(reinterpret_cast<const char*>(p.h) + blk * (kFtBlock * 2));
     asm volatile("s_waitcnt vmcnt(32)" : "+v"(gkr[0]), "+v"(gkr[MT > 1 ? 1 : 0]), "+v"(gkr[MT > 2 ? 2 : 0])::"memory");
 #pragma unroll
@@ -383,7 +362,7 @@ __global__ __launch_bounds__(kFtThreads, 1) void ffn_train_kernel(const FfnTrain
           hfw[s][2 * t + hlf] = pack2_bf16(d0 * __uint_as_float(w << 16), d1 * __uint_as_float(w & 0xffff0000u));
         }
       }
-      const ft_u32x4 hw = {hfw[s][0], hfw[s][1], hfw[s][2], hfw[s][3]};
+      const u32x4 hw = {hfw[s][0], hfw[s][1], hfw[s][2], hfw[s][3]};
       if constexpr (kFtStores) asm volatile(FT_ST ::"v"(st_off[s]), "v"(hw), "s"(db) : "memory");
       else asm volatile("" ::"v"(hw));
     }
@@ -400,31 +379,31 @@ __global__ __launch_bounds__(kFtThreads, 1) void ffn_train_kernel(const FfnTrain
       FT_LOAD_GK(block_of(0));
     } else {
       const float* bsrc = p.b1 + (lane < 32 ? block_of(0) : block_of(blk_wrap(1))) * kFtBlock + (lane & 31);
-      __builtin_amdgcn_global_load_lds((ft_gl_void_t*)bsrc, (ft_lds_void_t*)(smem + kFtOffBias + wave * 256), 4, 0, 0);
+      __builtin_amdgcn_global_load_lds((gl_void_t*)bsrc, (lds_void_t*)(smem + kFtOffBias + wave * 256), 4, 0, 0);
     }
   }
   {
     constexpr int IT = 16 * MT * 32 / kFtThreads;  // 16-byte pieces per thread
-    ft_f32x4 av[IT];
+    f32x4 av[IT];
 #pragma unroll
     for (int it = 0; it < IT; ++it) {
       const int idx = it * kFtThreads + tid;
       const int row = idx >> 5, ch = idx & 31;
       int m = m0 + row;
       if (m >= p.M) m = p.M - 1;
-      av[it] = *reinterpret_cast<const ft_f32x4*>(p.a + (int64_t)m * p.lda + ch * 8);
+      av[it] = *reinterpret_cast<const f32x4*>(p.a + (int64_t)m * p.lda + ch * 8);
     }
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
     for (int j = 0; j < 16; ++j)
 #pragma unroll
-      for (int s = 0; s < MT; ++s) O[j][s] = ft_f32x4{0.f, 0.f, 0.f, 0.f};
+      for (int s = 0; s < MT; ++s) O[j][s] = f32x4{0.f, 0.f, 0.f, 0.f};
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
     for (int it = 0; it < IT; ++it) {
       const int idx = it * kFtThreads + tid;
       const int row = idx >> 5, ch = idx & 31;
-      *reinterpret_cast<ft_f32x4*>(smem + row * kFtPitch + ch * 16) = av[it];
+      *reinterpret_cast<f32x4*>(smem + row * kFtPitch + ch * 16) = av[it];
     }
   }
   __syncthreads();
@@ -434,11 +413,11 @@ __global__ __launch_bounds__(kFtThreads, 1) void ffn_train_kernel(const FfnTrain
     for (int s = 0; s < MT; ++s) FT_LDS(af[0][s], a_addr[s], 0);
 #pragma unroll
     for (int s = 0; s < MT; ++s) FT_LDS(af[1][s], a_addr[s], 1 << 6);
-    ft_f32x4 b0lo = {0.f, 0.f, 0.f, 0.f}, b0hi = {0.f, 0.f, 0.f, 0.f};
+    f32x4 b0lo = {0.f, 0.f, 0.f, 0.f}, b0hi = {0.f, 0.f, 0.f, 0.f};
     b1lo = b0lo;
     b1hi = b0lo;
     if constexpr (!BWD) {  // the biases of this wave's first two blocks, from LDS: lane group g needs b1[32 blk + 8 g .. + 7]
-      const ft_f32x4* bl = reinterpret_cast<const ft_f32x4*>(smem + kFtOffBias + wave * 256) + 2 * g;
+      const f32x4* bl = reinterpret_cast<const f32x4*>(smem + kFtOffBias + wave * 256) + 2 * g;
       b0lo = bl[0];
       b0hi = bl[1];
       b1lo = bl[8];
@@ -450,7 +429,7 @@ __global__ __launch_bounds__(kFtThreads, 1) void ffn_train_kernel(const FfnTrain
     if constexpr (!BWD) {
       asm volatile("s_nop 15\n\ts_nop 3" : "+v"(SA[0][0]), "+v"(SA[0][1]), "+v"(SA[0][2]), "+v"(SA[1][0]), "+v"(SA[1][1]),
                    "+v"(SA[1][2]));  // MFMA result -> VALU read
-      ft_static_for<P + 1>([&](auto nc) __attribute__((always_inline)) { nano(nc, SA); });  // first half of block 0's Swish, exposed
+      static_for<P + 1>([&](auto nc) __attribute__((always_inline)) { nano(nc, SA); });  // first half of block 0's Swish, exposed
     }
 #pragma unroll
     for (int s = 0; s < MT; ++s) FT_LDS(af[1][s], a_addr[s], 1 << 6);  // (no second product ran to fetch k-step 1)
@@ -509,11 +488,11 @@ __global__ __launch_bounds__(kFtThreads, 1) void ffn_train_kernel(const FfnTrain
   auto ft_lds_barrier = []() __attribute__((always_inline)) { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); };
   ft_lds_barrier();  // every wave is done reading the activation tile
   FT_STAMP(5);
-  auto xslot = [&](int owner, int k) { return reinterpret_cast<ft_f32x4*>(smem + (owner * 2 + k) * kFtSlot) + lane; };
-  tc_f32x4 acc[4][MT];
+  auto xslot = [&](int owner, int k) { return reinterpret_cast<f32x4*>(smem + (owner * 2 + k) * kFtSlot) + lane; };
+  f32x4 acc[4][MT];
   {
-    ft_f32x4* d1 = xslot((wave + 1) & 3, 0);
-    ft_f32x4* d2 = xslot((wave + 2) & 3, 1);
+    f32x4* d1 = xslot((wave + 1) & 3, 0);
+    f32x4* d2 = xslot((wave + 2) & 3, 1);
 #pragma unroll
     for (int jt = 0; jt < 4; ++jt)
 #pragma unroll
@@ -524,8 +503,8 @@ __global__ __launch_bounds__(kFtThreads, 1) void ffn_train_kernel(const FfnTrain
   }
   ft_lds_barrier();
   {
-    const ft_f32x4* s1 = xslot(wave, 0);
-    const ft_f32x4* s2 = xslot(wave, 1);
+    const f32x4* s1 = xslot(wave, 0);
+    const f32x4* s2 = xslot(wave, 1);
 #pragma unroll
     for (int jt = 0; jt < 4; ++jt)
 #pragma unroll
@@ -533,7 +512,7 @@ __global__ __launch_bounds__(kFtThreads, 1) void ffn_train_kernel(const FfnTrain
   }
   ft_lds_barrier();
   {
-    ft_f32x4* d3 = xslot((wave + 3) & 3, 0);
+    f32x4* d3 = xslot((wave + 3) & 3, 0);
 #pragma unroll
     for (int jt = 0; jt < 4; ++jt)
 #pragma unroll
@@ -541,7 +520,7 @@ __global__ __launch_bounds__(kFtThreads, 1) void ffn_train_kernel(const FfnTrain
   }
   ft_lds_barrier();
   {
-    const ft_f32x4* s3 = xslot(wave, 0);
+    const f32x4* s3 = xslot(wave, 0);
 #pragma unroll
     for (int jt = 0; jt < 4; ++jt)
 #pragma unroll
@@ -570,7 +549,7 @@ __global__ __launch_bounds__(kFtThreads, 1) void ffn_train_kernel(const FfnTrain
     if (chain) {
       // norm_ff_macaron's backward of block l leaves g = the gradient of block l - 1's output, which is norm_final's output there:
       // that LayerNorm's backward follows on the same rows without a round trip of g through HBM and without a launch of its own
-      tc_f32x4 og[4][MT];
+      f32x4 og[4][MT];
       lnbwd_tail_compute<MT, false, true>(p.e, acc, xh5, rstd5, m0, p.M, wave, c, g, p.out, p.ldo, red2, (int)blockIdx.x, tin, og);
       lnbwd_stats_compute<MT>(p.e2, wave, c, g, red, xh6, rstd6);
       lnbwd_tail_compute<MT, true, false>(p.e2, og, xh6, rstd6, m0, p.M, wave, c, g, p.out, p.ldo, red2, (int)blockIdx.x, tin2);

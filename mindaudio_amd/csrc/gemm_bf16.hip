@@ -17,7 +17,6 @@
 #include <stdlib.h>
 
 #include <type_traits>
-#include <utility>
 
 #include "../../include/mindaudio_amd.h"
 #include "train_common.h"
@@ -26,14 +25,8 @@
 
 namespace ma {
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-
 constexpr int BK = 64;
 constexpr int kGemmThreads = 256;
-
-typedef __attribute__((address_space(3))) void lds_void_t;
-typedef __attribute__((address_space(1))) const void gl_void_t;
 
 struct GemmParams {
   const uint16_t* A;
@@ -63,13 +56,6 @@ struct GemmParams {
   int32_t nt_out;  // bf16 tiles leave through non-temporal stores (set by the launchers for short contractions)
 };
 
-// two f32 -> packed bf16x2, round to nearest even (v_cvt_pk_bf16_f32, gfx950)
-__device__ __forceinline__ uint32_t pack_bf16(float lo, float hi) {
-  uint32_t r;
-  asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(lo), "v"(hi));
-  return r;
-}
-
 template <bool EXT = true>
 __device__ __forceinline__ float apply_act(float v, int act) {
   // swish: x * sigmoid(x) (layers/swish.py:14-16) = x / (1 + 2^(-x log2 e))
@@ -78,15 +64,6 @@ __device__ __forceinline__ float apply_act(float v, int act) {
   if (EXT && act == 3) return __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.4426950408889634f * v));  // sigmoid
   if (EXT && act == 4) return 2.0f * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-2.8853900817779268f * v)) - 1.0f;  // tanh
   return v;
-}
-
-template <int... Is, class F>
-__device__ __forceinline__ void gemm_static_for_impl(std::integer_sequence<int, Is...>, F&& f) {
-  (f(std::integral_constant<int, Is>{}), ...);
-}
-template <int N, class F>
-__device__ __forceinline__ void gemm_static_for(F&& f) {
-  gemm_static_for_impl(std::make_integer_sequence<int, N>{}, f);
 }
 
 // ---- epilogue of a tile that lies fully inside the matrix: the code the common case runs.  (The general epilogue below decides
@@ -135,7 +112,7 @@ __device__ __forceinline__ void gemm_store_inside(const GemmParams& p, f32x4 (&a
     const int m = m0 + wm_off + i * 16 + em;
     rs[i] = ((p.row_scale && m < p.M) ? p.row_scale[m] : 1.0f) * p.alpha;
   }
-  gemm_static_for<FN>([&](auto jc) __attribute__((always_inline)) {
+  static_for<FN>([&](auto jc) __attribute__((always_inline)) {
     constexpr int j = decltype(jc)::value;
     const int n = n0 + wn_off + j * 16 + en;
     float4 bv = make_float4(0.f, 0.f, 0.f, 0.f), cs = make_float4(1.f, 1.f, 1.f, 1.f), ct = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -144,7 +121,7 @@ __device__ __forceinline__ void gemm_store_inside(const GemmParams& p, f32x4 (&a
       cs = *reinterpret_cast<const float4*>(p.col_scale + n);
       ct = *reinterpret_cast<const float4*>(p.col_shift + n);
     }
-    gemm_static_for<FM>([&](auto ic) __attribute__((always_inline)) {
+    static_for<FM>([&](auto ic) __attribute__((always_inline)) {
       constexpr int i = decltype(ic)::value;
       const int m = m0 + wm_off + i * 16 + em;
       if (OUT != 0 && m >= p.M) return;
@@ -165,7 +142,7 @@ __device__ __forceinline__ void gemm_store_inside(const GemmParams& p, f32x4 (&a
       if constexpr (OUT == 1) {
         *reinterpret_cast<float4*>(reinterpret_cast<float*>(p.out) + (int64_t)m * p.ldo + n) = make_float4(v[0], v[1], v[2], v[3]);
       } else {
-        const uint32_t lo = pack_bf16(v[0], v[1]), hi = pack_bf16(v[2], v[3]);
+        const uint32_t lo = pack2_bf16_asm(v[0], v[1]), hi = pack2_bf16_asm(v[2], v[3]);
         if constexpr (OUT == 0)
           *reinterpret_cast<uint2*>(smem + (wm_off + i * 16 + em) * (BN * 2 + 16) + (wn_off + j * 16 + en) * 2) = make_uint2(lo, hi);
         else
@@ -216,12 +193,12 @@ __device__ __forceinline__ void gemm_store_tile(const GemmParams& p, f32x4 (&acc
     else gemm_store_inside<FM, FN, EPI, BN, 2>(p, acc, m0, n0, wm_off, wn_off, smem, lane);
   } else
   // (compile-time tile indices: past a size the unroller leaves these loops rolled and the accumulators go to scratch memory)
-  gemm_static_for<FM>([&](auto ic) __attribute__((always_inline)) {
+  static_for<FM>([&](auto ic) __attribute__((always_inline)) {
     constexpr int i = decltype(ic)::value;
     const int m = m0 + wm_off + i * 16 + em;
     if (m >= p.M) return;
     const float rs = (p.row_scale ? p.row_scale[m] : 1.0f) * p.alpha;
-    gemm_static_for<FN>([&](auto jc) __attribute__((always_inline)) {
+    static_for<FN>([&](auto jc) __attribute__((always_inline)) {
       constexpr int j = decltype(jc)::value;
       const int n = n0 + wn_off + j * 16 + en;
       if (n >= p.N) return;
@@ -265,7 +242,7 @@ __device__ __forceinline__ void gemm_store_tile(const GemmParams& p, f32x4 (&acc
         }
       }
       if (p.out_bf16) {
-        const uint32_t lo = pack_bf16(v[0], v[1]), hi = pack_bf16(v[2], v[3]);
+        const uint32_t lo = pack2_bf16_asm(v[0], v[1]), hi = pack2_bf16_asm(v[2], v[3]);
         if (staged) {
           // C tile -> LDS (row-major bf16, BN*2-byte rows), whole rows leave below as 16-byte vectors
           const int lr_ = wm_off + i * 16 + em, lc_ = wn_off + j * 16 + en;
@@ -393,10 +370,10 @@ __global__ __launch_bounds__(kGemmThreads, (NST * (BM + BN) * BK * 2 > 80 * 1024
     const int64_t kw = (int64_t)kt * BK;
 #pragma unroll
     for (int g = 0; g < GA; ++g)
-      __builtin_amdgcn_global_load_lds((gl_void_t*)(a_src[g] + ka), (lds_void_t*)(st + (wave + 4 * g) * 1024), 16, 0, 0);
+      __builtin_amdgcn_global_load_lds((gl_cvoid_t*)(a_src[g] + ka), (lds_void_t*)(st + (wave + 4 * g) * 1024), 16, 0, 0);
 #pragma unroll
     for (int g = 0; g < GW; ++g)
-      __builtin_amdgcn_global_load_lds((gl_void_t*)(w_src[g] + kw),
+      __builtin_amdgcn_global_load_lds((gl_cvoid_t*)(w_src[g] + kw),
                                        (lds_void_t*)(st + BM * 128 + (wave + 4 * g) * 1024), 16, 0, 0);
   };
 
@@ -466,12 +443,7 @@ constexpr int k8Threads = 512, k8Unit = 128 * 128, k8Buf = 4 * k8Unit;  // units
 // (100 MHz) values in SGPRs and writes them out at the end of the kernel.
 #ifdef MA_G8_PROF
 __device__ unsigned long long g_g8_prof[3 * 8];
-#define G8_STAMP(k)                                    \
-  do {                                                 \
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); \
-    g8_ts[(k)] = wall_clock64();                       \
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); \
-  } while (0)
+#define G8_STAMP(k) MA_PHASE_STAMP(g8_ts, k)
 #else
 #define G8_STAMP(k) do { } while (0)
 #endif
@@ -533,11 +505,11 @@ __global__ __launch_bounds__(k8Threads, 1) void gemm_bf16_8ph_kernel(const GemmP
     char* dst = smem + buf * k8Buf + U * k8Unit + wid * 1024;
     const int64_t k0 = (int64_t)kt * BK;
     if constexpr (U == 0 || U == 3) {
-      __builtin_amdgcn_global_load_lds((gl_void_t*)(a_src[U == 3][0] + k0), (lds_void_t*)dst, 16, 0, 0);
-      __builtin_amdgcn_global_load_lds((gl_void_t*)(a_src[U == 3][1] + k0), (lds_void_t*)(dst + 8192), 16, 0, 0);
+      __builtin_amdgcn_global_load_lds((gl_cvoid_t*)(a_src[U == 3][0] + k0), (lds_void_t*)dst, 16, 0, 0);
+      __builtin_amdgcn_global_load_lds((gl_cvoid_t*)(a_src[U == 3][1] + k0), (lds_void_t*)(dst + 8192), 16, 0, 0);
     } else {
-      __builtin_amdgcn_global_load_lds((gl_void_t*)(w_src[U == 2][0] + k0), (lds_void_t*)dst, 16, 0, 0);
-      __builtin_amdgcn_global_load_lds((gl_void_t*)(w_src[U == 2][1] + k0), (lds_void_t*)(dst + 8192), 16, 0, 0);
+      __builtin_amdgcn_global_load_lds((gl_cvoid_t*)(w_src[U == 2][0] + k0), (lds_void_t*)dst, 16, 0, 0);
+      __builtin_amdgcn_global_load_lds((gl_cvoid_t*)(w_src[U == 2][1] + k0), (lds_void_t*)(dst + 8192), 16, 0, 0);
     }
   };
 
@@ -714,12 +686,12 @@ __global__ __launch_bounds__(kWsThreads, 1) void gemm_ws512_kernel(const GemmPar
       int m = tile * kWsRows + r;
       if (m >= p.M) m = p.M - 1;
       const uint16_t* src = p.A + (int64_t)m * p.lda + ((lane ^ (r & 15)) << 3);
-      __builtin_amdgcn_global_load_lds((gl_void_t*)src, (lds_void_t*)(dst + r * 1024), 16, 0, 0);
+      __builtin_amdgcn_global_load_lds((gl_cvoid_t*)src, (lds_void_t*)(dst + r * 1024), 16, 0, 0);
     }
     if constexpr (RS) {  // (every wave brings the same 32 values: the per-wave load counts stay equal)
       int m = tile * kWsRows + (lane & 31);
       if (m >= p.M) m = p.M - 1;
-      __builtin_amdgcn_global_load_lds((gl_void_t*)(p.row_scale + m), (lds_void_t*)(smem + kWsOffRs + buf * 256), 4, 0, 0);
+      __builtin_amdgcn_global_load_lds((gl_cvoid_t*)(p.row_scale + m), (lds_void_t*)(smem + kWsOffRs + buf * 256), 4, 0, 0);
     }
   };
   char* stage = smem + kWsBufs * kWsTile;
@@ -807,7 +779,7 @@ __global__ __launch_bounds__(kWsThreads, 1) void gemm_ws512_kernel(const GemmPar
 #pragma unroll
         for (int r = 0; r < 4; ++r) v[r] *= rs;
         *reinterpret_cast<uint2*>(stage + (16 * s2 + c) * kWsStagePitch + (wave * 32 + 16 * jt + 4 * g) * 2) =
-            make_uint2(pack_bf16(v[0], v[1]), pack_bf16(v[2], v[3]));
+            make_uint2(pack2_bf16_asm(v[0], v[1]), pack2_bf16_asm(v[2], v[3]));
       }
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -878,11 +850,6 @@ __global__ __launch_bounds__(256) void splitk_join_kernel(const float* __restric
   x.x += e.alpha * v[0]; x.y += e.alpha * v[1]; x.z += e.alpha * v[2]; x.w += e.alpha * v[3];
   *reinterpret_cast<float4*>(out + row * ldo + c) = x;
   if (!e.ln_g1) return;
-  auto wave_sum = [](float s) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
-    return s;
-  };
   const float mean = wave_sum((x.x + x.y) + (x.z + x.w)) * (1.0f / 256);
   x.x -= mean; x.y -= mean; x.z -= mean; x.w -= mean;
   const float var = wave_sum((x.x * x.x + x.y * x.y) + (x.z * x.z + x.w * x.w)) * (1.0f / 256);

@@ -21,11 +21,6 @@
 
 namespace ma {
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
-typedef __attribute__((ext_vector_type(2))) float f32x2;
-
 constexpr int kG2K = 256, kG2Cols = 256, kG2Threads = 256;
 constexpr int kG2StagePitch = 144;  // bf16 output staging: 128 B of a wave's 64 columns + 16 B pad
 constexpr int kG2Pitch = 544;  // LDS row pitch of the activation tile: conflict-free ds_read_b128 (see ffn_packed.hip)
@@ -51,11 +46,6 @@ struct GemmK256Params {
   int64_t ld_ln;
   float ln_eps;
 };
-
-__device__ __forceinline__ uint32_t g2_pack_bf16(float lo, float hi) {
-  const bf16x2 r = __builtin_convertvector((f32x2){lo, hi}, bf16x2);
-  return *reinterpret_cast<const uint32_t*>(&r);
-}
 
 // fragment (tile nt, k-step ks): lane (i = lane & 15, g = lane >> 4) holds W[16 nt + i][32 ks + 8 g .. + 8]
 __global__ void gemm_k256_pack_kernel(const uint16_t* __restrict__ w, int64_t ldw, int64_t total, uint4* __restrict__ out) {
@@ -171,11 +161,11 @@ __global__ __launch_bounds__(kG2Threads, NBL > 1 ? 1 : 2) void gemm_k256_kernel(
       }
       if (p.out_bf16) {  // staged in this wave's own LDS strip, written below as whole 128-byte row segments
         *reinterpret_cast<uint2*>(stage + (16 * s + c) * kG2StagePitch + (16 * jt + 4 * g) * 2) =
-            make_uint2(g2_pack_bf16(v0, v1), g2_pack_bf16(v2, v3));
+            make_uint2(pack2_bf16(v0, v1), pack2_bf16(v2, v3));
       } else if (live) {
         if (p.out_bf16)
           *reinterpret_cast<uint2*>(reinterpret_cast<uint16_t*>(p.out) + (int64_t)m * p.ldo + n) =
-              make_uint2(g2_pack_bf16(v0, v1), g2_pack_bf16(v2, v3));
+              make_uint2(pack2_bf16(v0, v1), pack2_bf16(v2, v3));
         else
           *reinterpret_cast<float4*>(reinterpret_cast<float*>(p.out) + (int64_t)m * p.ldo + n) = make_float4(v0, v1, v2, v3);
       }
@@ -236,8 +226,8 @@ __global__ __launch_bounds__(kG2Threads, NBL > 1 ? 1 : 2) void gemm_k256_kernel(
       const float4 be = *reinterpret_cast<const float4*>(p.ln_beta + n);
       const f32x4 v = acc[jt][s];
       *reinterpret_cast<uint2*>(p.ln_out + (int64_t)m * p.ld_ln + n) =
-          make_uint2(g2_pack_bf16(((v[0] - mean) * inv * ga.x + be.x) * lrs, ((v[1] - mean) * inv * ga.y + be.y) * lrs),
-                     g2_pack_bf16(((v[2] - mean) * inv * ga.z + be.z) * lrs, ((v[3] - mean) * inv * ga.w + be.w) * lrs));
+          make_uint2(pack2_bf16(((v[0] - mean) * inv * ga.x + be.x) * lrs, ((v[1] - mean) * inv * ga.y + be.y) * lrs),
+                     pack2_bf16(((v[2] - mean) * inv * ga.z + be.z) * lrs, ((v[3] - mean) * inv * ga.w + be.w) * lrs));
     }
   }
 }

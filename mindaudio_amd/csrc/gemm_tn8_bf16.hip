@@ -27,16 +27,13 @@
 
 #include "../../include/mindaudio_amd.h"
 #include "gemm_tn8.h"
+#include "device_common.h"
 #include "launch.h"
 
 namespace ma {
 
-typedef __attribute__((ext_vector_type(8))) __bf16 t8_bf16x8;
-typedef __attribute__((ext_vector_type(4))) float t8_f32x4;
 typedef short t8_v4s __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) t8_v4s t8_lds_v4s;
-typedef __attribute__((address_space(3))) void t8_lds_t;
-typedef __attribute__((address_space(1))) const void t8_gl_t;
 
 constexpr int kT8Threads = 512, kT8BK = 64, kT8Unit = 64 * 256, kT8Buf = 4 * kT8Unit, kT8Lds = 2 * kT8Buf;
 constexpr int kT8Max = 56;  // (56 x 64 B + 8 = 3 592 B of kernel arguments; 6 encoder blocks = 48 products + the decoder's 6 long ones)
@@ -61,13 +58,6 @@ struct Tn8Conv {
   int32_t H, Wd, C, Ho, Wo;
   float inv_wo, inv_ho;
 };
-
-__device__ __forceinline__ int t8_div(int m, int d, float inv) {  // floor(m / d) for 0 <= m < 2^24
-  int q = (int)((float)m * inv);
-  if (q * d > m) --q;
-  if ((q + 1) * d <= m) ++q;
-  return q;
-}
 
 // One 256 x 256 tile over the K-tiles [kt_lo, kt_lo + nk) of the contraction (Kc rows in all): out (+ i0 rows, j0 columns) is stored.
 template <bool IM2COL>
@@ -111,8 +101,8 @@ __device__ __forceinline__ void t8_tile(char* smem, const uint16_t* const A, con
       if (m >= Kc) m = Kc - 1;  // rows past Kc: finite duplicates, masked out of the A fragments below
       offa[ii] = (int64_t)m * lda;
       if (IM2COL) {
-        const int t = t8_div(m, cv.Wo, cv.inv_wo), wo = m - t * cv.Wo;
-        const int b = t8_div(t, cv.Ho, cv.inv_ho), ho = t - b * cv.Ho;
+        const int t = div_small(m, cv.Wo, cv.inv_wo), wo = m - t * cv.Wo;
+        const int b = div_small(t, cv.Ho, cv.inv_ho), ho = t - b * cv.Ho;
         offb[ii] = (((int64_t)b * cv.H + 2 * ho) * cv.Wd + 2 * wo) * cv.C;
       } else {
         offb[ii] = (int64_t)m * ldb;
@@ -124,11 +114,11 @@ __device__ __forceinline__ void t8_tile(char* smem, const uint16_t* const A, con
     constexpr int U = decltype(uc)::value;
     char* dst = smem + buf * kT8Buf + U * kT8Unit + wid * 1024;
     if constexpr (U == 0 || U == 3) {
-      __builtin_amdgcn_global_load_lds((t8_gl_t*)(a_src[U == 3][0] + offa[0]), (t8_lds_t*)dst, 16, 0, 0);
-      __builtin_amdgcn_global_load_lds((t8_gl_t*)(a_src[U == 3][1] + offa[1]), (t8_lds_t*)(dst + 8192), 16, 0, 0);
+      __builtin_amdgcn_global_load_lds((gl_cvoid_t*)(a_src[U == 3][0] + offa[0]), (lds_void_t*)dst, 16, 0, 0);
+      __builtin_amdgcn_global_load_lds((gl_cvoid_t*)(a_src[U == 3][1] + offa[1]), (lds_void_t*)(dst + 8192), 16, 0, 0);
     } else {
-      __builtin_amdgcn_global_load_lds((t8_gl_t*)(b_src[U == 2][0] + offb[0]), (t8_lds_t*)dst, 16, 0, 0);
-      __builtin_amdgcn_global_load_lds((t8_gl_t*)(b_src[U == 2][1] + offb[1]), (t8_lds_t*)(dst + 8192), 16, 0, 0);
+      __builtin_amdgcn_global_load_lds((gl_cvoid_t*)(b_src[U == 2][0] + offb[0]), (lds_void_t*)dst, 16, 0, 0);
+      __builtin_amdgcn_global_load_lds((gl_cvoid_t*)(b_src[U == 2][1] + offb[1]), (lds_void_t*)(dst + 8192), 16, 0, 0);
     }
   };
 
@@ -143,12 +133,12 @@ __device__ __forceinline__ void t8_tile(char* smem, const uint16_t* const A, con
 #pragma unroll
   for (int j = 0; j < 2; ++j) off_b[j] = r_frag * 256 + (((wc * 2 + j) ^ fsw) << 5) + lb * 8;
 
-  t8_f32x4 acc[8][4], cs[2];
+  f32x4 acc[8][4], cs[2];
 #pragma unroll
   for (int i = 0; i < 8; ++i)
 #pragma unroll
-    for (int j = 0; j < 4; ++j) acc[i][j] = t8_f32x4{0.f, 0.f, 0.f, 0.f};
-  cs[0] = cs[1] = t8_f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+  cs[0] = cs[1] = f32x4{0.f, 0.f, 0.f, 0.f};
   t8_v4s af[4][2][2], bfr[2][2][2];  // [fragment][k-half][rows 0-3 | 4-7]
 
   auto load_a = [&](const char* unit) __attribute__((always_inline)) {
@@ -172,10 +162,10 @@ __device__ __forceinline__ void t8_tile(char* smem, const uint16_t* const A, con
   auto frag = [](const t8_v4s (&f)[2]) __attribute__((always_inline)) {
     typedef short v8s __attribute__((ext_vector_type(8)));
     const v8s v = {f[0][0], f[0][1], f[0][2], f[0][3], f[1][0], f[1][1], f[1][2], f[1][3]};
-    return __builtin_bit_cast(t8_bf16x8, v);
+    return __builtin_bit_cast(bf16x8, v);
   };
   const uint4 ones_pk = make_uint4(0x3f803f80u, 0x3f803f80u, 0x3f803f80u, 0x3f803f80u);  // bf16 1.0 x 8
-  const t8_bf16x8 ones = __builtin_bit_cast(t8_bf16x8, ones_pk);
+  const bf16x8 ones = __builtin_bit_cast(bf16x8, ones_pk);
   int kt = 0;
   // zero the contraction rows past Kc in the A fragments of the last K-tile (element e of a lane = row base + e)
   auto mask_tail = [&]() __attribute__((always_inline)) {

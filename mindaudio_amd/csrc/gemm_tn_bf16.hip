@@ -18,14 +18,10 @@
 #include "../../include/mindaudio_amd.h"
 
 #include "gemm_tn8.h"
+#include "device_common.h"
 #include "launch.h"
 
 namespace ma {
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((address_space(3))) void tn_lds_t;
-typedef __attribute__((address_space(1))) const void tn_gl_t;
 
 struct TnParams {
   const uint16_t* A;  // (Kc, >= Mo) row stride lda
@@ -49,13 +45,6 @@ template <int ROWB>
 __device__ __forceinline__ int tn_f(int r) {
   if (ROWB == 256) return (r & 3) | (((r >> 3) & 1) << 2);  // 8 granules per row
   return ((r >> 1) & 1) | (((r >> 3) & 1) << 1);            // 128-byte rows: 4 granules, two rows per bank sweep
-}
-
-__device__ __forceinline__ int tn_div(int m, int d, float inv) {  // floor(m / d) for 0 <= m < 2^24
-  int q = (int)((float)m * inv);
-  if (q * d > m) --q;
-  if ((q + 1) * d <= m) ++q;
-  return q;
 }
 
 template <int BM, bool IM2COL>  // output rows per workgroup (columns of A): 64 or 128; output columns per workgroup: 128
@@ -110,7 +99,7 @@ __device__ __forceinline__ void tn_body(const TnParams& p, const int bx, const i
     for (int g = 0; g < GA; ++g) {
       int m = m0 + a_row[g];
       if (m >= p.Kc) m = p.Kc - 1;  // rows past Kc: finite duplicates, masked out of the A fragments below
-      __builtin_amdgcn_global_load_lds((tn_gl_t*)(a_src[g] + (int64_t)m * p.lda), (tn_lds_t*)(st + (wave + 4 * g) * 1024), 16, 0, 0);
+      __builtin_amdgcn_global_load_lds((gl_cvoid_t*)(a_src[g] + (int64_t)m * p.lda), (lds_void_t*)(st + (wave + 4 * g) * 1024), 16, 0, 0);
     }
 #pragma unroll
     for (int g = 0; g < GB; ++g) {
@@ -118,14 +107,14 @@ __device__ __forceinline__ void tn_body(const TnParams& p, const int bx, const i
       if (m >= p.Kc) m = p.Kc - 1;
       int64_t roff;
       if (IM2COL) {
-        const int t = tn_div(m, p.Wo, p.inv_wo), wo = m - t * p.Wo;
-        const int b = tn_div(t, p.Ho, p.inv_ho), ho = t - b * p.Ho;
+        const int t = div_small(m, p.Wo, p.inv_wo), wo = m - t * p.Wo;
+        const int b = div_small(t, p.Ho, p.inv_ho), ho = t - b * p.Ho;
         roff = (((int64_t)b * p.H + 2 * ho) * p.Wd + 2 * wo) * p.C;
       } else {
         roff = (int64_t)m * p.ldb;
       }
-      __builtin_amdgcn_global_load_lds((tn_gl_t*)(b_src[g] + roff),
-                                       (tn_lds_t*)(st + kABytes + (wave + 4 * g) * 1024), 16, 0, 0);
+      __builtin_amdgcn_global_load_lds((gl_cvoid_t*)(b_src[g] + roff),
+                                       (lds_void_t*)(st + kABytes + (wave + 4 * g) * 1024), 16, 0, 0);
     }
   };
 
@@ -142,7 +131,7 @@ __device__ __forceinline__ void tn_body(const TnParams& p, const int bx, const i
   const int lg = lane >> 4, la = (lane & 15) >> 2, lb = lane & 3;
   const int r_frag = lg * 8 + la;
   uint32_t off_a[FM], off_b[FN];
-  const uint32_t lds_base = (uint32_t)(uintptr_t)(tn_lds_t*)smem;
+  const uint32_t lds_base = (uint32_t)(uintptr_t)(lds_void_t*)smem;
 #pragma unroll
   for (int i = 0; i < FM; ++i) {
     const int gran = (wm * (BM / 2) + i * 16) / 16;
@@ -247,7 +236,6 @@ __device__ __forceinline__ void tn_body(const TnParams& p, const int bx, const i
     }
   }
 }
-
 
 template <int BM, bool IM2COL>
 __global__ __launch_bounds__(kTnThreads, 2) void gemm_tn_bf16_kernel(const TnParams p) {

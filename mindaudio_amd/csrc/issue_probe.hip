@@ -8,6 +8,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "device_common.h"
 #include "launch.h"
 
 namespace ma {
@@ -30,18 +31,16 @@ __global__ __launch_bounds__(256) void valu_issue_kernel(float* __restrict__ sin
 // it issues 4 MFMAs per fragment - the access pattern of ffn_packed_kernel's main loop (every fragment has one consumer wave, 64 rows
 // per workgroup = 4 row tiles per fragment), every CU of the chip doing the same.  One 4-wave workgroup per CU, 16-slot register
 // ring, counted vmcnt; `rounds` x 16 fragments per wave.  Host side: GB/s per CU = 4 * rounds * 16 * 1024 / t.
-typedef __attribute__((ext_vector_type(8))) __bf16 ip_bf16x8;
-typedef __attribute__((ext_vector_type(4))) float ip_f32x4;
 
 __global__ __launch_bounds__(256, 1) void weight_stream_kernel(const char* __restrict__ buf, uint32_t bytes, int rounds, float* sink) {
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const uint32_t quarter = bytes / 4;
   const char* base = buf + (size_t)wave * quarter;
-  ip_f32x4 acc[4] = {{0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}};
-  ip_bf16x8 b;
+  f32x4 acc[4] = {{0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}};
+  bf16x8 b;
   for (int i = 0; i < 8; ++i) b[i] = (__bf16)1.0f;
-  ip_bf16x8 ring[16];
+  bf16x8 ring[16];
   uint32_t off = 0;
 #define IP_LOAD(q)                                                                                   \
   do {                                                                                               \

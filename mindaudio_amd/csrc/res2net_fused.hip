@@ -18,23 +18,13 @@
 
 #include "../../include/mindaudio_amd.h"
 
+#include "device_common.h"
 #include "launch.h"
 
 namespace ma {
 
-typedef __attribute__((ext_vector_type(8))) __bf16 r2_bf16x8;
-typedef __attribute__((ext_vector_type(4))) float r2_f32x4;
 // native vector types for the register arrays: hipcc keeps arrays of HIP's uint4 / uint2 STRUCTS in scratch memory
-typedef __attribute__((ext_vector_type(4))) uint32_t r2_u32x4;
 typedef __attribute__((ext_vector_type(2))) uint32_t r2_u32x2;
-
-__device__ __forceinline__ float r2_bf2f(uint32_t h16) { return __uint_as_float(h16 << 16); }
-__device__ __forceinline__ uint32_t r2_pack(float lo, float hi) {
-  typedef __attribute__((ext_vector_type(2))) __bf16 b2;
-  typedef __attribute__((ext_vector_type(2))) float f2;
-  const b2 r = __builtin_convertvector((f2){lo, hi}, b2);  // v_cvt_pk_bf16_f32, round to nearest even
-  return *reinterpret_cast<const uint32_t*>(&r);
-}
 
 // 8 waves per workgroup, one workgroup per CU (one utterance each; the cfg-5 batch is 256 utterances = the CUs of the chip).
 //
@@ -88,13 +78,13 @@ __global__ __launch_bounds__(kR2Threads, 1) void res2net_fused_kernel(const Res2
   const int tile_bytes = (nrt * 16 + 2 * dil) * kPitch;
   float* prm = reinterpret_cast<float*>(smem + tile_bytes);  // [3][STEPS][CC]: bias | scale | shift
 
-  r2_bf16x8 wf[2][kKS];                        // the wave's weights of the current step: [16-channel fragment][k-step]
+  bf16x8 wf[2][kKS];                        // the wave's weights of the current step: [16-channel fragment][k-step]
   r2_u32x2 cur[kTPW][2];                       // x_s (+ y_{s-1}), bf16 x 4, in the accumulator layout: [row tile][fragment]
 #define R2_WLOAD(step_)                                                                                            \
   {                                                                                                                \
     const uint16_t* ws_ = p.w + (int64_t)((step_) - 1) * CC * 3 * CC + (int64_t)(cg * 32 + fi) * (3 * CC) + fg * 8; \
     _Pragma("unroll") for (int cf = 0; cf < 2; ++cf) _Pragma("unroll") for (int ks = 0; ks < kKS; ++ks)               \
-      wf[cf][ks] = *reinterpret_cast<const r2_bf16x8*>(ws_ + (int64_t)cf * 16 * (3 * CC) + ks * 32);                \
+      wf[cf][ks] = *reinterpret_cast<const bf16x8*>(ws_ + (int64_t)cf * 16 * (3 * CC) + ks * 32);                \
   }
   // cell (q, cf) of this lane: row 16 (rh + kRS q) + fi, channels cg 32 + cf 16 + fg 4 .. + 4, through buffer descriptors of THIS
   // utterance's rows (one 32-bit offset register per cell row instead of 64-bit pointers - 24 cells x two pointers were the spills of
@@ -168,19 +158,19 @@ __global__ __launch_bounds__(kR2Threads, 1) void res2net_fused_kernel(const Res2
       const int rt0 = rh + kRS * q2, rt1 = rt0 + kRS;
       if (rt0 < nrt) {
         const bool two = rt1 < nrt;
-        r2_f32x4 acc[2][2];
+        f32x4 acc[2][2];
 #pragma unroll
         for (int a = 0; a < 2; ++a)
 #pragma unroll
-          for (int cf = 0; cf < 2; ++cf) acc[a][cf] = r2_f32x4{0.f, 0.f, 0.f, 0.f};
+          for (int cf = 0; cf < 2; ++cf) acc[a][cf] = f32x4{0.f, 0.f, 0.f, 0.f};
         const char* a0 = smem + (rt0 * 16 + fi) * kPitch + fg * 16;
         const char* a1 = smem + ((two ? rt1 : rt0) * 16 + fi) * kPitch + fg * 16;  // (one tile left: computed twice, stored once)
 #pragma unroll
         for (int ks = 0; ks < kKS; ++ks) {
           const int tap = (ks * 32) / CC, c0 = (ks * 32) % CC;
           const int off = tap * dil * kPitch + c0 * 2;  // (tap - 1) d + d rows of top padding
-          const r2_bf16x8 f0 = *reinterpret_cast<const r2_bf16x8*>(a0 + off);
-          const r2_bf16x8 f1 = *reinterpret_cast<const r2_bf16x8*>(a1 + off);
+          const bf16x8 f0 = *reinterpret_cast<const bf16x8*>(a0 + off);
+          const bf16x8 f1 = *reinterpret_cast<const bf16x8*>(a1 + off);
           acc[0][0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[0][ks], f0, acc[0][0], 0, 0, 0);
           acc[1][0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[0][ks], f1, acc[1][0], 0, 0, 0);
           acc[0][1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[1][ks], f0, acc[0][1], 0, 0, 0);
@@ -195,17 +185,17 @@ __global__ __launch_bounds__(kR2Threads, 1) void res2net_fused_kernel(const Res2
             const float keep = (r >= p.H && r < p.H + p.T) ? 1.0f : 0.0f;
 #pragma unroll
             for (int cf = 0; cf < 2; ++cf) {
-              const r2_f32x4 v = acc[a][cf];
+              const f32x4 v = acc[a][cf];
               // (the next step adds the bf16-rounded y - what the separate launches read back - not the float32 value)
-              const r2_u32x2 pk = {r2_pack((fmaxf(v[0] + bv[cf].x, 0.0f) * sv[cf].x + tv[cf].x) * keep,
+              const r2_u32x2 pk = {pack2_bf16((fmaxf(v[0] + bv[cf].x, 0.0f) * sv[cf].x + tv[cf].x) * keep,
                                            (fmaxf(v[1] + bv[cf].y, 0.0f) * sv[cf].y + tv[cf].y) * keep),
-                                   r2_pack((fmaxf(v[2] + bv[cf].z, 0.0f) * sv[cf].z + tv[cf].z) * keep,
+                                   pack2_bf16((fmaxf(v[2] + bv[cf].z, 0.0f) * sv[cf].z + tv[cf].z) * keep,
                                            (fmaxf(v[3] + bv[cf].w, 0.0f) * sv[cf].w + tv[cf].w) * keep)};
               __builtin_amdgcn_raw_buffer_store_b64(pk, yrs, yo + (q2 + a) * ystr + (step * CC + cf * 16) * 2, 0, 0);
               if (step < STEPS) {
                 const r2_u32x2 xv = cur[q2 + a][cf];
-                cur[q2 + a][cf] = r2_u32x2{r2_pack(r2_bf2f(xv.x & 0xffffu) + r2_bf2f(pk.x & 0xffffu), r2_bf2f(xv.x >> 16) + r2_bf2f(pk.x >> 16)),
-                                           r2_pack(r2_bf2f(xv.y & 0xffffu) + r2_bf2f(pk.y & 0xffffu), r2_bf2f(xv.y >> 16) + r2_bf2f(pk.y >> 16))};
+                cur[q2 + a][cf] = r2_u32x2{pack2_bf16(bf2f_lo(xv.x & 0xffffu) + bf2f_lo(pk.x & 0xffffu), bf2f_lo(xv.x >> 16) + bf2f_lo(pk.x >> 16)),
+                                           pack2_bf16(bf2f_lo(xv.y & 0xffffu) + bf2f_lo(pk.y & 0xffffu), bf2f_lo(xv.y >> 16) + bf2f_lo(pk.y >> 16))};
               }
             }
           }

@@ -26,7 +26,6 @@
 #include <stdlib.h>
 
 #include <type_traits>
-#include <utility>
 
 #include "../../include/mindaudio_amd.h"
 #include "train_common.h"
@@ -34,20 +33,6 @@
 #include "launch.h"
 
 namespace ma {
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((address_space(3))) void lds_void_t;
-typedef __attribute__((address_space(1))) const void gl_void_t;
-
-template <int... Is, class F>
-__device__ __forceinline__ void rp_static_for_impl(std::integer_sequence<int, Is...>, F&& f) {
-  (f(std::integral_constant<int, Is>{}), ...);
-}
-template <int N, class F>
-__device__ __forceinline__ void rp_static_for(F&& f) {
-  rp_static_for_impl(std::make_integer_sequence<int, N>{}, f);
-}
 
 constexpr int kRpRows = 64, kRpN = 256, kRpThreads = 320;  // 4 MFMA waves + the activation-loader wave
 constexpr int kRpStage = kRpRows * 128;  // 8 KiB: 64 rows x 128 B, 16-byte chunks XOR-swizzled by (row & 7)
@@ -87,12 +72,7 @@ __global__ void rows_pack_kernel(const uint16_t* __restrict__ w, int64_t ldw, in
 // values and writes them out at the end of the kernel (MODE 5).
 #ifdef MA_RP_PROF
 __device__ unsigned long long g_rp_prof[3 * 8];
-#define RP_STAMP(k)                                    \
-  do {                                                 \
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); \
-    rp_ts[(k)] = wall_clock64();                       \
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); \
-  } while (0)
+#define RP_STAMP(k) MA_PHASE_STAMP(rp_ts, k)
 #else
 #define RP_STAMP(k) do { } while (0)
 #endif
@@ -128,7 +108,7 @@ __global__ __launch_bounds__(kRpThreads, 1) void rows_packed_kernel(const RowsPa
       char* st = smem + (chunk & (kRpStages - 1)) * kRpStage;
 #pragma unroll
       for (int i = 0; i < NI; ++i)
-        __builtin_amdgcn_global_load_lds((gl_void_t*)(a_src[i] + (int64_t)cc * 64), (lds_void_t*)(st + i * 1024), 16, 0, 0);
+        __builtin_amdgcn_global_load_lds((gl_cvoid_t*)(a_src[i] + (int64_t)cc * 64), (lds_void_t*)(st + i * 1024), 16, 0, 0);
     };
     for (int ch = 0; ch < kRpAhead; ++ch) issue_a(ch);
     if constexpr (MODE == 5) {  // the MFMA waves' LayerNorm statistics in front of their main loop: two exchanges = four barriers
@@ -207,7 +187,7 @@ __global__ __launch_bounds__(kRpThreads, 1) void rows_packed_kernel(const RowsPa
     RP_LDS(1, 0); RP_LDS(1, 1); RP_LDS(1, 2);
     if constexpr (MT == 4) RP_LDS(1, 3);
 #undef RP_LDS
-    rp_static_for<2>([&](auto kc) __attribute__((always_inline)) {
+    static_for<2>([&](auto kc) __attribute__((always_inline)) {
       constexpr int kk = decltype(kc)::value;
       if constexpr (kk == 0 && MT == 4)
         asm volatile("s_waitcnt lgkmcnt(4)" : "+v"(af[0][0]), "+v"(af[0][1]), "+v"(af[0][2]), "+v"(af[0][MT - 1])::"memory");
@@ -216,12 +196,12 @@ __global__ __launch_bounds__(kRpThreads, 1) void rows_packed_kernel(const RowsPa
       else
         asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(af[1][0]), "+v"(af[1][1]), "+v"(af[1][2]), "+v"(af[1][MT - 1])::"memory");
       __builtin_amdgcn_sched_barrier(0);
-      rp_static_for<4>([&](auto tc) __attribute__((always_inline)) {
+      static_for<4>([&](auto tc) __attribute__((always_inline)) {
         constexpr int jt = decltype(tc)::value;
         constexpr int q = kk * 4 + jt;
         asm volatile("s_waitcnt vmcnt(23)" : "+v"(ring[ST][q])::"memory");
         __builtin_amdgcn_sched_barrier(0);
-        rp_static_for<MT>([&](auto sc) __attribute__((always_inline)) {
+        static_for<MT>([&](auto sc) __attribute__((always_inline)) {
           constexpr int s = decltype(sc)::value;
           acc[jt][s] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ring[ST][q], af[kk][s], acc[jt][s], 0, 0, 0);
         });

@@ -33,28 +33,13 @@
 #include <stdlib.h>
 
 #include <type_traits>
-#include <utility>
 
 #include "../../include/mindaudio_amd.h"
 
+#include "device_common.h"
 #include "launch.h"
 
 namespace ma {
-
-typedef __attribute__((ext_vector_type(8))) __bf16 sf_bf16x8;
-typedef __attribute__((ext_vector_type(4))) float sf_f32x4;
-typedef __attribute__((ext_vector_type(2))) __bf16 sf_bf16x2;
-typedef __attribute__((ext_vector_type(2))) float sf_f32x2;
-typedef __attribute__((address_space(3))) void sf_lds_void_t;
-
-template <int... Is, class F>
-__device__ __forceinline__ void sf_static_for_impl(std::integer_sequence<int, Is...>, F&& f) {
-  (f(std::integral_constant<int, Is>{}), ...);
-}
-template <int N, class F>
-__device__ __forceinline__ void sf_static_for(F&& f) {
-  sf_static_for_impl(std::make_integer_sequence<int, N>{}, f);
-}
 
 constexpr int kSfRows = 128, kSfC = 256, kSfThreads = 512;  // 4 consumer (conv2) waves + 4 producer (conv1) waves
 constexpr int kSfIdim = 80, kSfF1 = 39, kSfF2 = 19;         // feature axis: 80 -> 39 -> 19
@@ -85,12 +70,8 @@ struct SubsampleFusedParams {
   int32_t Ho, tiles_per_utt;
 };
 
-__device__ __forceinline__ uint32_t sf_pack_bf16(float lo, float hi) {
-  const sf_bf16x2 r = __builtin_convertvector((sf_f32x2){lo, hi}, sf_bf16x2);
-  return *reinterpret_cast<const uint32_t*>(&r);
-}
 // x rounded to bf16 (nearest even), as a float
-__device__ __forceinline__ float sf_head(float x) { return __uint_as_float(sf_pack_bf16(x, 0.0f) << 16); }
+__device__ __forceinline__ float sf_head(float x) { return __uint_as_float(pack2_bf16(x, 0.0f) << 16); }
 
 // The 32 k-values of one conv1 operand row from its 9 float32 taps v: X = (head, head, tail), W = (head, tail, head) at
 // k = 0..8 | 9..17 | 18..26 (27..31 zero)  ->  sum_k X[k] W[k] = xh wh + xh wl + xl wh per tap.
@@ -112,7 +93,7 @@ __device__ __forceinline__ void sf_split_row(const float (&v)[9], uint32_t (&d)[
 #pragma unroll
   for (int t = 27; t < 32; ++t) k[t] = 0.0f;
 #pragma unroll
-  for (int j = 0; j < 16; ++j) d[j] = sf_pack_bf16(k[2 * j], k[2 * j + 1]);
+  for (int j = 0; j < 16; ++j) d[j] = pack2_bf16(k[2 * j], k[2 * j + 1]);
 }
 
 // W2 item (wave w, chunk cc, tap, tile jt): lane (i, g) holds W2[64 w + 16 jt + i][tap][32 cc + 8 g .. + 8].
@@ -239,21 +220,21 @@ __global__ __launch_bounds__(kSfThreads, 2) void subsample_fused_kernel(const Su
   auto build_patch = [&](int cc, int pw, int nprod) __attribute__((always_inline)) {
     const uint4* w1f = reinterpret_cast<const uint4*>(p.packed + kSfW2Bytes) + (2 * cc) * 64 + lane;
     const uint4 wa = w1f[0], wb = w1f[64];
-    const sf_bf16x8 a0 = *reinterpret_cast<const sf_bf16x8*>(&wa), a1 = *reinterpret_cast<const sf_bf16x8*>(&wb);
+    const bf16x8 a0 = *reinterpret_cast<const bf16x8*>(&wa), a1 = *reinterpret_cast<const bf16x8*>(&wb);
     const float4 ba = *reinterpret_cast<const float4*>(p.b1 + 32 * cc + 4 * gi);
     const float4 bb = *reinterpret_cast<const float4*>(p.b1 + 32 * cc + 16 + 4 * gi);
-    const sf_f32x4 c0 = {ba.x, ba.y, ba.z, ba.w}, c1 = {bb.x, bb.y, bb.z, bb.w};
+    const f32x4 c0 = {ba.x, ba.y, ba.z, ba.w}, c1 = {bb.x, bb.y, bb.z, bb.w};
     const char* xsrc = xim + ci * 64 + gi * 16;
     char* dst = patch + (cc & 1) * kSfPatchBytes + ci * kSfPitch + gi * 8;
     const int ntile = (npatch + 15) >> 4;
     for (int pt = pw; pt < ntile; pt += nprod) {
       const uint4 xr = *reinterpret_cast<const uint4*>(xsrc + pt * (16 * 64));
-      const sf_bf16x8 xf = *reinterpret_cast<const sf_bf16x8*>(&xr);
-      const sf_f32x4 d0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a0, xf, c0, 0, 0, 0);
-      const sf_f32x4 d1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a1, xf, c1, 0, 0, 0);
+      const bf16x8 xf = *reinterpret_cast<const bf16x8*>(&xr);
+      const f32x4 d0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a0, xf, c0, 0, 0, 0);
+      const f32x4 d1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a1, xf, c1, 0, 0, 0);
       char* o = dst + pt * (16 * kSfPitch);
-      *reinterpret_cast<uint2*>(o) = make_uint2(sf_pack_bf16(fmaxf(d0[0], 0.f), fmaxf(d0[1], 0.f)), sf_pack_bf16(fmaxf(d0[2], 0.f), fmaxf(d0[3], 0.f)));
-      *reinterpret_cast<uint2*>(o + 32) = make_uint2(sf_pack_bf16(fmaxf(d1[0], 0.f), fmaxf(d1[1], 0.f)), sf_pack_bf16(fmaxf(d1[2], 0.f), fmaxf(d1[3], 0.f)));
+      *reinterpret_cast<uint2*>(o) = make_uint2(pack2_bf16(fmaxf(d0[0], 0.f), fmaxf(d0[1], 0.f)), pack2_bf16(fmaxf(d0[2], 0.f), fmaxf(d0[3], 0.f)));
+      *reinterpret_cast<uint2*>(o + 32) = make_uint2(pack2_bf16(fmaxf(d1[0], 0.f), fmaxf(d1[1], 0.f)), pack2_bf16(fmaxf(d1[2], 0.f), fmaxf(d1[3], 0.f)));
     }
   };
   build_patch(0, wave, 8);  // the first patch: all 8 waves
@@ -289,7 +270,7 @@ __global__ __launch_bounds__(kSfThreads, 2) void subsample_fused_kernel(const Su
     int m = 16 * s + c;
     if (m >= np) m = np - 1;
     const int pos = p0 + m, ho = pos / kSfF2, wo = pos - ho * kSfF2;
-    a_addr[s] = (uint32_t)(uintptr_t)(sf_lds_void_t*)(patch + ((2 * (ho - ho0)) * kSfF1 + 2 * wo) * kSfPitch + g * 16);
+    a_addr[s] = (uint32_t)(uintptr_t)(lds_void_t*)(patch + ((2 * (ho - ho0)) * kSfF1 + 2 * wo) * kSfPitch + g * 16);
   }
   // W2 fragments: SGPR base of the flat tap + lane offset; ring of 8 = two taps
   const uint32_t voff = lane * 16 + 2048;
@@ -300,9 +281,9 @@ __global__ __launch_bounds__(kSfThreads, 2) void subsample_fused_kernel(const Su
     asm volatile("global_load_dwordx4 %0, %1, %2 offset:%3" : "=v"(dst) : "v"(voff), "s"(cb_), "n"(((jt) - 2) * 1024) \
                  : "memory");                                                                                         \
   } while (0)
-  sf_bf16x8 ring[8];
-  sf_f32x4 acc[4][8];
-  sf_bf16x8 af[2][8];
+  bf16x8 ring[8];
+  f32x4 acc[4][8];
+  bf16x8 af[2][8];
 #define SF_LDS(dst, s_, imm_) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(a_addr[s_]), "n"(imm_) : "memory")
 #define SF_LDS8(buf_, imm_)                                                                                   \
   SF_LDS(af[buf_][0], 0, imm_); SF_LDS(af[buf_][1], 1, imm_); SF_LDS(af[buf_][2], 2, imm_); SF_LDS(af[buf_][3], 3, imm_); \
@@ -325,12 +306,12 @@ __global__ __launch_bounds__(kSfThreads, 2) void subsample_fused_kernel(const Su
                    : "+v"(af[PAR][0]), "+v"(af[PAR][1]), "+v"(af[PAR][2]), "+v"(af[PAR][3]), "+v"(af[PAR][4]), "+v"(af[PAR][5]),
                      "+v"(af[PAR][6]), "+v"(af[PAR][7])::"memory");
     }
-    sf_static_for<4>([&](auto tc) __attribute__((always_inline)) {
+    static_for<4>([&](auto tc) __attribute__((always_inline)) {
       constexpr int jt = decltype(tc)::value;
       constexpr int q = PAR * 4 + jt;
       // loads younger than W(ft)[jt], oldest first: W(ft)[jt+1..3], W(ft+1)[0..3], W(ft+2)[0..jt-1] = 7
       asm volatile("s_waitcnt vmcnt(7)" : "+v"(ring[q])::"memory");
-      sf_static_for<8>([&](auto sc) __attribute__((always_inline)) {
+      static_for<8>([&](auto sc) __attribute__((always_inline)) {
         constexpr int s = decltype(sc)::value;
         acc[jt][s] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ring[q], af[PAR][s], acc[jt][s], 0, 0, 0);
       });
@@ -340,7 +321,7 @@ __global__ __launch_bounds__(kSfThreads, 2) void subsample_fused_kernel(const Su
   };
   auto chunk_mfma = [&](auto bufc, int cc) __attribute__((always_inline)) {
     constexpr int BUF = decltype(bufc)::value;  // = cc & 1; 9 cc has the same parity
-    sf_static_for<kSfTaps>([&](auto tapc) __attribute__((always_inline)) {
+    static_for<kSfTaps>([&](auto tapc) __attribute__((always_inline)) {
       constexpr int TAP = decltype(tapc)::value;
       tap_step(tapc, std::integral_constant<int, (BUF + TAP) & 1>{}, bufc, cc * kSfTaps + TAP);
     });
@@ -349,7 +330,7 @@ __global__ __launch_bounds__(kSfThreads, 2) void subsample_fused_kernel(const Su
 #pragma unroll
   for (int jt = 0; jt < 4; ++jt)
 #pragma unroll
-    for (int s = 0; s < 8; ++s) acc[jt][s] = sf_f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int s = 0; s < 8; ++s) acc[jt][s] = f32x4{0.f, 0.f, 0.f, 0.f};
   SF_LOAD(ring[0], 0, 0); SF_LOAD(ring[1], 0, 1); SF_LOAD(ring[2], 0, 2); SF_LOAD(ring[3], 0, 3);
   SF_LOAD(ring[4], 1, 0); SF_LOAD(ring[5], 1, 1); SF_LOAD(ring[6], 1, 2); SF_LOAD(ring[7], 1, 3);
   // Barriers here are RAW s_barrier: the W2 fragments in flight must stay in flight across them (a __syncthreads() would drain
@@ -397,7 +378,7 @@ __global__ __launch_bounds__(kSfThreads, 2) void subsample_fused_kernel(const Su
     for (int jt = 0; jt < 4; ++jt) {
       const float v0 = fmaxf(acc[jt][s][0] + bv[jt].x, 0.f), v1 = fmaxf(acc[jt][s][1] + bv[jt].y, 0.f);
       const float v2 = fmaxf(acc[jt][s][2] + bv[jt].z, 0.f), v3 = fmaxf(acc[jt][s][3] + bv[jt].w, 0.f);
-      *reinterpret_cast<uint2*>(srow + 32 * jt) = make_uint2(sf_pack_bf16(v0, v1), sf_pack_bf16(v2, v3));
+      *reinterpret_cast<uint2*>(srow + 32 * jt) = make_uint2(pack2_bf16(v0, v1), pack2_bf16(v2, v3));
     }
   }
   uint16_t* obase = p.out + ((int64_t)b * npos + p0) * kSfC + 64 * wave + 8 * (lane & 7);

@@ -1,10 +1,11 @@
 // Pieces shared by the training-step kernels (train_kernels.hip, gemm_k256.hip, rows_packed.hip): the counter-based dropout and
-// the epilogue description of the packed dense layers' training forms.
+// the epilogue description of the packed dense layers' training forms.  (The general device helpers are in device_common.h.)
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "../../include/mindaudio_amd.h"
+#include "device_common.h"
 
 namespace ma {
 
@@ -56,28 +57,6 @@ inline Drop make_drop(float p, uint32_t seed, uint32_t salt) {
     d.inv_keep = 1.0f / (1.0f - p);
   }
   return d;
-}
-
-// round to bf16 and back (round to nearest even; what a bf16 store followed by a load does)
-__device__ __forceinline__ float bf16_round(float f) {
-  uint32_t u = __float_as_uint(f);
-  if ((u & 0x7fffffffu) > 0x7f800000u) return f;
-  u += 0x7fffu + ((u >> 16) & 1u);
-  return __uint_as_float(u & 0xffff0000u);
-}
-// bf16_round of a pair through the hardware conversion: one v_cvt_pk_bf16_f32 + a shift and a mask instead of two five-instruction
-// integer sequences (same round-to-nearest-even; NaNs come back as the conversion's quiet NaN)
-__device__ __forceinline__ uint32_t pack2_bf16(float lo, float hi);
-__device__ __forceinline__ void bf16_round2(float& a, float& b) {
-  const uint32_t pk = pack2_bf16(a, b);
-  a = __uint_as_float(pk << 16);
-  b = __uint_as_float(pk & 0xffff0000u);
-}
-__device__ __forceinline__ uint32_t pack2_bf16(float lo, float hi) {
-  typedef __attribute__((ext_vector_type(2))) __bf16 bf2_t;
-  typedef __attribute__((ext_vector_type(2))) float f2_t;
-  const bf2_t r = __builtin_convertvector((f2_t){lo, hi}, bf2_t);  // v_cvt_pk_bf16_f32 (round to nearest even)
-  return *reinterpret_cast<const uint32_t*>(&r);
 }
 
 // Epilogue of the training forms of the packed dense layers (ma_gemm_k256_train_bf16 / ma_gemm_rows_train_bf16).
@@ -175,11 +154,6 @@ inline int train_epi_fill5(const ma_train_epilogue_t* epi, int64_t M, TrainEpi& 
   return MA_OK;
 }
 
-// (v_rcp_f32 instead of an IEEE division: 1 ulp, invisible after the bf16 rounding of every consumer)
-__device__ __forceinline__ float sigmoid_fast(float v) { return __builtin_amdgcn_rcpf(1.0f + __expf(-v)); }
-
-typedef __attribute__((ext_vector_type(4))) float tc_f32x4;
-
 // Epilogue mode 3 on a 256-wide output whose columns are split over the 4 waves of a workgroup (gemm_k256 / rows_packed layout:
 // lane (c = lane & 15, g = lane >> 4) of wave w holds rows m0 + 16 s + c, columns 64 w + 16 jt + 4 g + r in acc[jt][s][r]):
 //     z   = bf16((acc + bias) * row_scale[m])                    (what the un-fused GEMM stored)
@@ -215,17 +189,17 @@ __device__ __forceinline__ void train_epi_rows256_load(const TrainEpi& e, int m0
   __builtin_amdgcn_sched_barrier(0);
 }
 template <int MT>
-__device__ __forceinline__ void train_epi_rows256_compute(const TrainEpi& e, tc_f32x4 (&acc)[4][MT], int m0, int M, int wave, int c, int g,
+__device__ __forceinline__ void train_epi_rows256_compute(const TrainEpi& e, f32x4 (&acc)[4][MT], int m0, int M, int wave, int c, int g,
                                                           float* out, int64_t ldo, float* red, const JoinLoads<MT>& in);
 template <int MT>
-__device__ __forceinline__ void train_epi_rows256(const TrainEpi& e, tc_f32x4 (&acc)[4][MT], int m0, int M, int wave, int c, int g,
+__device__ __forceinline__ void train_epi_rows256(const TrainEpi& e, f32x4 (&acc)[4][MT], int m0, int M, int wave, int c, int g,
                                                   float* out, int64_t ldo, float* red) {
   JoinLoads<MT> in;
   train_epi_rows256_load<MT>(e, m0, M, wave, c, g, in);
   train_epi_rows256_compute<MT>(e, acc, m0, M, wave, c, g, out, ldo, red, in);
 }
 template <int MT>
-__device__ __forceinline__ void train_epi_rows256_compute(const TrainEpi& e, tc_f32x4 (&acc)[4][MT], int m0, int M, int wave, int c, int g,
+__device__ __forceinline__ void train_epi_rows256_compute(const TrainEpi& e, f32x4 (&acc)[4][MT], int m0, int M, int wave, int c, int g,
                                                           float* out, int64_t ldo, float* red, const JoinLoads<MT>& in) {
   constexpr int ROWS = 16 * MT;
   const float4 (&bv)[4] = in.bv;
@@ -248,7 +222,7 @@ __device__ __forceinline__ void train_epi_rows256_compute(const TrainEpi& e, tc_
       const float4 r = rv[s][jt];
       v[0] = r.x + e.alpha * v[0]; v[1] = r.y + e.alpha * v[1]; v[2] = r.z + e.alpha * v[2]; v[3] = r.w + e.alpha * v[3];
       if (live) *reinterpret_cast<float4*>(out + (int64_t)m * ldo + n) = make_float4(v[0], v[1], v[2], v[3]);
-      acc[jt][s] = tc_f32x4{v[0], v[1], v[2], v[3]};
+      acc[jt][s] = f32x4{v[0], v[1], v[2], v[3]};
     }
   }
   if (!e.ln_g1) return;
@@ -297,7 +271,7 @@ __device__ __forceinline__ void train_epi_rows256_compute(const TrainEpi& e, tc_
 #pragma unroll
       for (int s = 0; s < MT; ++s) {
         const float inv = 1.0f / sqrtf(var[s] * (1.0f / 256.0f) + e.eps);
-        acc[jt][s] = tc_f32x4{acc[jt][s][0] * inv * ga.x + be.x, acc[jt][s][1] * inv * ga.y + be.y, acc[jt][s][2] * inv * ga.z + be.z,
+        acc[jt][s] = f32x4{acc[jt][s][0] * inv * ga.x + be.x, acc[jt][s][1] * inv * ga.y + be.y, acc[jt][s][2] * inv * ga.z + be.z,
                               acc[jt][s][3] * inv * ga.w + be.w};
       }
     }
@@ -323,7 +297,7 @@ __device__ __forceinline__ void train_epi_rows256_compute(const TrainEpi& e, tc_
 #pragma unroll
     for (int jt = 0; jt < 4; ++jt) {
       const int n = 64 * wave + 16 * jt + 4 * g;
-      const tc_f32x4 v = acc[jt][s] * lrs;
+      const f32x4 v = acc[jt][s] * lrs;
       if (e.ln_out_bf16)
         *reinterpret_cast<uint2*>(reinterpret_cast<uint16_t*>(e.ln_out) + (int64_t)m * e.ld_ln + n) =
             make_uint2(pack2_bf16(v[0], v[1]), pack2_bf16(v[2], v[3]));
@@ -449,20 +423,20 @@ __device__ __forceinline__ void lnbwd_tail_load(const TrainEpi& e, int m0, int M
 // KEEP: the updated rows o = g + dLN/dx(dy) are NOT stored (and no dy_next is emitted): they are handed back in `okeep` for a second
 // LayerNorm backward on the same rows (ffn_train.hip: norm_ff_macaron of block l, then norm_final of block l - 1).
 template <int MT, bool DY_F32 = false, bool KEEP = false>
-__device__ __forceinline__ void lnbwd_tail_compute(const TrainEpi& e, tc_f32x4 (&acc)[4][MT], const float4 (&xv)[MT][4],
+__device__ __forceinline__ void lnbwd_tail_compute(const TrainEpi& e, f32x4 (&acc)[4][MT], const float4 (&xv)[MT][4],
                                                    const float (&rstd)[MT], int m0, int M, int wave, int c, int g, float* gout, int64_t ldg,
-                                                   float* red2, int blk, const LnTailLoads<MT>& in, tc_f32x4 (*okeep)[MT] = nullptr);
+                                                   float* red2, int blk, const LnTailLoads<MT>& in, f32x4 (*okeep)[MT] = nullptr);
 template <int MT>
-__device__ __forceinline__ void lnbwd_tail(const TrainEpi& e, tc_f32x4 (&acc)[4][MT], const float4 (&xv)[MT][4], const float (&rstd)[MT],
+__device__ __forceinline__ void lnbwd_tail(const TrainEpi& e, f32x4 (&acc)[4][MT], const float4 (&xv)[MT][4], const float (&rstd)[MT],
                                            int m0, int M, int wave, int c, int g, float* gout, int64_t ldg, float* red2, int blk) {
   LnTailLoads<MT> in;
   lnbwd_tail_load<MT>(e, m0, M, wave, c, g, gout, ldg, in);
   lnbwd_tail_compute<MT>(e, acc, xv, rstd, m0, M, wave, c, g, gout, ldg, red2, blk, in);
 }
 template <int MT, bool DY_F32, bool KEEP>
-__device__ __forceinline__ void lnbwd_tail_compute(const TrainEpi& e, tc_f32x4 (&acc)[4][MT], const float4 (&xv)[MT][4],
+__device__ __forceinline__ void lnbwd_tail_compute(const TrainEpi& e, f32x4 (&acc)[4][MT], const float4 (&xv)[MT][4],
                                                    const float (&rstd)[MT], int m0, int M, int wave, int c, int g, float* gout, int64_t ldg,
-                                                   float* red2, int blk, const LnTailLoads<MT>& in, tc_f32x4 (*okeep)[MT]) {
+                                                   float* red2, int blk, const LnTailLoads<MT>& in, f32x4 (*okeep)[MT]) {
   constexpr int ROWS = 16 * MT;
   const float4 (&gv)[MT][4] = in.gv;
   const float4 (&gam)[4] = in.gam;
@@ -489,7 +463,7 @@ __device__ __forceinline__ void lnbwd_tail_compute(const TrainEpi& e, tc_f32x4 (
 #pragma unroll
         for (int r = 0; r < 4; ++r) v[r] *= rsv[s];
       }
-      const tc_f32x4 dy = tc_f32x4{v[0], v[1], v[2], v[3]};
+      const f32x4 dy = f32x4{v[0], v[1], v[2], v[3]};
       acc[jt][s] = dy;
       const float4 xh = xv[s][jt];
       const float w0 = dy[0] * gam[jt].x, w1 = dy[1] * gam[jt].y, w2 = dy[2] * gam[jt].z, w3 = dy[3] * gam[jt].w;
@@ -519,14 +493,14 @@ __device__ __forceinline__ void lnbwd_tail_compute(const TrainEpi& e, tc_f32x4 (
     for (int jt = 0; jt < 4; ++jt) {
       const int n = 64 * wave + 16 * jt + 4 * g;
       const float4 xh = xv[s][jt];
-      const tc_f32x4 dy = acc[jt][s];
+      const f32x4 dy = acc[jt][s];
       float4 o = gv[s][jt];
       o.x += rstd[s] * (dy[0] * gam[jt].x - a - xh.x * b);
       o.y += rstd[s] * (dy[1] * gam[jt].y - a - xh.y * b);
       o.z += rstd[s] * (dy[2] * gam[jt].z - a - xh.z * b);
       o.w += rstd[s] * (dy[3] * gam[jt].w - a - xh.w * b);
       if constexpr (KEEP) {
-        okeep[jt][s] = tc_f32x4{o.x, o.y, o.z, o.w};
+        okeep[jt][s] = f32x4{o.x, o.y, o.z, o.w};
         continue;
       }
       if (live[s]) *reinterpret_cast<float4*>(gout + (int64_t)mrow[s] * ldg + n) = o;
@@ -546,7 +520,7 @@ __device__ __forceinline__ void lnbwd_tail_compute(const TrainEpi& e, tc_f32x4 (
 #pragma unroll
     for (int s = 0; s < MT; ++s) {
       if (!live[s]) continue;
-      const tc_f32x4 dy = acc[jt][s];
+      const f32x4 dy = acc[jt][s];
       const float4 xh = xv[s][jt];
       cg[0] += dy[0] * xh.x; cg[1] += dy[1] * xh.y; cg[2] += dy[2] * xh.z; cg[3] += dy[3] * xh.w;
       cb[0] += dy[0]; cb[1] += dy[1]; cb[2] += dy[2]; cb[3] += dy[3];

@@ -21,17 +21,6 @@
 
 namespace ma {
 
-__device__ __forceinline__ float bf2f(uint16_t h) { return __uint_as_float((uint32_t)h << 16); }
-__device__ __forceinline__ uint16_t f2bf(float f) {
-  uint32_t u = __float_as_uint(f);
-  if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40);  // NaN stays NaN
-  u += 0x7fffu + ((u >> 16) & 1u);                                             // round to nearest even
-  return (uint16_t)(u >> 16);
-}
-// (v_rcp_f32 instead of an IEEE division: these element-wise kernels are VALU-bound - exp, the reciprocal and the integer
-// multiplies of the dropout hash - not bandwidth-bound; 1 ulp, invisible after the bf16 rounding of every consumer)
-__device__ __forceinline__ float sigmoidf_(float v) { return __builtin_amdgcn_rcpf(1.0f + __expf(-v)); }
-
 // activation storage type of the element-wise training kernels: uint16_t = bf16 bit patterns (throughput mode) or float
 // (the float32 validation mode, entry points with the _x32 suffix)
 __device__ __forceinline__ float ldact(const uint16_t* p) { return bf2f(*p); }
@@ -39,7 +28,7 @@ __device__ __forceinline__ float ldact(const float* p) { return *p; }
 __device__ __forceinline__ void stact(uint16_t* p, float v) { *p = f2bf(v); }
 __device__ __forceinline__ void stact(float* p, float v) { *p = v; }
 // precise sigmoid for the float32 mode; the bf16 mode keeps the 1-ulp v_rcp / v_exp form (invisible after bf16 rounding)
-template <typename AT> __device__ __forceinline__ float sigm(float v) { return sigmoidf_(v); }
+template <typename AT> __device__ __forceinline__ float sigm(float v) { return sigmoid_fast(v); }
 template <> __device__ __forceinline__ float sigm<float>(float v) { return 1.0f / (1.0f + expf(-v)); }
 
 // ---- transpose (+ column sums) --------------------------------------------------------------------------------
@@ -400,8 +389,8 @@ __global__ __launch_bounds__(256) void act_dropout_fwd_kernel(const uint16_t* __
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       float v0 = __uint_as_float(w[e] << 16), v1 = __uint_as_float(w[e] & 0xffff0000u);
-      float r0 = relu ? fmaxf(v0, 0.0f) : v0 * sigmoidf_(v0);
-      float r1 = relu ? fmaxf(v1, 0.0f) : v1 * sigmoidf_(v1);
+      float r0 = relu ? fmaxf(v0, 0.0f) : v0 * sigmoid_fast(v0);
+      float r1 = relu ? fmaxf(v1, 0.0f) : v1 * sigmoid_fast(v1);
       if (d.thresh) {
         const uint64_t i = (uint64_t)i8 * 8 + 2 * e;
         r0 = keep_elem(d.seed, d.salt, i, d.thresh) ? r0 * d.inv_keep : 0.0f;
@@ -428,7 +417,7 @@ __global__ __launch_bounds__(256) void act_dropout_bwd_kernel(const uint16_t* __
       for (int q = 0; q < 2; ++q) {
         const float v = q ? __uint_as_float(wu[e] & 0xffff0000u) : __uint_as_float(wu[e] << 16);
         const float dv = q ? __uint_as_float(wd[e] & 0xffff0000u) : __uint_as_float(wd[e] << 16);
-        const float sg = sigmoidf_(v);
+        const float sg = sigmoid_fast(v);
         float gr = dv * (relu ? (v > 0.0f ? 1.0f : 0.0f) : (sg + v * sg * (1.0f - sg)));
         if (d.thresh) gr = keep_elem(d.seed, d.salt, (uint64_t)i8 * 8 + 2 * e + q, d.thresh) ? gr * d.inv_keep : 0.0f;
         g[q] = gr;
@@ -1175,10 +1164,7 @@ __global__ __launch_bounds__(256) void adam_mirror_kernel(float* __restrict__ p,
     reinterpret_cast<float4*>(m)[i] = m4;
     reinterpret_cast<float4*>(v)[i] = v4;
     reinterpret_cast<float4*>(p)[i] = p4;
-    uint32_t lo, hi;
-    asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(lo) : "v"(p4.x), "v"(p4.y));
-    asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(hi) : "v"(p4.z), "v"(p4.w));
-    reinterpret_cast<uint2*>(mirror)[i] = make_uint2(lo, hi);
+    reinterpret_cast<uint2*>(mirror)[i] = make_uint2(pack2_bf16_asm(p4.x, p4.y), pack2_bf16_asm(p4.z, p4.w));
   }
 }
 

@@ -18,6 +18,7 @@
 
 #include <stdint.h>
 
+#include "device_common.h"
 #include "launch.h"
 
 namespace {
@@ -31,12 +32,6 @@ constexpr int LDT = 160;          // LDS row stride (floats): lanes 32..63 read 
 constexpr int SEL_THREADS = 1024;  // also the bin count of the select's last histogram
 constexpr int ROWS_PER_SCAN_CHUNK = 256;
 
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 // 1 / ||x[r]|| in float64 (0 for a zero row: sklearn's normalize leaves such a row at zero); one wave per row
 __global__ __launch_bounds__(256) void inv_norm_kernel(const float* __restrict__ x, int64_t ld, int64_t rows, int D,
                                                        double* __restrict__ inv) {
@@ -48,7 +43,7 @@ __global__ __launch_bounds__(256) void inv_norm_kernel(const float* __restrict__
     const double v = (double)x[r * ld + d];
     s += v * v;
   }
-  s = wave_sum(s);
+  s = ma::wave_sum(s);
   if (lane == 0) inv[r] = s > 0.0 ? 1.0 / sqrt(s) : 0.0;
 }
 
@@ -277,8 +272,8 @@ __global__ __launch_bounds__(SEL_THREADS) void cohort_select_kernel(const float*
     s1 += (double)hist[tid] * d;
     s2 += (double)hist[tid] * d * d;
   }
-  s1 = wave_sum(s1);
-  s2 = wave_sum(s2);
+  s1 = ma::wave_sum(s1);
+  s2 = ma::wave_sum(s2);
   if ((tid & 63) == 0) {
     red[0][tid >> 6] = s1;
     red[1][tid >> 6] = s2;
@@ -324,9 +319,9 @@ __global__ __launch_bounds__(256) void trial_scores_kernel(const float* __restri
     ne += a * a;
     nt += b * b;
   }
-  dot = wave_sum(dot);
-  ne = wave_sum(ne);
-  nt = wave_sum(nt);
+  dot = ma::wave_sum(dot);
+  ne = ma::wave_sum(ne);
+  nt = ma::wave_sum(nt);
   if (lane != 0) return;
   double s = (ne > 0.0 && nt > 0.0) ? dot / (sqrt(ne) * sqrt(nt)) : 0.0;
   if (mode == MA_SCORE_NORM_Z) {

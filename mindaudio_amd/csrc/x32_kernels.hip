@@ -18,6 +18,7 @@
 
 #include "../../include/mindaudio_amd.h"
 
+#include "device_common.h"
 #include "launch.h"
 
 namespace ma {
@@ -113,16 +114,6 @@ __global__ __launch_bounds__(256) void colsum_x32_kernel(const float* __restrict
 // ---- rel-pos attention, float32 -----------------------------------------------------------------------------------
 // scores[i][j] = ((q_i + u) . k_j + (q_i + v) . p_j) / sqrt(d_k) - 10000 [mask_j == 0]   (attention.py:226-235, 100-107)
 // One wave per (query i, head h, utterance b); lanes stride the keys for the scores and own one of the d_k = 64 output columns.
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, 64));
-  return v;
-}
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
 
 // scores of query row i against every key into sc[0..T) (LDS); returns nothing.  qu / qv: LDS [64]
 __device__ __forceinline__ void score_row(const float* __restrict__ qkv, int64_t ld, const float* __restrict__ pos, int64_t ldp,

@@ -76,6 +76,34 @@ def test_product_never_imports_oracle():
                 assert "oracle" not in src.replace("no CPU fallback", ""), "%s mentions the oracle" % f
 
 
+# (file, pattern) pairs that stay outside device_common.h because moving them changed the file's device code, with the reason
+_PRIVATE_HELPER_COPIES = {
+    ("ctc.hip", "0x7fffu + ((u >> 16)"): "dlogit_bits rounds without f2bf's NaN branch; f2bf in its place changes ctc.hip's assembly",
+}
+
+
+def test_device_helpers_have_one_home():
+    """csrc/device_common.h holds the one definition of every small device helper (typedefs, static_for, bf16 conversions, wave
+    reductions ...): no other file under csrc/ defines a function of one of its names, and the patterns that every private copy of
+    static_for / sum_xor16 / f2bf contained occur nowhere else."""
+    csrc = os.path.join(ROOT, "mindaudio_amd", "csrc")
+    common = open(os.path.join(csrc, "device_common.h")).read()
+    names = set(re.findall(r"^__device__ __forceinline__ [\w ]+?\b(\w+)\(", common, flags=re.M))
+    assert {"static_for", "bf2f", "f2bf", "pack2_bf16", "pack2_bf16_asm", "wave_sum", "wave_max", "sum_xor16", "div_small"} <= names
+    alt = "|".join(sorted(names))
+    definition = re.compile(r"(?:__device__|__host__|\binline\b|\bstatic\b)[\w \*&:<>]*?\b(%s)\s*\(|\bauto (%s) = \[" % (alt, alt))
+    for fn in sorted(os.listdir(csrc)):
+        if fn == "device_common.h" or not fn.endswith((".hip", ".h", ".inc")):
+            continue
+        src = open(os.path.join(csrc, fn)).read()
+        for lineno, line in enumerate(src.split("\n"), 1):
+            m = definition.search(line.split("//")[0])
+            assert not m, "%s:%d defines %s again (it lives in device_common.h)" % (fn, lineno, m.group(1) or m.group(2))
+        for pattern in ("std::integer_sequence<int", "v_permlane16_swap_b32", "0x7fffu + ((u >> 16)"):
+            assert pattern in common
+            assert pattern not in src or (fn, pattern) in _PRIVATE_HELPER_COPIES, "%s: %r belongs in device_common.h" % (fn, pattern)
+
+
 def test_host_tables_match_oracle():
     """Host-built tables (window, mel banks) of the product vs the oracle's restatement."""
     import numpy as np
