@@ -1284,6 +1284,24 @@ int ma_aam_cosine_f32(const float* x, const float* W, int64_t B, int32_t D, int6
 int ma_aam_margin_f32(const float* cosine, const float* targets, int64_t n, float margin, float scale, int32_t easy_margin, float* out,
                       ma_stream_t stream);
 
+/* ---- phase vocoder (mindaudio/data/augment.py:828-871 _phase_vocoder; time_stretch :795-825 and pitch_shift :874-901 are
+ * ma_stft_f32 -> this -> ma_istft_f32 (-> ma_resample_fft_f32), with no layout copy in between) -----------------------------------
+ * spec: complex64 as interleaved float32, (B, frames, n_freq) for in_layout MA_STFT_FRAME_MAJOR (what ma_stft_f32 writes) or
+ * (B, n_freq, frames) for MA_STFT_FREQ_MAJOR.  out: complex64 (B, n_freq, T_out), what ma_istft_f32 reads.  step_index (int32) and
+ * step_alpha (float64), T_out device entries each: the integer and fractional parts of np.arange(0, frames, rate).
+ * Step t, i = step_index[t], a = step_alpha[t], c_j = column j of the row (zero for j outside [0, frames), never read there - the
+ * reference pads two zero columns):
+ *   out[t] = ((1 - a) |c_i| + a |c_i+1|) (cos acc_t, sin acc_t),   acc_0 = angle(c_0),
+ *   acc_t+1 = acc_t + phi + wrap(angle(c_i+1) - angle(c_i) - phi),  wrap(d) = d - 2 pi round(d / 2 pi),
+ *   phi[k] = np.linspace(0, pi hop, n_freq)[k].
+ * Angles, magnitudes, the mix, sine and cosine are float32.  phi, wrap and acc are float64, acc is reduced modulo 2 pi in float64
+ * before the sine and cosine; the reference keeps acc in the spectrogram's precision (float32 for complex64) and loses what that
+ * costs.  acc is a chunked scan over t with a summation order that depends on T_out only, without atomics: results are bit-identical
+ * from run to run and for a row computed alone or inside a batch.
+ * MA_ERR_HOP for hop < 1; MA_ERR_INVALID_ARG for B, frames or T_out < 1, n_freq < 2, an unknown layout or a null pointer. */
+int ma_phase_vocoder_f32(const float* spec, int32_t in_layout, int64_t B, int64_t frames, int32_t n_freq, const int32_t* step_index,
+                         const double* step_alpha, int64_t T_out, int32_t hop, float* out, ma_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -370,6 +370,8 @@ PROTOTYPES = {
     "ma_aam_softmax_bwd_f32": (ctypes.c_int, [vp, vp, vp, i64, i32, i64, f32, f32, vp, vp, vp, vp, vp, vp, f32, vp, vp, vp, i64, vp]),
     "ma_aam_cosine_f32": (ctypes.c_int, [vp, vp, i64, i32, i64, f32, vp, vp, vp, vp]),
     "ma_aam_margin_f32": (ctypes.c_int, [vp, vp, i64, f32, f32, i32, vp, vp]),
+    # ---- phase vocoder ----
+    "ma_phase_vocoder_f32": (ctypes.c_int, [vp, i32, i64, i64, i32, vp, vp, i64, i32, vp, vp]),
 }
 
 AUG_MIX_NOISE, AUG_MIX_BABBLE, AUG_MIX_UNIT_AVG, AUG_MIX_UNIT_PEAK, AUG_MIX_UNIT_RMS = 0, 1, 2, 3, 4  # MA_AUG_MIX_*

@@ -1,6 +1,7 @@
 """Mirror of mindaudio.data.augment for the time-domain augmenters of ECAPA training-data generation (augment.py:101-792):
 convolve1d, reverberate, add_reverb, add_noise, add_babble, drop_freq, drop_chunk, speed_perturb, rms_normalize, caculate_rms, on
-MI355X through the kernels of csrc/augment.hip.
+MI355X through the kernels of csrc/augment.hip; and for its phase vocoder (augment.py:795-901): time_stretch, _phase_vocoder,
+pitch_shift, through csrc/phase_vocoder.hip between the stft, istft and resample kernels.
 
 Conventions, as everywhere in mindaudio_amd.data: NumPy in -> NumPy out, device tensor in -> device tensor out.  Arithmetic is
 float32 on the device and the result is float32 - the reference returns float64 from most of these because it mixes in float64 file
@@ -22,7 +23,9 @@ Deviations from the reference, on purpose:
     in the reference (`np.pad(..., pad=...)`) and raises here; an int is ignored, as there.
   * add_babble, drop_chunk and speed_perturb take `[batch, time]` (the shapes the example uses); `[batch, time, channels]` is not
     built for them.
-Not built: time_stretch, pitch_shift, frequencymasking, timemasking.
+  * _phase_vocoder accumulates the phase in float64 whatever the spectrogram's precision; the reference accumulates a complex64
+    spectrogram's phase in float32 and rounds a growing phase at every step (DESIGN.md 8.2.1 has what that costs).  One rate per call.
+Not built: frequencymasking, timemasking (MindSpore ops in the reference).
 """
 import random
 
@@ -30,12 +33,13 @@ import numpy as np
 
 from .. import _host, _lib, ops
 from . import processing as _processing
+from . import spectrum as _spectrum
 from .filters import notch_filter
 from .io import read
-from .spectrum import _rows_channel_last, dB_to_amplitude
+from .spectrum import _pad_shape, _rows_channel_last, dB_to_amplitude
 
 __all__ = ["convolve1d", "reverberate", "add_reverb", "add_noise", "add_babble", "drop_freq", "drop_chunk", "speed_perturb",
-           "rms_normalize", "caculate_rms"]
+           "rms_normalize", "caculate_rms", "time_stretch", "pitch_shift", "phase_vocoder_steps"]
 
 
 def _rows_time_last(samples):
@@ -416,3 +420,99 @@ def drop_chunk(waveforms, lengths, drop_length_low=100, drop_length_high=1000, d
     if dec is None:
         return _back(rows.clone(), was_numpy)
     return _back(drop_chunk_device(rows, dec, noise_factor), was_numpy)
+
+
+# ---- phase vocoder: time_stretch, pitch_shift ------------------------------------------------------------------------------------------
+def phase_vocoder_steps(frames, rate):
+    """Host: the reference's time steps np.arange(0, frames, rate) (augment.py:841 - its own call, so the number of steps has its
+    float quirks) as (int32 column index, float64 fraction np.mod(step, 1.0))."""
+    steps = np.arange(0, frames, rate, dtype=np.float64)
+    return steps.astype(np.int32), np.mod(steps, 1.0)
+
+
+_step_tables = {}  # (frames, rate, device) -> the two tables on the device: they depend on shapes only, a repeated call uploads nothing
+
+
+def _device_steps(frames, rate, device):
+    key = (int(frames), float(rate), str(device))
+    tables = _step_tables.get(key)
+    if tables is None:
+        if len(_step_tables) >= 64:
+            _step_tables.clear()
+        index, alpha = phase_vocoder_steps(frames, rate)
+        tables = _step_tables[key] = (_dev(index, device, np.int32), _dev(alpha, device, np.float64))
+    return tables
+
+
+def phase_vocoder_device(spec, rate, hop_length):
+    """Device: spec (B, n_freq, frames) complex64 -> (B, n_freq, steps) complex64, contiguous (what istft reads).  A transposed view
+    of frame-major memory, as spectrum.stft returns, is read in place; anything else as bin-major rows."""
+    t = _host.torch()
+    b, n_freq, frames = spec.shape
+    layout = _lib.STFT_FRAME_MAJOR
+    if not spec.transpose(1, 2).is_contiguous():
+        spec, layout = spec.contiguous(), _lib.STFT_FREQ_MAJOR
+    index, alpha = _device_steps(frames, rate, spec.device)
+    out = t.empty((b, n_freq, index.shape[0], 2), dtype=t.float32, device=spec.device)
+    rc = _lib.load().ma_phase_vocoder_f32(_host.ptr(spec), layout, b, frames, n_freq, _host.ptr(index), _host.ptr(alpha), index.shape[0],
+                                          int(hop_length), _host.ptr(out), _host.current_stream_ptr())
+    _lib.check(rc, "_phase_vocoder")
+    return t.view_as_complex(out)
+
+
+def _phase_vocoder(matrix, rate, hop_length=None, n_fft=None):
+    """augment._phase_vocoder: the spectrogram `matrix` (..., n_freq, frames) resampled along time at the steps 0, rate, 2 rate, ... -
+    magnitudes interpolated between neighbouring columns, phases advanced by the accumulated wrapped phase difference.  NumPy in ->
+    complex64 NumPy out, device tensor in -> device tensor out; what spectrum.stft returns for a tensor is taken without a copy."""
+    if not rate > 0:
+        raise ValueError("rate must be a positive number")
+    t = _host.require_gpu()
+    was_numpy = not isinstance(matrix, t.Tensor)
+    D = t.as_tensor(np.asarray(matrix) if was_numpy else matrix).to(device="cuda", dtype=t.complex64)
+    if D.dim() < 2:
+        raise ValueError("matrix must be (..., 1 + n_fft/2, frames)")
+    lead, n_freq, frames = tuple(D.shape[:-2]), D.shape[-2], D.shape[-1]
+    if n_fft is None:
+        n_fft = 2 * (n_freq - 1)
+    if hop_length is None:
+        hop_length = int(n_fft // 4)
+    out = phase_vocoder_device(D.reshape((-1, n_freq, frames)), rate, hop_length)
+    out = out.reshape(lead + tuple(out.shape[1:]))
+    return out.cpu().numpy() if was_numpy else out
+
+
+def time_stretch_device(rows, rate):
+    """Device: (B, n) float32 rows -> (B, round(n / rate)) float32 - stft with its defaults, the vocoder on its frame-major memory,
+    istft.  Nothing is read back."""
+    spec = _spectrum.stft(rows)
+    return _spectrum.istft(_phase_vocoder(spec, rate), length=int(round(rows.shape[-1] / rate)))
+
+
+def time_stretch(waveforms, rate=None):
+    """augment.time_stretch: `[time]`, `[batch, time]` (or more leading axes) made 1 / rate times as long without a change of pitch.
+    NumPy in -> float64 NumPy out (the reference's istft buffer), device tensor in -> float32 device tensor out.  rate=None fails
+    with the reference's TypeError."""
+    if rate <= 0:
+        raise ValueError("rate must be a positive number")
+    rows, lead, was_numpy = _host.to_device_2d(waveforms)
+    y = time_stretch_device(rows, rate)
+    y = y.reshape(lead + (y.shape[-1],))
+    return y.cpu().numpy().astype(np.float64) if was_numpy else y
+
+
+def pitch_shift(waveforms, sr, n_steps, bins_per_octave=12):
+    """augment.pitch_shift: time_stretch by rate = 2 ** (-n_steps / bins_per_octave), then resample from sr / rate back to sr.
+    As in the reference the result is cut or zero-padded to the STRETCHED length round(n / rate), not to the input's n: the
+    resampled signal has about n samples again and the rest is zeros (n_steps > 0) or a cut (n_steps < 0) - (2, 4000) at
+    n_steps=4 comes back as (2, 5040).  NumPy in -> float64 NumPy out, device tensor in -> float32 device tensor out."""
+    rate = 2.0 ** (-float(n_steps) / bins_per_octave)
+    rows, lead, was_numpy = _host.to_device_2d(waveforms)
+    y = time_stretch_device(rows, rate)
+    n = y.shape[-1]
+    orig_freq = float(sr) / rate
+    if orig_freq != sr:  # (processing.resample hands its input back otherwise)
+        m = _processing.resampled_length(n, orig_freq, sr)
+        y = _processing.resample_batch(y, [n] * y.shape[0], [m] * y.shape[0])
+    y = _pad_shape(y, n)
+    y = y.reshape(lead + (n,))
+    return y.cpu().numpy().astype(np.float64) if was_numpy else y

@@ -131,6 +131,19 @@ def istft(stft_matrix, n_fft=None, win_length=None, hop_length=None, window="han
     return out.cpu().numpy().astype(np.float64) if was_numpy else out
 
 
+def _pad_shape(y_shift, data_shape):
+    """spectrum._pad_shape (spectrum.py:307-320): the last axis cut to `data_shape` samples, or zero-padded behind to it.  NumPy
+    array or tensor, returned as is when the length already fits."""
+    need_shape = y_shift.shape[-1]
+    if need_shape > data_shape:
+        return y_shift[..., :data_shape]
+    if need_shape < data_shape:
+        if isinstance(y_shift, np.ndarray):
+            return np.pad(y_shift, [(0, 0)] * (y_shift.ndim - 1) + [(0, data_shape - need_shape)], mode="constant")
+        return _host.torch().nn.functional.pad(y_shift, (0, data_shape - need_shape))
+    return y_shift
+
+
 def _mel_args(n_fft, win_length, hop_length, window, center, pad_mode, n_mels, sample_rate, f_min, f_max, device,
               norm="none", mel_type="htk"):
     win_length = win_length if win_length is not None else n_fft  # spectrum.py:665
