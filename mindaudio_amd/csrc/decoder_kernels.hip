@@ -387,16 +387,19 @@ __global__ __launch_bounds__(256) void mha_small_bwd_kernel(const SmallAttn<AT> 
   }
   __syncthreads();
   if (tid < Lq) {
-    float s = 0.0f;
+    // (summed in the order of dP below - four interleaved partial sums: where a row has one visible key, ctx_i = v_j and dP_ij - D_i
+    // is exactly zero, as the gradient is; as one running sum the two differed by their rounding noise.  This is the float32 form and
+    // the bf16 form beyond kSmK keys; the matrix-core form below takes dP from an MFMA and keeps that noise.)
+    float s4[4] = {0.0f, 0.0f, 0.0f, 0.0f};
     const AT* op = ctx + ((int64_t)b * p.LqT + p.q0 + tid) * ldc + h * kSmD;
 #pragma unroll
     for (int c8 = 0; c8 < kSmD / 8; ++c8) {
       float t8[8];
       d_ld8(op + c8 * 8, t8);
 #pragma unroll
-      for (int e = 0; e < 8; ++e) s = fmaf(dOs[tid][c8 * 8 + e], t8[e], s);
+      for (int e = 0; e < 8; ++e) s4[e & 3] = fmaf(dOs[tid][c8 * 8 + e], t8[e], s4[e & 3]);
     }
-    Dq[tid] = s;
+    Dq[tid] = (s4[0] + s4[1]) + (s4[2] + s4[3]);
   }
   __syncthreads();
   for (int j = tid; j < Lk; j += 256) {
@@ -415,6 +418,9 @@ __global__ __launch_bounds__(256) void mha_small_bwd_kernel(const SmallAttn<AT> 
       dkr[d] = 0.0f;
     }
     for (int i = 0; i < Lq; ++i) {
+      // (KEEP this order - feature d into partial sum d & 3, combined as (0 + 1) + (2 + 3) - equal to that of Dq above: a row with
+      // one visible key relies on dp == Dq[i] bit for bit.  The order-free form dO . (v_j - ctx_i) needs the 32 context rows in LDS,
+      // which the 1088-key score rows leave no room for.)
       float dp0 = 0.0f, dp1 = 0.0f, dp2 = 0.0f, dp3 = 0.0f;
 #pragma unroll
       for (int d = 0; d < kSmD; d += 4) {

@@ -134,6 +134,17 @@ __device__ __forceinline__ void score_row(const float* __restrict__ qkv, int64_t
   }
 }
 
+// Every key of query row i masked (a padded frame under the chunk masks): the additive -10000 is then a shift of the WHOLE row, which
+// the softmax does not see - but float32 rounds scores next to 10000 to a grid of 2^-10, and the row's probabilities came out up to
+// 5e-4 (relative) off.  Such a row is scored without the shift; its log-sum-exp carries it.  One wave per row: a wave vote.
+__device__ __forceinline__ bool row_all_masked(const float* __restrict__ mask, int mask_qk, int i, int64_t b, int T) {
+  if (!mask) return false;
+  const float* mrow = mask_qk ? mask + (b * T + i) * T : mask + b * T;
+  int seen = 0;
+  for (int j = threadIdx.x; j < T; j += 64) seen |= mrow[j] != 0.0f;
+  return __ballot(seen) == 0;
+}
+
 __global__ __launch_bounds__(64) void attn_fwd_x32_kernel(const float* __restrict__ qkv, int64_t ld, const float* __restrict__ pos,
                                                           int64_t ldp, const float* __restrict__ bu, const float* __restrict__ bv,
                                                           const float* __restrict__ mask, int mask_qk, int T, int D, float scale,
@@ -148,7 +159,8 @@ __global__ __launch_bounds__(64) void attn_fwd_x32_kernel(const float* __restric
   qu[lane] = q + bu[h * 64 + lane];
   qv[lane] = q + bv[h * 64 + lane];
   __syncthreads();
-  score_row(qkv, ld, pos, ldp, mask, mask_qk, i, b, T, h, D, qu, qv, scale, sc);
+  const bool shifted = row_all_masked(mask, mask_qk, i, b, T);
+  score_row(qkv, ld, pos, ldp, shifted ? nullptr : mask, mask_qk, i, b, T, h, D, qu, qv, scale, sc);
   __syncthreads();
   float m = -INFINITY;
   for (int j = lane; j < T; j += 64) m = fmaxf(m, sc[j]);
@@ -165,10 +177,14 @@ __global__ __launch_bounds__(64) void attn_fwd_x32_kernel(const float* __restric
   float o = 0.0f;
   for (int j = 0; j < T; ++j) o = fmaf(sc[j] * inv, qkv[(b * T + j) * ld + 2 * D + h * 64 + lane], o);
   ctx[(b * T + i) * ldc + h * 64 + lane] = o;
-  if (lane == 0) lse[((int64_t)b * gridDim.y + h) * T + i] = m + logf(s);
+  // (an all-masked row: the stored value is the reference's, shift included, and float32 drops the row's low bits next to 10000 -
+  // lse alone no longer rebuilds such a row's probabilities: attn_bwd_row_x32_kernel takes its log-sum-exp from the unshifted scores)
+  if (lane == 0) lse[((int64_t)b * gridDim.y + h) * T + i] = m + logf(s) + (shifted ? -10000.0f : 0.0f);
 }
 
 // Backward, per query row: P[i][:] and dS[i][:] = scale * P (dP - D) into the workspaces, dq_i, and nothing else.
+// dP_ij - D_i is taken as dctx_i . (v_j - ctx_i): one sum instead of the difference of two - where a row has ONE visible key
+// (ctx_i = v_j: an utterance of one frame, the first row of a causal mask) the gradient is exactly zero, not their rounding noise.
 __global__ __launch_bounds__(64) void attn_bwd_row_x32_kernel(const float* __restrict__ qkv, int64_t ld, const float* __restrict__ pos,
                                                               int64_t ldp, const float* __restrict__ bu,
                                                               const float* __restrict__ bv, const float* __restrict__ mask,
@@ -180,20 +196,29 @@ __global__ __launch_bounds__(64) void attn_bwd_row_x32_kernel(const float* __res
   float* qu = sm;
   float* qv = sm + 64;
   float* dc = sm + 128;
-  float* sc = sm + 192;
+  float* cx = sm + 192;
+  float* sc = sm + 256;
   const int i = blockIdx.x, h = blockIdx.y, lane = threadIdx.x;
   const int64_t b = blockIdx.z;
   const int H = gridDim.y;
   const float q = qkv[(b * T + i) * ld + h * 64 + lane];
   qu[lane] = q + bu[h * 64 + lane];
   qv[lane] = q + bv[h * 64 + lane];
-  const float dci = dctx[(b * T + i) * lddc + h * 64 + lane];
-  dc[lane] = dci;
-  const float Di = wave_sum(dci * ctx[(b * T + i) * ldc + h * 64 + lane]);
+  dc[lane] = dctx[(b * T + i) * lddc + h * 64 + lane];
+  cx[lane] = ctx[(b * T + i) * ldc + h * 64 + lane];
   __syncthreads();
-  score_row(qkv, ld, pos, ldp, mask, mask_qk, i, b, T, h, D, qu, qv, scale, sc);
+  const bool shifted = row_all_masked(mask, mask_qk, i, b, T);
+  score_row(qkv, ld, pos, ldp, shifted ? nullptr : mask, mask_qk, i, b, T, h, D, qu, qv, scale, sc);
   __syncthreads();
-  const float z = lse[((int64_t)b * H + h) * T + i];
+  float z = lse[((int64_t)b * H + h) * T + i];
+  if (shifted) {  // (the stored value carries the shift and lost the row's low bits to it: the log-sum-exp of the unshifted scores)
+    float m = -INFINITY;
+    for (int j = lane; j < T; j += 64) m = fmaxf(m, sc[j]);
+    m = wave_max(m);
+    float se = 0.0f;
+    for (int j = lane; j < T; j += 64) se += expf(sc[j] - m);
+    z = m + logf(wave_sum(se));
+  }
   float* Pr = P + (((int64_t)b * H + h) * T + i) * T;
   float* dSr = dS + (((int64_t)b * H + h) * T + i) * T;
   for (int j = lane; j < T; j += 64) {
@@ -201,8 +226,8 @@ __global__ __launch_bounds__(64) void attn_bwd_row_x32_kernel(const float* __res
     const float* vr = qkv + (b * T + j) * ld + 2 * D + h * 64;
     float dp = 0.0f;
 #pragma unroll 8
-    for (int d = 0; d < 64; ++d) dp = fmaf(dc[d], vr[d], dp);
-    const float ds = pj * (dp - Di) * scale;
+    for (int d = 0; d < 64; ++d) dp = fmaf(dc[d], vr[d] - cx[d], dp);
+    const float ds = pj * dp * scale;
     Pr[j] = pj;
     dSr[j] = ds;
     sc[j] = ds;
@@ -370,7 +395,7 @@ static int attention_bwd_x32(const float* qkv, int64_t ld_qkv, const float* pos,
   float* cs = dS + batch * heads * T * T;
   hipStream_t s = (hipStream_t)stream;
   const dim3 grid((unsigned)T, (unsigned)heads, (unsigned)batch);
-  MA_LAUNCH(attn_bwd_row_x32_kernel, grid, dim3(64), (size_t)(192 + T) * 4, s, qkv, ld_qkv, pos, ld_pos, bias_u, bias_v, mask,
+  MA_LAUNCH(attn_bwd_row_x32_kernel, grid, dim3(64), (size_t)(256 + T) * 4, s, qkv, ld_qkv, pos, ld_pos, bias_u, bias_v, mask,
             mask_qk, (int)T, D, scale, ctx, ld_ctx, dctx, ld_dctx, lse, P, dS, dqkv, ld_dqkv);
   MA_LAUNCH(attn_bwd_col_x32_kernel, grid, dim3(64), 0, s, qkv, ld_qkv, bias_u, (int)T, D, dctx, ld_dctx, P, dS, cs, dqkv,
             ld_dqkv);

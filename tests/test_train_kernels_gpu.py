@@ -1,11 +1,53 @@
 """GPU parity of the training-step kernels (mindaudio_amd/csrc/train_kernels.hip) against float32 PyTorch-CPU
-restatements of the same formulas (autograd of the oracle's layer definitions)."""
+restatements of the same formulas (autograd of the oracle's layer definitions).
+
+The attention backward kernels are also checked ROW BY ROW (test_attention_backward_rows, test_decoder_attention_backward_rows; inputs,
+float64 references and the rounded models in tests/attention_cases.py): worst row error ||got_i - ref_i|| / max(||ref_i||, floor)
+against float64 autograd, measured on an MI355X, as  bf16 kernel / rounded reference / float32 kernel.  The bf16 kernel must stay within
+4 x the rounded reference, the float32 kernel within 2e-5.
+
+  b3 t1 h4 pad          dq 1.52e-4 / 2.30e-4 / 0   dk 1.55e-4 / 2.25e-4 / 0   dv 0 / 0 / 0
+                        dpos 2.03e-4 / 2.43e-4 / 0   du 1.82e-4 / 2.24e-4 / 0   dbv 1.20e-4 / 1.00e-4 / 0
+  b3 t1 h4 chunk        dq 7.81e-5 / 5.25e-5 / 0   dk 6.86e-5 / 5.24e-5 / 0   dv 0 / 0 / 0
+                        dpos 8.65e-5 / 5.75e-5 / 0   du 8.39e-5 / 5.04e-5 / 0   dbv 4.67e-5 / 2.56e-5 / 0
+  b3 t17 h4 pad         dq 7.40e-3 / 8.01e-3 / 1.06e-6   dk 8.23e-3 / 7.75e-3 / 7.17e-7   dv 5.04e-3 / 5.04e-3 / 6.71e-7
+                        dpos 7.85e-3 / 7.62e-3 / 7.51e-7   du 3.78e-3 / 3.85e-3 / 5.48e-7   dbv 3.44e-3 / 3.58e-3 / 5.37e-7
+  b3 t17 h4 chunk       dq 8.84e-3 / 9.20e-3 / 1.21e-6   dk 1.11e-2 / 1.17e-2 / 1.12e-6   dv 5.25e-3 / 5.25e-3 / 1.10e-6
+                        dpos 1.10e-2 / 1.16e-2 / 1.11e-6   du 5.34e-3 / 5.97e-3 / 6.79e-7   dbv 5.66e-3 / 6.16e-3 / 6.70e-7
+  b3 t65 h4 pad         dq 3.03e-2 / 2.96e-2 / 2.06e-6   dk 7.88e-3 / 7.63e-3 / 1.66e-6   dv 7.40e-3 / 7.40e-3 / 1.34e-6
+                        dpos 6.95e-3 / 6.48e-3 / 1.73e-6   du 3.88e-3 / 3.67e-3 / 6.65e-7   dbv 4.06e-3 / 3.64e-3 / 6.78e-7
+  b3 t65 h4 chunk       dq 1.73e-2 / 1.37e-2 / 1.67e-6   dk 1.90e-2 / 2.85e-2 / 2.16e-6   dv 9.00e-3 / 8.30e-3 / 1.59e-6
+                        dpos 8.77e-3 / 7.73e-3 / 1.48e-6   du 3.83e-3 / 3.81e-3 / 6.80e-7   dbv 4.14e-3 / 4.05e-3 / 6.83e-7
+  b3 t97 h4 pad         dq 1.27e-2 / 1.04e-2 / 1.93e-6   dk 1.34e-2 / 1.11e-2 / 1.88e-6   dv 7.73e-3 / 7.73e-3 / 1.66e-6
+                        dpos 7.03e-3 / 6.72e-3 / 2.04e-6   du 3.90e-3 / 3.84e-3 / 9.03e-7   dbv 4.03e-3 / 4.03e-3 / 7.92e-7
+  b3 t97 h4 chunk       dq 1.85e-2 / 1.88e-2 / 2.82e-6   dk 1.36e-2 / 1.06e-2 / 1.86e-6   dv 8.74e-3 / 8.77e-3 / 1.97e-6
+                        dpos 7.50e-3 / 6.85e-3 / 1.22e-6   du 3.95e-3 / 3.81e-3 / 6.83e-7   dbv 3.73e-3 / 3.65e-3 / 7.44e-7
+  b2 t129 h4 pad        dq 2.31e-2 / 2.31e-2 / 2.00e-6   dk 8.74e-3 / 8.68e-3 / 1.63e-6   dv 7.52e-3 / 7.52e-3 / 1.85e-6
+                        dpos 8.96e-3 / 8.90e-3 / 1.68e-6   du 3.94e-3 / 3.83e-3 / 8.68e-7   dbv 3.84e-3 / 3.83e-3 / 9.15e-7
+  b2 t129 h4 chunk      dq 3.77e-2 / 4.22e-2 / 3.13e-6   dk 5.57e-2 / 5.93e-2 / 2.43e-6   dv 1.12e-2 / 1.12e-2 / 2.81e-6
+                        dpos 7.91e-3 / 8.07e-3 / 1.12e-6   du 4.03e-3 / 4.01e-3 / 6.57e-7   dbv 3.90e-3 / 3.97e-3 / 6.82e-7
+  b2 t65 h8 pad         dq 9.65e-3 / 9.89e-3 / 1.23e-6   dk 6.87e-3 / 7.61e-3 / 1.34e-6   dv 5.90e-3 / 5.90e-3 / 1.11e-6
+                        dpos 7.01e-3 / 7.40e-3 / 1.20e-6   du 4.23e-3 / 4.17e-3 / 7.38e-7   dbv 4.18e-3 / 4.29e-3 / 7.04e-7
+  b2 t65 h8 chunk       dq 1.01e-2 / 9.62e-3 / 1.45e-6   dk 2.22e-2 / 2.03e-2 / 1.43e-6   dv 7.64e-3 / 7.60e-3 / 1.37e-6
+                        dpos 6.52e-3 / 6.69e-3 / 1.30e-6   du 4.58e-3 / 4.42e-3 / 6.05e-7   dbv 4.43e-3 / 4.45e-3 / 6.51e-7
+  lq1 lk1 mode0         dq 6.36e-5 / 6.36e-5 / 0   dk 7.26e-6 / 7.14e-6 / 0   dv 0 / 0 / 0
+  lq33 lk320 mode1      dq 3.40e-3 / 3.40e-3 / 4.43e-7   dk 3.97e-3 / 3.73e-3 / 2.95e-7   dv 4.39e-3 / 3.47e-3 / 2.67e-7
+  lq65 lk321 mode1      dq 1.93e-3 / 1.93e-3 / 4.47e-7   dk 3.40e-3 / 1.95e-3 / 3.13e-7   dv 4.28e-3 / 1.95e-3 / 2.45e-7
+  lq64 lk64 mode2       dq 7.25e-3 / 7.25e-3 / 2.90e-7   dk 5.25e-3 / 5.04e-3 / 2.23e-7   dv 3.38e-3 / 3.38e-3 / 1.88e-7
+  lq97 lk97 mode2       dq 6.26e-3 / 6.26e-3 / 3.76e-7   dk 4.94e-3 / 3.93e-3 / 3.18e-7   dv 4.77e-3 / 3.56e-3 / 1.95e-7
+"""
 import math
+import os
+import sys
 
 import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
+import attention_cases as AC  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -1022,3 +1064,83 @@ def test_input_gradient_product_with_layernorm_backward_epilogue(K, m, k):
             diff = (a_ - b_).abs()
             assert float((diff / b_.abs().clamp(min=1e-3)).max()) <= 1.0 / 64  # one bf16 ulp (2^-7 relative at most)
             assert float((diff > 0).float().mean()) < 5e-3
+
+
+# ---- per-row gradient checks of the attention kernels (tests/attention_cases.py) ----------------------------------------------------
+def _rows_of(t, name):
+    return t.reshape(1, -1) if name in ("du", "dbv") else t
+
+
+def _check_rows(tag, got, got32, ref, model, names, where):
+    """Every gradient, row by row (du / dv as one row each), against float64 autograd: the bf16 kernel's worst row within
+    GRAD_FACTOR x the rounded reference's worst row, the float32 kernel's within X32_ROW_TOL.  Prints the figures, then asserts."""
+    GRAD_FACTOR, X32_ROW_TOL, worst = AC.GRAD_FACTOR, AC.X32_ROW_TOL, AC.worst
+    bad = []
+    for name in names:
+        r = _rows_of(ref[name], name)
+        e_k, at = worst(_rows_of(got[name], name), r)
+        e_m, _ = worst(_rows_of(model[name], name), r)
+        e_x, at_x = worst(_rows_of(got32[name], name), r)
+        print("ROWS %s %-4s kernel %.2e (row %d = %s, |ref row| %.2e)  model %.2e  x32 %.2e (row %d)"
+              % (tag, name, e_k, at, where(name, at), float(r[at].norm()), e_m, e_x, at_x))
+        if not e_k <= GRAD_FACTOR * e_m:
+            bad.append("%s: bf16 worst row %d (%s) %.3e > %g x model %.3e" % (name, at, where(name, at), e_k, GRAD_FACTOR, e_m))
+        if not e_x <= X32_ROW_TOL:
+            bad.append("%s: x32 worst row %d (%s) %.3e > %g" % (name, at_x, where(name, at_x), e_x, X32_ROW_TOL))
+    assert not bad, "%s: %s" % (tag, "; ".join(bad))
+
+
+@pytest.mark.parametrize("chunked", [False, True])
+@pytest.mark.parametrize("b,t,h", AC.RELPOS_GRAD_SHAPES)
+def test_attention_backward_rows(K, b, t, h, chunked):
+    """ma_relpos_attention_bwd_bf16 / _x32 and their (B, T, T)-mask forms, per ROW: lens = [t, t - 37, 1] (a one-frame utterance next
+    to a full one), q / k / v scaled so that a row has a few effective keys - one wrong key moves its row by O(1) - and dpos, du, dv
+    preset (the kernels add to them).  The measured figures are in the module docstring.
+    """
+    from mindaudio_amd.train import kernels_x32 as X
+
+    inp = AC.relpos_grad_inputs(b, t, h, chunked)
+    ref, model = AC.relpos_float64(inp), AC.rounded_reference_relpos(inp)
+    dm = h * 64
+    qkv, pos, u, v, mask, dctx = (inp[n].cuda() for n in ("qkv", "pos", "u", "v", "mask", "dctx"))
+
+    def run(fwd, bwd, cast):
+        ctx, lse = fwd(cast(qkv), cast(pos), u, v, mask, b, t, heads=h)
+        dpos, du, dv = inp["dpos0"].clone().cuda(), inp["du0"].clone().cuda(), inp["dv0"].clone().cuda()
+        dqkv = bwd(cast(qkv), cast(pos), u, v, mask, ctx, cast(dctx), lse, b, t, dpos, du, dv, heads=h)
+        sub = lambda buf, name: buf.double().cpu() - inp[name].double()  # noqa: E731  (what the kernel added)
+        return dict(dq=dqkv[:, :dm], dk=dqkv[:, dm:2 * dm], dv=dqkv[:, 2 * dm:], dpos=sub(dpos, "dpos0"), du=sub(du, "du0"),
+                    dbv=sub(dv, "dv0"))
+
+    got = run(K.attention_fwd, K.attention_bwd, lambda x: x)
+    got32 = run(X.attention_fwd, X.attention_bwd, lambda x: x.float())
+    lens = inp["lens"].tolist()
+    where = lambda name, r: ("t %d" % r if name == "dpos" else "-" if name in ("du", "dbv")  # noqa: E731
+                             else "utterance %d of length %d, t %d" % (r // t, lens[r // t], r % t))
+    _check_rows("relpos b%d t%d h%d %s" % (b, t, h, "chunk" if chunked else "pad"), got, got32, ref, model,
+                ("dq", "dk", "dv", "dpos", "du", "dbv"), where)
+
+
+@pytest.mark.parametrize("lq,lk,mode", AC.DECODER_GRAD_SHAPES)
+def test_decoder_attention_backward_rows(K, lq, lk, mode):
+    """ma_mha_small_bwd_bf16 / _x32 per ROW, the keys scaled by 8 (a few effective keys per row): one query and one key; the last
+    key count of the LDS-staged matrix-core form (320) and the first beyond it (321), with two and three query tiles; 64 = two full
+    tiles and 97 under the label mask.  The measured figures are in the module docstring.
+    """
+    from mindaudio_amd.train import kernels_x32 as X
+
+    inp = AC.decoder_grad_inputs(lq, lk, mode)
+    ref, model = AC.decoder_float64(inp), AC.rounded_reference_decoder(inp)
+    b, h, scale = inp["b"], inp["heads"], inp["scale"]
+    q, k, v, dctx = (inp[n].cuda() for n in ("q", "k", "v", "dctx"))
+    mask = inp["mask"].cuda() if inp["mask"] is not None else None
+
+    def run(mod, cast):
+        ctx, probs = mod.mha_small_fwd(cast(q), cast(k), cast(v), mask, mode, b, lq, lk, scale, h, 64)
+        dq, dk_, dv = (torch.empty_like(cast(x)) for x in (q, k, v))
+        mod.mha_small_bwd(cast(q), cast(k), cast(v), probs, ctx, cast(dctx), b, lq, lk, scale, dq, dk_, dv, h, 64)
+        return dict(dq=dq, dk=dk_, dv=dv)
+
+    got, got32 = run(K, lambda x: x), run(X, lambda x: x.float())
+    where = lambda name, r: "batch %d, %s %d" % ((r // lq, "query", r % lq) if name == "dq" else (r // lk, "key", r % lk))  # noqa: E731
+    _check_rows("decoder lq%d lk%d mode%d" % (lq, lk, mode), got, got32, ref, model, ("dq", "dk", "dv"), where)
