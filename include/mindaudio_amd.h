@@ -1302,6 +1302,54 @@ int ma_aam_margin_f32(const float* cosine, const float* targets, int64_t n, floa
 int ma_phase_vocoder_f32(const float* spec, int32_t in_layout, int64_t B, int64_t frames, int32_t n_freq, const int32_t* step_index,
                          const double* step_alpha, int64_t T_out, int32_t hop, float* out, ma_stream_t stream);
 
+/* ---- IIR filters (mindaudio/data/filters.py: cal_filter_by_coffs :79-122 behind low_pass_filter and peaking_equalizer; filtfilt
+ * :342-370 = scipy.signal.butter + scipy.signal.filtfilt) --------------------------------------------------------------------------
+ * x, y: (rows, T) contiguous device samples, float32 (sample_bytes 4) or float64 (sample_bytes 8); y may be x.  Every row is
+ * filtered by the order-n recursion in the transposed direct form II of scipy.signal.lfilter, n = filter->order, 1 <= n <= 16:
+ *   y[t] = b[0] x[t] + z_0,   z_i = b[i+1] x[t] + z_(i+1) - a[i+1] y[t]  (i < n, z_n = 0).
+ * Coefficients, state and arithmetic are float64 (fused multiply-adds); a sample is converted on the way in and rounded on the way
+ * out.  ma_iir_filter_t lives in HOST memory, and so do the arrays it points to (they travel as kernel arguments):
+ *   b, a     n + 1 coefficients each, normalised: a[0] == 1
+ *   zi       n initial state values or NULL (zero state); zi_mode says how they are used: MA_IIR_ZI_NONE (ignored), MA_IIR_ZI_AS_IS,
+ *            MA_IIR_ZI_TIMES_X0 (zi * the row's first sample in processing order: what scipy.signal.filtfilt does)
+ *   reverse  != 0: the row is walked from its last sample to its first and every result is written where its sample was read
+ *            (filtfilt's backward pass without flipped copies)
+ *   upper_clamp  != 0: min(y[t], 1.0) is what is stored; the recursion goes on from the unclamped y[t] (cal_filter_by_coffs)
+ *   chunk    L >= 1.  A row is cut into C = ceil(T / min(L, T)) chunks, one thread each: every chunk but the last runs from a zero
+ *            state, the final states s_c are carried in order, z_(c+1) = P z_c + s_c, and every chunk runs again from its true state.
+ *   power    P = A^L, n x n row-major, A[i][0] = -a[i+1], A[i][i+1] = 1: needed (and read) only when C > 1.  The caller decides
+ *            whether P is usable - poles strictly inside the unit circle and P finite; otherwise it passes chunk >= T and every row
+ *            is one sequential recursion (mindaudio_amd.data.filters.iir_plan).
+ *   steps    0: everything.  Otherwise a mask of MA_IIR_STEP_* - only those of the three launches run, for timing them one by one
+ *            (tools/iir_filter_bench.py); y or the workspace is then incomplete.  With C == 1 there is only MA_IIR_STEP_EMIT.
+ * workspace: ma_iir_filter_workspace_bytes(rows, T, n, chunk) bytes of device memory, 8-byte aligned (0 bytes when C == 1).
+ * No atomics; the order of every sum depends on T, L and n only: bit-identical from run to run and for a row alone or in a batch.
+ * MA_ERR_INVALID_ARG for a null x, y, filter, b or a, a null power when C > 1, rows, T, n or chunk < 1, a[0] != 1, an unknown
+ * zi_mode, steps or sample_bytes; MA_ERR_UNSUPPORTED for n > 16 or T >= 2^31 - 256; MA_ERR_WORKSPACE.  Nothing is launched on a refusal. */
+#define MA_IIR_MAX_ORDER 16
+#define MA_IIR_ZI_NONE 0
+#define MA_IIR_ZI_AS_IS 1
+#define MA_IIR_ZI_TIMES_X0 2
+#define MA_IIR_STEP_CHUNK_STATES 1
+#define MA_IIR_STEP_CARRY 2
+#define MA_IIR_STEP_EMIT 4
+typedef struct ma_iir_filter {
+  int32_t order;
+  int32_t zi_mode;
+  int32_t reverse;
+  int32_t upper_clamp;
+  int64_t chunk;
+  const double* b;
+  const double* a;
+  const double* zi;
+  const double* power;
+  int32_t steps;
+  int32_t reserved;
+} ma_iir_filter_t;
+int64_t ma_iir_filter_workspace_bytes(int64_t rows, int64_t T, int32_t order, int64_t chunk);
+int ma_iir_filter(const void* x, int32_t sample_bytes, int64_t rows, int64_t T, const ma_iir_filter_t* filter, void* y, void* workspace,
+                  int64_t workspace_bytes, ma_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

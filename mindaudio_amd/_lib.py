@@ -95,6 +95,14 @@ class PackItem(ctypes.Structure):
                 ("K", ctypes.c_int32), ("kind", ctypes.c_int32), ("first_block", ctypes.c_int32)]
 
 
+class IirFilter(ctypes.Structure):
+    """struct ma_iir_filter (include/mindaudio_amd.h); b, a, zi, power are HOST arrays of float64."""
+
+    _fields_ = [("order", ctypes.c_int32), ("zi_mode", ctypes.c_int32), ("reverse", ctypes.c_int32), ("upper_clamp", ctypes.c_int32),
+                ("chunk", ctypes.c_int64), ("b", ctypes.c_void_p), ("a", ctypes.c_void_p), ("zi", ctypes.c_void_p),
+                ("power", ctypes.c_void_p), ("steps", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
 class GemmEpilogue(ctypes.Structure):
     """struct ma_gemm_epilogue (include/mindaudio_amd.h)."""
 
@@ -372,8 +380,14 @@ PROTOTYPES = {
     "ma_aam_margin_f32": (ctypes.c_int, [vp, vp, i64, f32, f32, i32, vp, vp]),
     # ---- phase vocoder ----
     "ma_phase_vocoder_f32": (ctypes.c_int, [vp, i32, i64, i64, i32, vp, vp, i64, i32, vp, vp]),
+    # ---- IIR filters ----
+    "ma_iir_filter_workspace_bytes": (i64, [i64, i64, i32, i64]),
+    "ma_iir_filter": (ctypes.c_int, [vp, i32, i64, i64, ctypes.POINTER(IirFilter), vp, vp, i64, vp]),
 }
 
+IIR_MAX_ORDER = 16  # MA_IIR_MAX_ORDER
+IIR_ZI_NONE, IIR_ZI_AS_IS, IIR_ZI_TIMES_X0 = 0, 1, 2  # MA_IIR_ZI_*
+IIR_STEP_CHUNK_STATES, IIR_STEP_CARRY, IIR_STEP_EMIT = 1, 2, 4  # MA_IIR_STEP_*
 AUG_MIX_NOISE, AUG_MIX_BABBLE, AUG_MIX_UNIT_AVG, AUG_MIX_UNIT_PEAK, AUG_MIX_UNIT_RMS = 0, 1, 2, 3, 4  # MA_AUG_MIX_*
 
 _lib = None
