@@ -24,6 +24,7 @@
 #include "../../include/mindaudio_amd.h"
 
 #include "device_common.h"
+#include "gemm8.h"
 #include "launch.h"
 
 namespace ma {
@@ -41,6 +42,13 @@ struct DinParams {
   int32_t B, H, Wd, C, Ho, Wo;
   int32_t tiles_m[4];    // row tiles of class (ph, pw) = index 2 ph + pw
 };
+
+// ReLU'(act) on a bf16 pair: act is a ReLU output (>= 0, or -0 / NaN never); keep where the bf16 value is > 0
+__device__ __forceinline__ uint32_t relu_gate(uint32_t x, uint32_t aw) {
+  const uint32_t lo = (__uint_as_float(aw << 16) > 0.0f) ? 0x0000ffffu : 0u;
+  const uint32_t hi = (__uint_as_float(aw & 0xffff0000u) > 0.0f) ? 0xffff0000u : 0u;
+  return x & (lo | hi);
+}
 
 __global__ __launch_bounds__(kDiThreads, 2) void conv2_dinput_kernel(const DinParams p) {
   constexpr int FM = kDiBM / 32, FN = kDiBN / 32, GA = kDiBM / 32, GW = kDiBN / 32;
@@ -156,13 +164,7 @@ __global__ __launch_bounds__(kDiThreads, 2) void conv2_dinput_kernel(const DinPa
     uint4 v = *reinterpret_cast<const uint4*>(smem + r * kRow + cc * 16);
     if (p.act) {
       const uint4 a = *reinterpret_cast<const uint4*>(p.act + off);
-      // ReLU'(act): act is a ReLU output (>= 0, or -0 / NaN never); keep where the bf16 value is > 0
-      auto gate = [](uint32_t x, uint32_t aw) -> uint32_t {
-        const uint32_t lo = (__uint_as_float(aw << 16) > 0.0f) ? 0x0000ffffu : 0u;
-        const uint32_t hi = (__uint_as_float(aw & 0xffff0000u) > 0.0f) ? 0xffff0000u : 0u;
-        return x & (lo | hi);
-      };
-      v = make_uint4(gate(v.x, a.x), gate(v.y, a.y), gate(v.z, a.z), gate(v.w, a.w));
+      v = make_uint4(relu_gate(v.x, a.x), relu_gate(v.y, a.y), relu_gate(v.z, a.z), relu_gate(v.w, a.w));
     }
     *reinterpret_cast<uint4*>(p.out + off) = v;
   }
@@ -170,16 +172,15 @@ __global__ __launch_bounds__(kDiThreads, 2) void conv2_dinput_kernel(const DinPa
 
 MA_LDS_ATTR(conv2_dinput_kernel, kDiLds);
 
-// ---- round 4: the same product on 256 x 256 tiles, 8 waves, the 8-phase schedule of gemm_bf16_8ph_kernel (gemm_bf16.hip) ----------
+// ---- round 4: the same product on 256 x 256 tiles, 8 waves, the 8-phase schedule of gemm8.h (as gemm_bf16_8ph_kernel) ------------
 // C = 256 (the subsampling layer): a tile is 256 input positions of one parity class x all 256 channels.  128 flop per operand byte
 // instead of 64; one workgroup per CU (two 64 KiB K-tile buffers; the bf16 output tile is staged over them for the scatter).
 // Units of a K-tile buffer as in the GEMM kernel: A q0 | W q0 | W q1 | A q1, 128 rows x 128 bytes each, 16-byte chunks XOR-swizzled by
 // (row & 7) on the source side.  A unit q, unit row u <-> tile row (u >> 6) * 128 + 64 q + (u & 63) (a GATHERED dy row, or the zero row
 // when the tap falls outside the output grid); W unit q, unit row u <-> channel (u >> 5) * 64 + 32 q + (u & 31).
-constexpr int kD8Threads = 512, kD8Unit = 128 * 128, kD8Buf = 4 * kD8Unit;
 constexpr int kD8CRow = 256 * 2 + 16, kD8Lds = 256 * kD8CRow;  // 132 KiB: the staged output tile (>= the two 64 KiB buffers)
 
-__global__ __launch_bounds__(kD8Threads, 1) void conv2_dinput8_kernel(const DinParams p) {
+__global__ __launch_bounds__(k8Threads, 1) void conv2_dinput8_kernel(const DinParams p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -222,7 +223,7 @@ __global__ __launch_bounds__(kD8Threads, 1) void conv2_dinput8_kernel(const DinP
   // unit index U in a buffer: 0 = A q0, 1 = W q0, 2 = W q1, 3 = A q1
   auto stage = [&](auto uc, int kt, int buf) __attribute__((always_inline)) {
     constexpr int U = decltype(uc)::value;
-    char* dst = smem + buf * kD8Buf + U * kD8Unit + wid * 1024;
+    char* dst = smem + buf * k8Buf + U * k8Unit + wid * 1024;
     const int tap = kt / kt_per_tap, kin = (kt - tap * kt_per_tap) * 64;
     const int ih = tap / nkw, iw = tap - ih * nkw;
     if constexpr (U == 0 || U == 3) {
@@ -240,80 +241,12 @@ __global__ __launch_bounds__(kD8Threads, 1) void conv2_dinput8_kernel(const DinP
       __builtin_amdgcn_global_load_lds((gl_cvoid_t*)(w_src[q][1] + kw), (lds_void_t*)(dst + 8192), 16, 0, 0);
     }
   };
-  const int frow = lane & 15, fk = lane >> 4;
-  const int off_a = (wr * 64 + frow) * 128 + ((fk ^ (frow & 7)) << 4);
-  const int off_b = (wc * 32 + frow) * 128 + ((fk ^ (frow & 7)) << 4);
-  f32x4 acc[8][4];
-#pragma unroll
-  for (int i = 0; i < 8; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-  bf16x8 af[4][2], bfr[2][2];
-  auto load_a = [&](const char* unit) __attribute__((always_inline)) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int kk = 0; kk < 2; ++kk) af[i][kk] = *reinterpret_cast<const bf16x8*>(unit + ((off_a + i * 2048) ^ (kk << 6)));
-  };
-  auto load_b = [&](const char* unit) __attribute__((always_inline)) {
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int kk = 0; kk < 2; ++kk) bfr[j][kk] = *reinterpret_cast<const bf16x8*>(unit + ((off_b + j * 2048) ^ (kk << 6)));
-  };
-  auto mma = [&](auto ic, auto jc) __attribute__((always_inline)) {
-    constexpr int I = decltype(ic)::value, J = decltype(jc)::value;
-    __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-    for (int kk = 0; kk < 2; ++kk)
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-          acc[4 * I + i][2 * J + j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bfr[j][kk], af[i][kk], acc[4 * I + i][2 * J + j], 0, 0, 0);
-    __builtin_amdgcn_s_setprio(0);
-  };
-  using C0 = std::integral_constant<int, 0>;
-  using C1 = std::integral_constant<int, 1>;
-  using C2 = std::integral_constant<int, 2>;
-  using C3 = std::integral_constant<int, 3>;
+  MA_G8_NT_WAVE();
   const int nk = ntaps * kt_per_tap;
-  stage(C0{}, 0, 0);
-  stage(C1{}, 0, 0);
-  stage(C2{}, 0, 0);
-  stage(C3{}, 0, 0);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  if (wr == 1) __builtin_amdgcn_s_barrier();  // wave row 1 runs half a phase behind wave row 0
-#define D8_PHASE(MORE, READS, U, I, J)                                                \
-  {                                                                                   \
-    READS;                                                                            \
-    if constexpr (MORE) stage(U{}, kt + 1, nb);                                       \
-    __builtin_amdgcn_sched_barrier(0);                                                \
-    if constexpr (MORE) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");              \
-    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                             \
-    __builtin_amdgcn_s_barrier();                                                     \
-    __builtin_amdgcn_sched_barrier(0);                                                \
-    mma(I{}, J{});                                                                    \
-    __builtin_amdgcn_sched_barrier(0);                                                \
-    __builtin_amdgcn_s_barrier();                                                     \
-    __builtin_amdgcn_sched_barrier(0);                                                \
-  }
-#define D8_TILE(MORE)                                                                 \
-  {                                                                                   \
-    const char* cb = smem + (kt & 1) * kD8Buf;                                        \
-    const int nb = (kt + 1) & 1;                                                      \
-    D8_PHASE(MORE, load_a(cb); load_b(cb + kD8Unit), C0, C0, C0)                      \
-    D8_PHASE(MORE, load_b(cb + 2 * kD8Unit), C1, C0, C1)                              \
-    D8_PHASE(MORE, load_a(cb + 3 * kD8Unit), C2, C1, C1)                              \
-    D8_PHASE(MORE, load_b(cb + kD8Unit), C3, C1, C0)                                  \
-  }
-  int kt = 0;
-  for (; kt + 1 < nk; ++kt) D8_TILE(true)
-  D8_TILE(false)
-#undef D8_TILE
-#undef D8_PHASE
-  if (wr == 0) __builtin_amdgcn_s_barrier();  // (the barrier wave row 1 took at the start)
+  MA_G8_STAGE_FIRST();
+  g8_start(wr);
+  MA_G8_MAINLOOP(, , )
+  g8_finish(wr);
 
   // ---- epilogue: tile -> LDS (bf16, 528-byte rows), then whole 512-byte rows to their (b, h, w) positions with ReLU' -------------
   // 32 lanes per row (16 bytes each): thread (r0 = tid >> 5, cc = tid & 31) owns rows r0 + 16 k, k = 0 .. 15.  The ReLU' operand
@@ -354,12 +287,7 @@ __global__ __launch_bounds__(kD8Threads, 1) void conv2_dinput8_kernel(const DinP
     uint4 v = *reinterpret_cast<const uint4*>(smem + r * kD8CRow + cc * 16);
     if (p.act) {
       const uint4 a = av[k];
-      auto gate = [](uint32_t x, uint32_t aw) -> uint32_t {
-        const uint32_t lo = (__uint_as_float(aw << 16) > 0.0f) ? 0x0000ffffu : 0u;
-        const uint32_t hi = (__uint_as_float(aw & 0xffff0000u) > 0.0f) ? 0xffff0000u : 0u;
-        return x & (lo | hi);
-      };
-      v = make_uint4(gate(v.x, a.x), gate(v.y, a.y), gate(v.z, a.z), gate(v.w, a.w));
+      v = make_uint4(relu_gate(v.x, a.x), relu_gate(v.y, a.y), relu_gate(v.z, a.z), relu_gate(v.w, a.w));
     }
     *reinterpret_cast<uint4*>(p.out + off) = v;
   }
@@ -402,7 +330,7 @@ extern "C" int ma_conv2d_3x3s2_dinput_bf16(const void* dy, int64_t batch, int64_
     if (p.tiles_m[cls] > max_tiles) max_tiles = p.tiles_m[cls];
   }
   if (big) {
-    MA_LAUNCH(conv2_dinput8_kernel, dim3((unsigned)max_tiles, 4), dim3(kD8Threads), kD8Lds, (hipStream_t)stream, p);
+    MA_LAUNCH(conv2_dinput8_kernel, dim3((unsigned)max_tiles, 4), dim3(k8Threads), kD8Lds, (hipStream_t)stream, p);
     return MA_OK;
   }
   MA_LAUNCH(conv2_dinput_kernel, dim3((unsigned)(max_tiles * (C / kDiBN)), 4), dim3(kDiThreads), kDiLds, (hipStream_t)stream, p);

@@ -138,6 +138,17 @@ __device__ __forceinline__ int div_small(int m, int d, float inv) {  // floor(m 
 // (v_rcp_f32 instead of an IEEE division: 1 ulp, invisible after the bf16 rounding of every consumer)
 __device__ __forceinline__ float sigmoid_fast(float v) { return __builtin_amdgcn_rcpf(1.0f + __expf(-v)); }
 
+
+// XCD-aware bijective tile order: consecutive workgroup ids go to different XCDs (bid % 8); each XCD gets a contiguous run of the
+// ntiles tiles, so that tiles which share an operand panel find it in that XCD's L2.
+__device__ __forceinline__ int xcd_tile_order(int bid, int ntiles) {
+  const int q = ntiles / 8, r = ntiles % 8, xcd = bid % 8, idx = bid / 8;
+  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
+}
+// granule swizzle of a 256-byte LDS row (8 granules of 32 bytes): rows r = a + 4h + 8g (a < 4) of one transpose-read must hit
+// different banks
+__device__ __forceinline__ int swz_row256(int r) { return (r & 3) | (((r >> 3) & 1) << 2); }
+
 }  // namespace ma
 
 // Phase stamp of the kernels' timeline builds (each file's own -D...PROF): ts[k] = wall_clock64() (100 MHz) once the wave's scalar

@@ -721,18 +721,6 @@ __global__ __launch_bounds__(kThreads) void db_floor_kernel(float* out, int64_t 
 }
 
 // ---- host side ------------------------------------------------------------------------------
-static int g_num_cus = 0;
-static int num_cus() {
-  if (g_num_cus == 0) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess)
-      g_num_cus = prop.multiProcessorCount;
-    if (g_num_cus <= 0) g_num_cus = 256;
-  }
-  return g_num_cus;
-}
-
 static size_t feat_lds_bytes(int mode, int n_mels, int n_rows, int total_steps, int nw) {
   size_t b = (size_t)off_mel(nw);
   if (mode == kModeStft) return b;

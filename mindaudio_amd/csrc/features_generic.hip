@@ -225,9 +225,7 @@ static int launch_generic_mode(const FeatParams& p, const GenericGeom& g, hipStr
   constexpr size_t kDynLimit = 160 * 1024 - 1024;  // the kernel also holds a few hundred bytes of static LDS
   if (lds > kDynLimit) return MA_ERR_UNSUPPORTED;
   MA_LDS_ATTR_T(feat_generic_kernel<MODE>, kDynLimit);
-  int dev = 0, cus = 256;
-  hipDeviceProp_t prop;
-  if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) cus = prop.multiProcessorCount;
+  const int cus = num_cus();
   const int64_t tiles = (int64_t)(p.num_units / p.units_per_utt) * ((p.n_frames + kGTile - 1) / kGTile);
   int64_t grid = cus;  // one workgroup per CU: the DFT is MFMA-bound, a second workgroup would only share the pipes
   if (grid > tiles) grid = tiles;

@@ -21,6 +21,7 @@
 #include "../../include/mindaudio_amd.h"
 #include "train_common.h"
 
+#include "gemm8.h"
 #include "launch.h"
 
 namespace ma {
@@ -316,11 +317,7 @@ __global__ __launch_bounds__(kGemmThreads, (NST * (BM + BN) * BK * 2 > 80 * 1024
   const int tiles_n = (p.N + BN - 1) / BN;
   const int tiles_m = (p.M + BM - 1) / BM;
   const int ntiles = tiles_m * tiles_n;
-  int bid = blockIdx.x;
-  {
-    const int q = ntiles / 8, r = ntiles % 8, xcd = bid % 8, idx = bid / 8;
-    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-  }
+  const int bid = xcd_tile_order(blockIdx.x, ntiles);
   const int tile_m = bid / tiles_n, tile_n = bid % tiles_n;
   const int m0 = tile_m * BM, n0 = tile_n * BN;
 
@@ -423,22 +420,7 @@ __global__ __launch_bounds__(kGemmThreads, (NST * (BM + BN) * BK * 2 > 80 * 1024
   gemm_store_tile<FM, FN, BM, BN, EPI, kGemmThreads>(p, acc, m0, n0, wm * (BM / 2), wn * (BN / 2), smem, tid, lane);
 }
 
-// ---- 256 x 256 x 64 tile, 8 waves, "8-phase" schedule (cdna_hip_programming.md, the 256^2 8-phase template) -----------------
-// For GEMMs with enough 256 x 256 tiles to fill the chip (ECAPA's 1 x 1 convolutions: M = 76 800, N, K = 1024 .. 3072; the
-// training step's M = 10 240 layers).  The 128 x 128 kernel above is a lock-step structure (every wave: wait, barrier, fragments,
-// MFMAs) and stops at ~36 % of the MFMA peak.  Here:
-//   * 8 waves = 2 (M) x 4 (N), a wave owns 128 x 64 of the tile (32 accumulator tiles); the two wave rows run HALF A PHASE APART
-//     (one extra barrier for wave row 1 at the start, one for wave row 0 at the end), so while one wave of a SIMD runs its 16
-//     MFMAs the other one issues its LDS reads and its share of the next K-tile's loads;
-//   * a K-tile is four phases, one 64 x 32 quadrant of the wave's tile each: (A rows 0-63 | B cols 0-31), (same A | B 32-63),
-//     (A 64-127 | same B), (same A | B 0-31 again): 8 + 4, 4, 8, 4 fragment reads, 16 MFMAs per phase;
-//   * operands go HBM/L2 -> LDS by global_load_lds_dwordx4 in 16 KiB units of 128 rows (A: the rows of one quadrant row of both
-//     wave rows; B: the columns of one quadrant column of all four wave columns), one unit of the NEXT K-tile per phase, into the
-//     other of two 64 KiB buffers; one counted s_waitcnt vmcnt(4) per phase (two units = 4 loads of this wave stay in flight),
-//     never 0 inside the loop; a unit is read one phase after the wait + barrier that retire it and restaged >= 2 phases after
-//     its last read;
-//   * LDS rows of 128 bytes, 16-byte chunks XOR-swizzled by (row & 7) on the SOURCE address and on the read (as above).
-constexpr int k8Threads = 512, k8Unit = 128 * 128, k8Buf = 4 * k8Unit;  // units of a buffer: A q0 | B q0 | B q1 | A q1
+// ---- 256 x 256 x 64 tile, 8 waves, the "8-phase" schedule of gemm8.h (what it is and when it pays: the comment there) -----------------
 // Phase stamps for tools/gemm8_timeline.py (compiled in only with -DMA_G8_PROF): wave 0 of three workgroups keeps wall_clock64()
 // (100 MHz) values in SGPRs and writes them out at the end of the kernel.
 #ifdef MA_G8_PROF
@@ -459,11 +441,7 @@ __global__ __launch_bounds__(k8Threads, 1) void gemm_bf16_8ph_kernel(const GemmP
   const int wr = wid >> 2, wc = wid & 3;
   constexpr int BM = 256, BN = 256;
   const int tiles_n = (p.N + BN - 1) / BN, tiles_m = (p.M + BM - 1) / BM, ntiles = tiles_m * tiles_n;
-  int bid = blockIdx.x;
-  {  // XCD-aware bijective tile order (see above)
-    const int q = ntiles / 8, r = ntiles % 8, xcd = bid % 8, idx = bid / 8;
-    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-  }
+  const int bid = xcd_tile_order(blockIdx.x, ntiles);
   int tile_m = bid / tiles_n, tile_n = bid % tiles_n;
   if (p.blk_cols > 0) {
     // Blocked tile order (round 6).  An XCD's ~32 resident workgroups are consecutive tile indices; in row-major order with many
@@ -513,88 +491,15 @@ __global__ __launch_bounds__(k8Threads, 1) void gemm_bf16_8ph_kernel(const GemmP
     }
   };
 
-  // ---- fragment reads: lane (frow = lane & 15, fk = lane >> 4) reads unit row base + frow, logical chunk 4 kk + fk ---------------
-  const int frow = lane & 15, fk = lane >> 4;
-  const int off_a = (wr * 64 + frow) * 128 + ((fk ^ (frow & 7)) << 4);  // + i * 2048 (16 rows), kk = 1: ^ 64
-  const int off_b = (wc * 32 + frow) * 128 + ((fk ^ (frow & 7)) << 4);  // + j * 2048
-
-  f32x4 acc[8][4];
-#pragma unroll
-  for (int i = 0; i < 8; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-  bf16x8 af[4][2], bfr[2][2];  // [fragment][kk]
-
-  auto load_a = [&](const char* unit) __attribute__((always_inline)) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int kk = 0; kk < 2; ++kk) af[i][kk] = *reinterpret_cast<const bf16x8*>(unit + ((off_a + i * 2048) ^ (kk << 6)));
-  };
-  auto load_b = [&](const char* unit) __attribute__((always_inline)) {
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int kk = 0; kk < 2; ++kk) bfr[j][kk] = *reinterpret_cast<const bf16x8*>(unit + ((off_b + j * 2048) ^ (kk << 6)));
-  };
-  auto mma = [&](auto ic, auto jc) __attribute__((always_inline)) {  // quadrant (I, J): acc[4 I + i][2 J + j]
-    constexpr int I = decltype(ic)::value, J = decltype(jc)::value;
-    __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-    for (int kk = 0; kk < 2; ++kk)
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-          acc[4 * I + i][2 * J + j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bfr[j][kk], af[i][kk], acc[4 * I + i][2 * J + j], 0, 0, 0);
-    __builtin_amdgcn_s_setprio(0);
-  };
-  using C0 = std::integral_constant<int, 0>;
-  using C1 = std::integral_constant<int, 1>;
-  using C2 = std::integral_constant<int, 2>;
-  using C3 = std::integral_constant<int, 3>;
-
+  MA_G8_NT_WAVE();
   const int nk = p.K / BK;
-  stage(C0{}, 0, 0);
-  stage(C1{}, 0, 0);
-  stage(C2{}, 0, 0);
-  stage(C3{}, 0, 0);
+  MA_G8_STAGE_FIRST();
   G8_STAMP(1);  // first K-tile issued
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  G8_STAMP(2);  // ... landed
-  if (wr == 1) __builtin_amdgcn_s_barrier();  // wave row 1 runs half a phase behind wave row 0
-  // One phase: fragment reads of this quadrant, one unit of the next K-tile, the counted wait, barrier, 16 MFMAs, barrier.
-#define G8_PHASE(MORE, READS, U, I, J)                                                \
-  {                                                                                   \
-    READS;                                                                            \
-    if constexpr (MORE) stage(U{}, kt + 1, nb);                                       \
-    __builtin_amdgcn_sched_barrier(0);                                                \
-    if constexpr (MORE) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");              \
-    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                             \
-    __builtin_amdgcn_s_barrier();                                                     \
-    __builtin_amdgcn_sched_barrier(0);                                                \
-    mma(I{}, J{});                                                                    \
-    __builtin_amdgcn_sched_barrier(0);                                                \
-    __builtin_amdgcn_s_barrier();                                                     \
-    __builtin_amdgcn_sched_barrier(0);                                                \
-  }
-#define G8_TILE(MORE)                                                                 \
-  {                                                                                   \
-    const char* cb = smem + (kt & 1) * k8Buf;                                         \
-    const int nb = (kt + 1) & 1;                                                      \
-    G8_PHASE(MORE, load_a(cb); load_b(cb + k8Unit), C0, C0, C0)                       \
-    G8_PHASE(MORE, load_b(cb + 2 * k8Unit), C1, C0, C1)                               \
-    G8_PHASE(MORE, load_a(cb + 3 * k8Unit), C2, C1, C1)                               \
-    G8_PHASE(MORE, load_b(cb + k8Unit), C3, C1, C0)                                   \
-  }
-  int kt = 0;
-  for (; kt + 1 < nk; ++kt) G8_TILE(true)
-  G8_TILE(false)  // the last K-tile: nothing left to stage
-#undef G8_TILE
-#undef G8_PHASE
+  g8_start(wr);
+  G8_STAMP(2);  // ... landed (wave 0, whose stamps are kept, takes no skew barrier)
+  MA_G8_MAINLOOP(, , )
   G8_STAMP(3);  // main loop done
-  if (wr == 0) __builtin_amdgcn_s_barrier();  // (the barrier wave row 1 took at the start)
+  g8_finish(wr);
   gemm_store_tile<8, 4, BM, BN, EPI, k8Threads>(p, acc, m0, n0, wr * 128, wc * 64, smem, tid, lane);
 #ifdef MA_G8_PROF
   G8_STAMP(4);  // epilogue instructions issued
@@ -872,18 +777,6 @@ __global__ __launch_bounds__(256) void splitk_join_kernel(const float* __restric
   }
 }
 
-static int g_gemm_cus = 0;
-static int gemm_num_cus() {
-  if (g_gemm_cus == 0) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess)
-      g_gemm_cus = prop.multiProcessorCount;
-    if (g_gemm_cus <= 0) g_gemm_cus = 256;
-  }
-  return g_gemm_cus;
-}
-
 template <int BM, int BN, int NST, int IM2COL, int EPI>
 static int launch_gemm_tile(const GemmParams& p, hipStream_t stream) {
   constexpr int ring = NST * (BM + BN) * BK * 2, stage_c = BM * (BN * 2 + 16);  // K-tile ring / staged bf16 C tile
@@ -931,7 +824,7 @@ static int launch_gemm(const GemmParams& p, hipStream_t stream) {
     // K >= 1024 (with fewer K-tiles the 128 x 128 kernel's shorter prologue / epilogue wins: ECAPA's 512 -> 512 layers 2.49 vs 2.79 ms
     // per forward) and at most 1/8 of the column tiles' width outside the matrix (tools/gemm_bench.py, tools/ecapa_bench.py)
     const int64_t n_pad = (int64_t)((p.N + 255) / 256) * 256 - p.N;
-    if (p.K >= MA_G8_MIN_K && 8 * n_pad <= p.N && (MA_GEMM_FORCE == 2 || t256 >= (int64_t)(0.9 * gemm_num_cus())))
+    if (p.K >= MA_G8_MIN_K && 8 * n_pad <= p.N && (MA_GEMM_FORCE == 2 || t256 >= (int64_t)(0.9 * num_cus())))
       return launch_gemm_8ph<EPI>(p, stream);
   }
   if constexpr (MA_GEMM_FORCE == 3) return launch_gemm_tile<128, 128, 2, IM2COL, EPI>(p, stream);
@@ -949,9 +842,9 @@ static int launch_gemm(const GemmParams& p, hipStream_t stream) {
   // 64x128 tile prefers 3 workgroups/CU (2 stages) when there are enough tiles to fill them, else the 3-stage ring
   // (re-measured with the lean epilogue, tools/gemm_tiles.py: 76 800 x 512 x 512 64 vs 70 us on the 64-row tile; the 128 x 128 x 3-stage
   // choice for long K with one tile per CU went: 15 936 x 256 x 4864 49 vs 59 us, x 2048 25 vs 30 us on the 64-row tile with 2 stages)
-  if (big >= 2 * gemm_num_cus() && p.K >= 512) return launch_gemm_tile<128, 128, 2, IM2COL, EPI>(p, stream);
+  if (big >= 2 * num_cus() && p.K >= 512) return launch_gemm_tile<128, 128, 2, IM2COL, EPI>(p, stream);
   const int64_t small = (int64_t)((p.M + 63) / 64) * ((p.N + 127) / 128);
-  if (small >= (int64_t)(1.9 * gemm_num_cus())) return launch_gemm_tile<64, 128, 2, IM2COL, EPI>(p, stream);
+  if (small >= (int64_t)(1.9 * num_cus())) return launch_gemm_tile<64, 128, 2, IM2COL, EPI>(p, stream);
   return launch_gemm_tile<64, 128, 3, IM2COL, EPI>(p, stream);
 }
 
@@ -1024,7 +917,7 @@ int ma_gemm_bf16(const void* A, int64_t lda, const void* W, int64_t ldw, void* o
   if (K == kWsK && (N % kWsCols) == 0 && N <= 1024 && M >= 16384 && p.out_bf16 && !p.residual && p.alpha == 1.0f && (ldo & 7) == 0 &&
       (reinterpret_cast<uintptr_t>(out) & 15) == 0 && (!p.bias || (reinterpret_cast<uintptr_t>(p.bias) & 15) == 0)) {
     const int ncb = (int)(N / kWsCols);
-    int grid = gemm_num_cus();
+    int grid = num_cus();
     grid -= grid % (8 * ncb);
     if (grid >= 8 * ncb) {
       if (p.row_scale) MA_LAUNCH(gemm_ws512_kernel<true>, dim3((unsigned)grid), dim3(kWsThreads), kWsLds, (hipStream_t)stream, p);
@@ -1066,7 +959,7 @@ static int splitk_plan(int64_t M, int64_t N, int64_t K, int* kt_split) {
   // about two workgroups per CU, at least 8 K-tiles (512 contraction elements) per split
   const int64_t tiles = ((M + 63) / 64) * ((N + 127) / 128);
   const int64_t nk = K / BK;
-  int64_t splits = (2 * gemm_num_cus() + tiles - 1) / tiles;
+  int64_t splits = (2 * num_cus() + tiles - 1) / tiles;
   if (splits > nk / 8) splits = nk / 8;
   if (splits < 1) splits = 1;
   *kt_split = (int)((nk + splits - 1) / splits);

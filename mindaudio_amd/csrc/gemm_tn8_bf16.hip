@@ -7,7 +7,7 @@
 // 2 x 128 x 128 x 64 flops = 64 flop/B, i.e. at the MFMA peak a CU would need 64 B/clk from L2 - the whole L2 -> CU path - and a
 // block's eight products are only 156 such tiles, so the contraction (M = batch x time = 10 200 rows) had to be split ~7 ways to
 // fill the chip: 421 TFLOP/s in the products plus a 45 us pass per block that re-reads and adds the partials (2.0 ms per step).
-// Here: 256 x 256 tiles (128 flop/B) on the 8-phase schedule of gemm_bf16_8ph_kernel, and the products of SIX blocks issued as one
+// Here: 256 x 256 tiles (128 flop/B) on the 8-phase schedule of gemm8.h (as gemm_bf16_8ph_kernel), and the products of SIX blocks issued as one
 // grid (39 tiles per block -> 234 workgroups, one per CU, every tile with the full contraction): no partials, no reduction pass,
 // the result is stored straight into the flat gradient.
 //
@@ -28,6 +28,7 @@
 #include "../../include/mindaudio_amd.h"
 #include "gemm_tn8.h"
 #include "device_common.h"
+#include "gemm8.h"
 #include "launch.h"
 
 namespace ma {
@@ -35,7 +36,8 @@ namespace ma {
 typedef short t8_v4s __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) t8_v4s t8_lds_v4s;
 
-constexpr int kT8Threads = 512, kT8BK = 64, kT8Unit = 64 * 256, kT8Buf = 4 * kT8Unit, kT8Lds = 2 * kT8Buf;
+constexpr int kT8BK = 64, kT8Lds = 2 * k8Buf;
+static_assert(k8Unit == 64 * 256, "a unit is 64 contraction rows of 256 bytes here");
 constexpr int kT8Max = 56;  // (56 x 64 B + 8 = 3 592 B of kernel arguments; 6 encoder blocks = 48 products + the decoder's 6 long ones)
 
 struct Tn8Item {  // 64 bytes: 48 of them travel in the kernel arguments
@@ -49,8 +51,6 @@ struct Tn8Group {
   Tn8Item it[kT8Max];
   int32_t n, total;
 };
-
-__device__ __forceinline__ int t8_f(int r) { return (r & 3) | (((r >> 3) & 1) << 2); }  // granule swizzle of a 256-byte LDS row
 
 // IM2COL: B is the im2col matrix of a 3x3 stride-2 valid convolution over an NHWC activation (batch, H, Wd, C), C % 256 == 0: row
 // m = (b, ho, wo), column (kh, kw, c) - the 256 columns of a tile are the channels [c0, c0 + 256) of ONE tap (kh, kw)
@@ -80,7 +80,7 @@ __device__ __forceinline__ void t8_tile(char* smem, const uint16_t* const A, con
   for (int ii = 0; ii < 2; ++ii) {
     const int r = 4 * (wid + 8 * ii) + (lane >> 4);
     srow[ii] = r;
-    const int sch = (((pch >> 1) ^ t8_f(r)) << 1) | (pch & 1);
+    const int sch = (((pch >> 1) ^ swz_row256(r)) << 1) | (pch & 1);
 #pragma unroll
     for (int q = 0; q < 2; ++q) {
       a_src[q][ii] = A + i0 + (sch >> 3) * 128 + 64 * q + (sch & 7) * 8;
@@ -109,10 +109,10 @@ __device__ __forceinline__ void t8_tile(char* smem, const uint16_t* const A, con
       }
     }
   };
-  // unit index U in a buffer: 0 = A q0, 1 = B q0, 2 = B q1, 3 = A q1 (the order in which a K-tile first needs them)
-  auto stage = [&](auto uc, int buf) __attribute__((always_inline)) {
+  // unit index U in a buffer: 0 = A q0, 1 = B q0, 2 = B q1, 3 = A q1; the K-tile is the one set_rows was last called for
+  auto stage = [&](auto uc, int, int buf) __attribute__((always_inline)) {
     constexpr int U = decltype(uc)::value;
-    char* dst = smem + buf * kT8Buf + U * kT8Unit + wid * 1024;
+    char* dst = smem + buf * k8Buf + U * k8Unit + wid * 1024;
     if constexpr (U == 0 || U == 3) {
       __builtin_amdgcn_global_load_lds((gl_cvoid_t*)(a_src[U == 3][0] + offa[0]), (lds_void_t*)dst, 16, 0, 0);
       __builtin_amdgcn_global_load_lds((gl_cvoid_t*)(a_src[U == 3][1] + offa[1]), (lds_void_t*)(dst + 8192), 16, 0, 0);
@@ -126,7 +126,7 @@ __device__ __forceinline__ void t8_tile(char* smem, const uint16_t* const A, con
   // read, + 32 for the second k-half), bytes lb * 8 of the fragment's 32-byte granule; it receives contraction rows lg * 8 .. + 7 of
   // tile column (lane & 15) of the granule - the MFMA operand layout
   const int lg = lane >> 4, la = (lane & 15) >> 2, lb = lane & 3;
-  const int r_frag = lg * 8 + la, fsw = t8_f(r_frag);
+  const int r_frag = lg * 8 + la, fsw = swz_row256(r_frag);
   int off_a[4], off_b[2];
 #pragma unroll
   for (int i = 0; i < 4; ++i) off_a[i] = r_frag * 256 + (((wr * 4 + i) ^ fsw) << 5) + lb * 8;
@@ -166,9 +166,8 @@ __device__ __forceinline__ void t8_tile(char* smem, const uint16_t* const A, con
   };
   const uint4 ones_pk = make_uint4(0x3f803f80u, 0x3f803f80u, 0x3f803f80u, 0x3f803f80u);  // bf16 1.0 x 8
   const bf16x8 ones = __builtin_bit_cast(bf16x8, ones_pk);
-  int kt = 0;
   // zero the contraction rows past Kc in the A fragments of the last K-tile (element e of a lane = row base + e)
-  auto mask_tail = [&]() __attribute__((always_inline)) {
+  auto mask_tail = [&](int kt) __attribute__((always_inline)) {
     if ((kt_lo + kt + 1) * kT8BK > Kc) {
 #pragma unroll
       for (int kk = 0; kk < 2; ++kk) {
@@ -211,50 +210,11 @@ __device__ __forceinline__ void t8_tile(char* smem, const uint16_t* const A, con
       }
     }
   };
-  using C0 = std::integral_constant<int, 0>;
-  using C1 = std::integral_constant<int, 1>;
-  using C2 = std::integral_constant<int, 2>;
-  using C3 = std::integral_constant<int, 3>;
-
   set_rows(0);
-  stage(C0{}, 0);
-  stage(C1{}, 0);
-  stage(C2{}, 0);
-  stage(C3{}, 0);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  if (wr == 1) __builtin_amdgcn_s_barrier();  // wave row 1 runs half a phase behind wave row 0
-  // One phase: fragment reads of this quadrant, one unit of the next K-tile, the counted wait, barrier, 16 MFMAs, barrier.
-#define T8_PHASE(MORE, READS, U, I, J, EXTRA)                                         \
-  {                                                                                   \
-    READS;                                                                            \
-    if constexpr (MORE) stage(U{}, nb);                                               \
-    __builtin_amdgcn_sched_barrier(0);                                                \
-    if constexpr (MORE) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");              \
-    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                             \
-    __builtin_amdgcn_s_barrier();                                                     \
-    __builtin_amdgcn_sched_barrier(0);                                                \
-    EXTRA;                                                                            \
-    mma(I{}, J{});                                                                    \
-    __builtin_amdgcn_sched_barrier(0);                                                \
-    __builtin_amdgcn_s_barrier();                                                     \
-    __builtin_amdgcn_sched_barrier(0);                                                \
-  }
-#define T8_TILE(MORE)                                                                             \
-  {                                                                                               \
-    const char* cb = smem + (kt & 1) * kT8Buf;                                                    \
-    const int nb = (kt + 1) & 1;                                                                  \
-    if constexpr (MORE) set_rows(kt + 1);                                                         \
-    T8_PHASE(MORE, load_a(cb); load_b(cb + kT8Unit), C0, C0, C0, mask_tail(); colsum_mma(C0{}))   \
-    T8_PHASE(MORE, load_b(cb + 2 * kT8Unit), C1, C0, C1, )                                        \
-    T8_PHASE(MORE, load_a(cb + 3 * kT8Unit), C2, C1, C1, mask_tail(); colsum_mma(C1{}))           \
-    T8_PHASE(MORE, load_b(cb + kT8Unit), C3, C1, C0, )                                            \
-  }
-  for (; kt + 1 < nk; ++kt) T8_TILE(true)
-  T8_TILE(false)  // the last K-tile: nothing left to stage
-#undef T8_TILE
-#undef T8_PHASE
-  if (wr == 0) __builtin_amdgcn_s_barrier();  // (the barrier wave row 1 took at the start)
+  MA_G8_STAGE_FIRST();
+  g8_start(wr);
+  MA_G8_MAINLOOP(set_rows(kt + 1), mask_tail(kt); colsum_mma(C0{}), mask_tail(kt); colsum_mma(C1{}))
+  g8_finish(wr);
 
   // ---- epilogue: lane holds out[row .. + (lane & 15)][column .. + (lane >> 4) * 4 + 0..3]: 16-byte stores, 64 bytes per row ------
   const int ei = lane & 15, ej = (lane >> 4) * 4;
@@ -272,13 +232,9 @@ __device__ __forceinline__ void t8_tile(char* smem, const uint16_t* const A, con
   }
 }
 
-__global__ __launch_bounds__(kT8Threads, 1) void gemm_tn8_group_kernel(const Tn8Group g) {
+__global__ __launch_bounds__(k8Threads, 1) void gemm_tn8_group_kernel(const Tn8Group g) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  int bid = blockIdx.x;
-  {  // XCD-aware bijective order: consecutive tiles (same product: shared operand panels) land on one XCD's L2
-    const int ntiles = g.total, q = ntiles / 8, r = ntiles % 8, xcd = bid % 8, idx = bid / 8;
-    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-  }
+  const int bid = xcd_tile_order(blockIdx.x, g.total);  // consecutive tiles (same product: shared operand panels) on one XCD's L2
   int item = 0;
   for (int k = 1; k < g.n; ++k)
     if (bid >= g.it[k].first) item = k;
@@ -300,7 +256,7 @@ struct Tn8ConvParams {
   int32_t ld_dy, Cout, No, Kc, kt_split, tiles_n;
   Tn8Conv cv;
 };
-__global__ __launch_bounds__(kT8Threads, 1) void gemm_tn8_conv_kernel(const Tn8ConvParams p) {
+__global__ __launch_bounds__(k8Threads, 1) void gemm_tn8_conv_kernel(const Tn8ConvParams p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int t = blockIdx.x, by = blockIdx.y;
   const int tile_m = t / p.tiles_n, tile_n = t - tile_m * p.tiles_n;
@@ -314,23 +270,12 @@ __global__ __launch_bounds__(kT8Threads, 1) void gemm_tn8_conv_kernel(const Tn8C
 MA_LDS_ATTR(gemm_tn8_group_kernel, kT8Lds);
 MA_LDS_ATTR(gemm_tn8_conv_kernel, kT8Lds);
 
-static int t8_cus() {
-  static int cus = 0;
-  if (cus == 0) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) cus = prop.multiProcessorCount;
-    if (cus <= 0) cus = 256;
-  }
-  return cus;
-}
-
 // one workgroup per CU (the kernel owns the CU's LDS): as many splits as keep tiles x splits inside one resident round, each with at
 // least 16 K-tiles
 static int t8_conv_plan(int64_t M, int64_t C, int64_t Cout, int* kt_split) {
   if ((C & 255) || (Cout & 255) || M < 1 || M >= (1 << 24)) return 0;
   const int64_t tiles = (Cout / 256) * (9 * C / 256), nk = (M + kT8BK - 1) / kT8BK;
-  int64_t splits = t8_cus() / tiles;
+  int64_t splits = num_cus() / tiles;
   if (splits > nk / 16) splits = nk / 16;
   if (splits < 1) splits = 1;
   *kt_split = (int)((nk + splits - 1) / splits);
@@ -361,7 +306,7 @@ int tn8_conv_launch(const void* dy, int64_t ld_dy, const void* act, int64_t batc
   p.cv.H = (int32_t)H; p.cv.Wd = (int32_t)Wd; p.cv.C = (int32_t)C; p.cv.Ho = (int32_t)Ho; p.cv.Wo = (int32_t)Wo;
   p.cv.inv_wo = 1.0f / (float)Wo;
   p.cv.inv_ho = 1.0f / (float)Ho;
-  MA_LAUNCH(gemm_tn8_conv_kernel, dim3((unsigned)((Cout / 256) * p.tiles_n), (unsigned)splits), dim3(kT8Threads), kT8Lds, stream, p);
+  MA_LAUNCH(gemm_tn8_conv_kernel, dim3((unsigned)((Cout / 256) * p.tiles_n), (unsigned)splits), dim3(k8Threads), kT8Lds, stream, p);
   return MA_OK;
 }
 
@@ -403,6 +348,6 @@ extern "C" int ma_gemm_tn_direct_group_bf16(const ma_tn_direct_item_t* items, in
   for (int k = n; k < kT8Max; ++k) g.it[k] = g.it[0];
   g.n = n;
   g.total = total;
-  MA_LAUNCH(gemm_tn8_group_kernel, dim3((unsigned)total), dim3(kT8Threads), kT8Lds, (hipStream_t)stream, g);
+  MA_LAUNCH(gemm_tn8_group_kernel, dim3((unsigned)total), dim3(k8Threads), kT8Lds, (hipStream_t)stream, g);
   return MA_OK;
 }

@@ -43,7 +43,7 @@ constexpr int kTnBK = 64, kTnStages = 3, kTnThreads = 256;
 // swizzle of the 32-byte granules of LDS row r: rows r = a + 4h + 8g (a < 4) of one tr-read must hit different banks
 template <int ROWB>
 __device__ __forceinline__ int tn_f(int r) {
-  if (ROWB == 256) return (r & 3) | (((r >> 3) & 1) << 2);  // 8 granules per row
+  if (ROWB == 256) return swz_row256(r);                     // 8 granules per row
   return ((r >> 1) & 1) | (((r >> 3) & 1) << 1);            // 128-byte rows: 4 granules, two rows per bank sweep
 }
 
@@ -365,17 +365,6 @@ __global__ __launch_bounds__(256) void tn_reduce_batch_kernel(const ma_reduce_it
   store4(i0, sum);
 }
 
-static int tn_cus() {
-  static int cus = 0;
-  if (cus == 0) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) cus = prop.multiProcessorCount;
-    if (cus <= 0) cus = 256;
-  }
-  return cus;
-}
-
 static int tn_plan(int64_t Mo, int64_t No, int64_t Kc, int* bm, int* kt_split) {
   // 128-row tiles when there are enough of them; about two workgroups per CU; >= 8 K-tiles per split
   const int64_t big = ((Mo + 127) / 128) * ((No + 127) / 128);
@@ -386,7 +375,7 @@ static int tn_plan(int64_t Mo, int64_t No, int64_t Kc, int* bm, int* kt_split) {
   // workgroups ran the conv2 weight gradient as a full round plus one of 64 (710 us; 7 splits: one round).  One workgroup per CU
   // (half the partial-sum traffic: the block's batched sum 41 -> 36 us) costs more in the products than it saves (FFN-size weight
   // gradients 25 -> 30 us, conv2 498 -> 940 us; step 12.7 -> 13.4 ms, round 3).
-  int64_t splits = (2 * tn_cus()) / tiles;
+  int64_t splits = (2 * num_cus()) / tiles;
   if (splits > nk / 8) splits = nk / 8;
   if (splits < 1) splits = 1;
   *kt_split = (int)((nk + splits - 1) / splits);

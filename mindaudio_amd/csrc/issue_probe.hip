@@ -82,10 +82,7 @@ __global__ __launch_bounds__(256, 1) void weight_stream_kernel(const char* __res
 
 extern "C" int ma_weight_stream_probe(const void* buf, int64_t bytes, int32_t rounds, float* sink, ma_stream_t stream) {
   if (!buf || !sink || bytes < 65536 || bytes > (1ll << 30) || (bytes & 4095) || rounds < 1) return MA_ERR_INVALID_ARG;
-  int dev = 0, cus = 256;
-  hipDeviceProp_t prop;
-  if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0)
-    cus = prop.multiProcessorCount;
+  const int cus = ma::num_cus();
   MA_LAUNCH(ma::weight_stream_kernel, dim3((unsigned)cus), dim3(256), 0, (hipStream_t)stream, reinterpret_cast<const char*>(buf),
             (uint32_t)bytes, (int)rounds, sink);
   return MA_OK;
@@ -93,10 +90,7 @@ extern "C" int ma_weight_stream_probe(const void* buf, int64_t bytes, int32_t ro
 
 extern "C" int ma_valu_issue_probe(int32_t wgs_per_cu, int32_t iters, float* sink, ma_stream_t stream) {
   if (wgs_per_cu < 1 || wgs_per_cu > 8 || iters < 1 || !sink) return MA_ERR_INVALID_ARG;
-  int dev = 0, cus = 256;
-  hipDeviceProp_t prop;
-  if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0)
-    cus = prop.multiProcessorCount;
+  const int cus = ma::num_cus();
   MA_LAUNCH(ma::valu_issue_kernel, dim3((unsigned)(cus * wgs_per_cu)), dim3(256), 0, (hipStream_t)stream, sink, (int)iters, 0.999f,
             0.001f);
   return MA_OK;

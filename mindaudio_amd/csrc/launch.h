@@ -22,6 +22,10 @@ struct LdsAttr {
 // MA_OK, or MA_ERR_LAUNCH if the runtime refused an attribute (sticky).
 int ensure_init();
 
+// Compute units of the current device (cached per device ordinal); 256 when the runtime cannot tell.  For launch plans only: every
+// caller sizes a grid or picks a split with it, none depends on it for correctness.
+int num_cus();
+
 // For kernels that are template instances chosen inside a template launcher: naming `LdsAttrOf<&kernel<...>, bytes>::reg` in the
 // launcher instantiates the static member, whose constructor runs when the library is loaded.
 template <auto Kernel, int Bytes>

@@ -1,5 +1,7 @@
 // ma_init(): everything the library has to tell the HIP runtime about its kernels, applied ONCE per process and device - the raised
-// dynamic-LDS limits that launch.h's MA_LDS_ATTR / MA_LDS_ATTR_T registrations collected while the library was loaded.
+// dynamic-LDS limits that launch.h's MA_LDS_ATTR / MA_LDS_ATTR_T registrations collected while the library was loaded.  Also the one
+// place that asks the runtime about the device (num_cus).
+#include <atomic>
 #include <mutex>
 
 #include "launch.h"
@@ -30,6 +32,27 @@ int ensure_init() {
     (void)hipGetLastError();
   });
   return g_status[dev];
+}
+
+int num_cus() {
+  static std::atomic<int> cached[kMaxDevices];  // 0 = not asked yet
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDevices) {
+    (void)hipGetLastError();
+    return 256;
+  }
+  int cus = cached[dev].load(std::memory_order_relaxed);
+  if (cus == 0) {
+    hipDeviceProp_t prop;
+    if (hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) {
+      cus = prop.multiProcessorCount;
+      cached[dev].store(cus, std::memory_order_relaxed);
+    } else {
+      (void)hipGetLastError();
+      cus = 256;
+    }
+  }
+  return cus;
 }
 
 }  // namespace ma

@@ -375,15 +375,7 @@ extern "C" int ma_gemm_rows_packed_f32(const void* A, int64_t lda, int64_t M, in
 
 // 48-row workgroups when the 64-row grid would fill less than 7/8 of the CUs and the 48-row grid still fits one round
 static bool rows_train_use48(int64_t M) {
-  int cus = 256;
-  {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    static int cached = 0;
-    if (!cached && hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0)
-      cached = prop.multiProcessorCount;
-    if (cached) cus = cached;
-  }
+  const int cus = num_cus();
   const int64_t g64 = (M + 63) / 64, g48 = (M + 47) / 48;
   return (g64 % cus) != 0 && (g64 % cus) * 8 < cus * 7 && (g48 + cus - 1) / cus == (g64 + cus - 1) / cus;
 }

@@ -104,6 +104,26 @@ def test_device_helpers_have_one_home():
             assert pattern not in src or (fn, pattern) in _PRIVATE_HELPER_COPIES, "%s: %r belongs in device_common.h" % (fn, pattern)
 
 
+def test_gemm8_schedule_and_launch_helpers_have_one_home():
+    """csrc/gemm8.h holds the one definition of the 8-phase 256 x 256 schedule, device_common.h the XCD tile order and ma_init.hip
+    the device query: no kernel file defines a phase macro of its own, writes the schedule's wait-and-two-barriers sequence
+    inside a macro, spells the tile order out or asks the runtime for the CU count."""
+    csrc = os.path.join(ROOT, "mindaudio_amd", "csrc")
+    files = {fn: open(os.path.join(csrc, fn)).read() for fn in sorted(os.listdir(csrc)) if fn.endswith((".hip", ".h", ".inc"))}
+    assert [fn for fn, src in files.items() if "multiProcessorCount" in src] == ["ma_init.hip"]
+    assert [fn for fn, src in files.items() if "xcd * (q + 1)" in src] == ["device_common.h"]
+    # a #define (with its continuation lines) that holds the counted wait followed by two barriers
+    macro = re.compile(r"^[ \t]*#[ \t]*define\b(?:[^\n]*\\\n)*[^\n]*", re.M)
+    phase = re.compile(r"s_waitcnt vmcnt\(4\)(?:[^\n]*\n){1,8}?[^\n]*s_barrier(?:[^\n]*\n){1,8}?[^\n]*s_barrier")
+    assert [fn for fn, src in files.items() if any(phase.search(m) for m in macro.findall(src))] == ["gemm8.h"]
+    for fn, src in files.items():
+        if fn.endswith(".hip"):
+            own = re.findall(r"^[ \t]*#[ \t]*define[ \t]+(\w+_PHASE)\b", src, flags=re.M)  # (ecapa_kernels.hip's ASP_TILE is no schedule)
+            assert not own, "%s defines %s: the 8-phase schedule lives in gemm8.h" % (fn, own)
+    for fn in ("gemm_bf16.hip", "conv2_dinput.hip", "gemm_tn8_bf16.hip"):
+        assert "MA_G8_MAINLOOP(" in files[fn] and '#include "gemm8.h"' in files[fn], fn
+
+
 def test_host_tables_match_oracle():
     """Host-built tables (window, mel banks) of the product vs the oracle's restatement."""
     import numpy as np
