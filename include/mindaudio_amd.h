@@ -1350,6 +1350,74 @@ int64_t ma_iir_filter_workspace_bytes(int64_t rows, int64_t T, int32_t order, in
 int ma_iir_filter(const void* x, int32_t sample_bytes, int64_t rows, int64_t T, const ma_iir_filter_t* filter, void* y, void* workspace,
                   int64_t workspace_bytes, ma_stream_t stream);
 
+/* ---- silence front end and reductions of mindaudio/data/processing.py (trim :263-319, split :322-377, normalize :28-95,
+ * stereo_to_mono :235-260) -------------------------------------------------------------------------------------------------------------
+ * Frames.  A row of n samples is zero-padded by frame_length / 2 on both sides and has
+ *   F(n) = (n + 2 (frame_length / 2) - frame_length) / hop_length + 1
+ * frames, which is n / hop_length + 1 for an even frame_length and (n - 1) / hop_length + 1 for an odd one (the reference's frame()
+ * on the padded signal); frame f covers the padded positions [f hop_length, f hop_length + frame_length).
+ * ma_frame_power_frames: F(n) on the host, MA_ERR_INVALID_ARG for n, frame_length or hop_length < 1.
+ *
+ * ma_frame_power: x (B, T) float32 (sample_bytes 4) or float64 (8), row stride ldx >= T; lengths: B int32 on the device (clamped to
+ * [0, T]; a row of length 0 has no frames) or NULL (every row has T samples).  power (B, ldp) float64, ldp >= F(T):
+ *   power[b][f] = sqrt(mean(x^2))^2 for f < F(lengths[b]) - the mean in float64, then the reference's square root and square -
+ *   and 0 behind it; row_max[b] = the largest of them (0 for a row without frames).
+ * Where hop_length divides frame_length and the ratio is at most MA_FRAME_POWER_MAX_RATIO a frame is the sum, in index order, of its
+ * hop blocks' sums; otherwise a frame is summed directly.  A workgroup owns MA_FRAME_POWER_TILE frames.  No atomics, the order of
+ * every sum depends on frame_length and hop_length only: bit-identical from run to run and for a row alone or inside a batch.
+ *
+ * ma_silence_edges: power as above; ref_rows: B float64 reference values on the device (ma_frame_power's row_max) or NULL, then
+ * ref_scalar for every row.  In float64,
+ *   nonsilent[b][f] = 10 log10(max(power, 1e-10)) - 10 log10(max(1e-10, ref)) > -top_db   for f < F(lengths[b]), 0 behind it
+ * (nonsilent (B, ldp) uint8).  A boundary is an index i in [0, F] at which the flag changes, both ends counting as silent.
+ *   trim_index (B, 2) int32: first boundary * hop_length, last boundary * hop_length (NOT clipped to the length, as trim leaves it)
+ *   counts (B,) int32: intervals = boundaries / 2;  edges (B, ldp + 1) int32: min(boundary * hop_length, limit) in order, i.e.
+ *   (start, end) pairs, -1 behind them; limit = clip when clip >= 0, else the row's length (split clips with shape[-1]).
+ * A row without a non-silent frame has count 0 and trim_index (-1, -1).
+ *
+ * ma_axis_stats: x viewed as (outer, n, inner) contiguous, dtype MA_DTYPE_*; out (outer, inner) float64 = the statistic MA_AXIS_*
+ * of |x| over n, in float64: maximum, minimum (a NaN wins both), count of |x| > 0, sum, sum of squares, mean = sum / n, and the
+ * population standard deviation sqrt(sum (|x| - mean)^2 / n).  n is cut into 256 / min(64, pow2 >= inner) slices summed in index
+ * order and joined by a halving tree: the order depends on n and inner only.
+ *
+ * ma_axis_apply: out = (x - sub) / div element by element in float64, sub and div (outer, inner) float64 statistics broadcast
+ * over n, either of them NULL (left out; both NULL: MA_ERR_INVALID_ARG).  out has x's dtype (out_dtype == dtype: the float64
+ * result is rounded to float32, or truncated toward zero to an integer, as an assignment into np.empty_like does) or is float64
+ * (out_dtype == MA_DTYPE_F64).  out must not be x.
+ *
+ * ma_channel_mean: x (n, channels) channel last, float32 or float64 -> out (n,) of the same type: the channels added in that type
+ * in the order of NumPy's add.reduce - index order below 8 channels, ((0+1)+(2+3))+((4+5)+(6+7)) at 8 - then divided by the
+ * channel count, so that the result equals np.mean(x, axis=-1) bit for bit.  channels > MA_CHANNEL_MEAN_MAX: MA_ERR_UNSUPPORTED.
+ *
+ * All five: MA_ERR_INVALID_ARG for a null pointer, B, T, n, outer, inner, channels, frame_length or hop_length < 1, ldx < T,
+ * ldp < F(T), an unknown sample_bytes, dtype or stat; MA_ERR_UNSUPPORTED where a position would not fit int32.  Nothing is launched
+ * on a refusal. */
+#define MA_FRAME_POWER_TILE 16
+#define MA_FRAME_POWER_MAX_RATIO 32
+#define MA_CHANNEL_MEAN_MAX 8
+#define MA_DTYPE_F32 0
+#define MA_DTYPE_F64 1
+#define MA_DTYPE_I32 2
+#define MA_DTYPE_I64 3
+#define MA_AXIS_MAX 0
+#define MA_AXIS_MIN 1
+#define MA_AXIS_L0 2
+#define MA_AXIS_SUM 3
+#define MA_AXIS_SUMSQ 4
+#define MA_AXIS_MEAN 5
+#define MA_AXIS_STD 6
+int64_t ma_frame_power_frames(int64_t n, int32_t frame_length, int32_t hop_length);
+int ma_frame_power(const void* x, int32_t sample_bytes, int64_t B, int64_t T, int64_t ldx, const int32_t* lengths,
+                   int32_t frame_length, int32_t hop_length, double* power, int64_t ldp, double* row_max, ma_stream_t stream);
+int ma_silence_edges(const double* power, int64_t ldp, int64_t B, int64_t T, const int32_t* lengths, int32_t frame_length,
+                     int32_t hop_length, const double* ref_rows, double ref_scalar, double top_db, int64_t clip, uint8_t* nonsilent,
+                     int32_t* trim_index, int32_t* counts, int32_t* edges, ma_stream_t stream);
+int ma_axis_stats(const void* x, int32_t dtype, int64_t outer, int64_t n, int64_t inner, int32_t stat, double* out,
+                  ma_stream_t stream);
+int ma_axis_apply(const void* x, int32_t dtype, int64_t outer, int64_t n, int64_t inner, const double* sub, const double* div, void* out,
+                  int32_t out_dtype, ma_stream_t stream);
+int ma_channel_mean(const void* x, int32_t sample_bytes, int64_t n, int32_t channels, void* out, ma_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

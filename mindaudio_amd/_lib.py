@@ -383,7 +383,19 @@ PROTOTYPES = {
     # ---- IIR filters ----
     "ma_iir_filter_workspace_bytes": (i64, [i64, i64, i32, i64]),
     "ma_iir_filter": (ctypes.c_int, [vp, i32, i64, i64, ctypes.POINTER(IirFilter), vp, vp, i64, vp]),
+    # ---- silence front end, axis statistics, channel mean (data.processing) ----
+    "ma_frame_power_frames": (i64, [i64, i32, i32]),
+    "ma_frame_power": (ctypes.c_int, [vp, i32, i64, i64, i64, vp, i32, i32, vp, i64, vp, vp]),
+    "ma_silence_edges": (ctypes.c_int, [vp, i64, i64, i64, vp, i32, i32, vp, ctypes.c_double, ctypes.c_double, i64, vp, vp, vp, vp,
+                                        vp]),
+    "ma_axis_stats": (ctypes.c_int, [vp, i32, i64, i64, i64, i32, vp, vp]),
+    "ma_axis_apply": (ctypes.c_int, [vp, i32, i64, i64, i64, vp, vp, vp, i32, vp]),
+    "ma_channel_mean": (ctypes.c_int, [vp, i32, i64, i32, vp, vp]),
 }
+
+FRAME_POWER_TILE, FRAME_POWER_MAX_RATIO, CHANNEL_MEAN_MAX = 16, 32, 8  # MA_FRAME_POWER_TILE, MA_FRAME_POWER_MAX_RATIO, MA_CHANNEL_MEAN_MAX
+DTYPE_F32, DTYPE_F64, DTYPE_I32, DTYPE_I64 = 0, 1, 2, 3  # MA_DTYPE_*
+AXIS_MAX, AXIS_MIN, AXIS_L0, AXIS_SUM, AXIS_SUMSQ, AXIS_MEAN, AXIS_STD = range(7)  # MA_AXIS_*
 
 IIR_MAX_ORDER = 16  # MA_IIR_MAX_ORDER
 IIR_ZI_NONE, IIR_ZI_AS_IS, IIR_ZI_TIMES_X0 = 0, 1, 2  # MA_IIR_ZI_*
