@@ -1418,6 +1418,65 @@ int ma_axis_apply(const void* x, int32_t dtype, int64_t outer, int64_t n, int64_
                   int32_t out_dtype, ma_stream_t stream);
 int ma_channel_mean(const void* x, int32_t sample_bytes, int64_t n, int32_t channels, void* out, ma_stream_t stream);
 
+/* ---- harmonic / percussive separation of mindaudio/data/features.py (soft_mask :438-469, hpss :472-529) ---------------------------
+ * ma_median_filter: a 1-D median filter of k taps along the axis n of a strided view (rows, n, inner), dtype MA_DTYPE_F32 or
+ * MA_DTYPE_F64; x_strides and out_strides are three ELEMENT strides each (rows, n, inner), so one entry serves the time axis and
+ * the frequency axis of a (B, F, T) spectrogram in either memory order, without a copy.  The semantics are those of
+ * scipy.ndimage.median_filter(size=k, mode="reflect", origin=0) along that axis:
+ *   the window of output i covers the indices i - k / 2 ... i - k / 2 + k - 1 (an even k leans left);
+ *   the result is the element of rank k / 2 of the sorted window (an even k takes the upper middle, nothing is averaged);
+ *   an index j outside [0, n) is read at j mod 2n, and at 2n - 1 - that where it is >= n: d c b a | a b c d | d c b a.
+ * SciPy leaves this periodic reflection once the window is about 8n wide, so 1 <= k <= MA_MEDIAN_MAX_K and k <= 4n are required
+ * (MA_ERR_INVALID_ARG otherwise).  The output is one of the window's inputs, bit for bit: element j wins when
+ *   #(w[m] < w[j]) + #(w[m] == w[j], m < j) == k / 2,
+ * which exactly one j does whatever the ties (where the tied values are +0 and -0, which of the two zeros comes out is not
+ * specified).  Inputs are finite: the result for a window that holds a NaN is not specified.  A workgroup stages
+ * MA_MEDIAN_SEGMENT outputs' worth of a few lines, plus the k - 1 halo with the reflection applied, in LDS.  No atomics: the same bits
+ * from run to run and for a row alone or inside a batch.  out must not overlap x.
+ *
+ * ma_soft_mask: count elements, a, b (and spec, mask, out) of dtype MA_DTYPE_F32 or MA_DTYPE_F64 laid out alike.  With
+ * x = a * (T)scale_a and r = b * (T)scale_b in the arrays' type T, the reference's order of operations, each correctly rounded
+ * and none contracted into an FMA:
+ *   z = max(x, r); bad = z < tiny(T) (FLT_MIN / DBL_MIN); z = 1 where bad; m = (x / z) ** power, rm = (r / z) ** power;
+ *   m = m / (m + rm), and where bad 0, or 0.5 if split_zeros.
+ * ** 1 is the value itself, ** 2 the product v * v, ** 0.5 the square root (NumPy's fast paths); every other power is powf / pow
+ * with (T)power.  power = +inf: m = x > r.  power <= 0 or NaN: MA_ERR_INVALID_ARG.
+ *   mask (optional): m as T, or for power = +inf as uint8 0 / 1.
+ *   out (optional, with spec): spec * m as T; with phase (count complex64 pairs, float32 only) the complex64 (spec * m) * phase.
+ *   negative (optional): one int32 on the device, set to 1 (a plain store; never cleared here) when any x or r is < 0.
+ * At least one of mask and out is given.
+ *
+ * Both: MA_ERR_INVALID_ARG for a null pointer, a dimension < 1 or an unknown dtype, MA_ERR_UNSUPPORTED where the grid would not fit
+ * 31 bits.  Nothing is launched on a refusal.
+ *
+ * ma_stft_frames_c32: the frames of ma_stft_f32 before the transform, for the n_fft its fused kernels do not cover (spectrum.stft
+ * sends a power-of-two n_fft above 1024 - harmonic's 2048 - through ma_fft_pow2_c32): x (batch, n) float32 with row stride ldx,
+ * frames (batch, n_frames, n_fft) complex64 as float pairs = (window[i] * padded x[f * hop - pad + i], 0), pad = n_fft / 2 when
+ * center else 0, the padding np.pad's MA_PAD_* mode; n_frames must be ma_num_frames(n, n_fft, hop, center).  The errors of
+ * ma_stft_f32; batch > 65535: MA_ERR_UNSUPPORTED.
+ *
+ * ma_istft_rows_c32 / ma_istft_ola_c32: the way back for the same n_fft, around the inverse ma_fft_pow2_c32.  ma_istft_f32 adds a
+ * frame's n_fft / 2 terms one after the other in float32; at n_fft = 2048 that rounding is several times everything else in
+ * features.harmonic.  ma_istft_rows_c32: spec (batch, n_fft / 2 + 1, frames_total) complex64 bin-major -> rows (batch, n_frames,
+ * n_fft) complex64, the Hermitian extension of each of the first n_frames frames (imaginary parts of the DC and Nyquist bins
+ * dropped).  ma_istft_ola_c32: rows = their unnormalised inverse transforms -> out (batch, out_len), ma_istft_f32's synthesis
+ * window, overlap-add, division by the window sum-square (> 1e-9) and `start` offset, on real(rows) / n_fft.  The errors of
+ * ma_istft_f32. */
+#define MA_MEDIAN_MAX_K 127
+#define MA_MEDIAN_SEGMENT 64
+int ma_median_filter(const void* x, int32_t dtype, int64_t rows, int64_t n, int64_t inner, int64_t x_stride_rows, int64_t x_stride_n,
+                     int64_t x_stride_inner, int32_t k, void* out, int64_t out_stride_rows, int64_t out_stride_n,
+                     int64_t out_stride_inner, ma_stream_t stream);
+int ma_soft_mask(const void* a, const void* b, int32_t dtype, int64_t count, double scale_a, double scale_b, double power,
+                 int32_t split_zeros, void* mask, const void* spec, const void* phase, void* out, int32_t* negative,
+                 ma_stream_t stream);
+int ma_stft_frames_c32(const float* x, int64_t batch, int64_t n, int64_t ldx, int32_t n_fft, int32_t hop, const float* window,
+                       int32_t center, int32_t pad_mode, float* frames, int64_t n_frames, ma_stream_t stream);
+int ma_istft_rows_c32(const float* spec, int64_t batch, int32_t n_fft, int64_t frames_total, int64_t n_frames, float* rows,
+                      ma_stream_t stream);
+int ma_istft_ola_c32(const float* rows, int64_t batch, int32_t n_fft, int64_t n_frames, int32_t hop, const float* window,
+                     int32_t start, float* out, int64_t out_len, ma_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -391,10 +391,17 @@ PROTOTYPES = {
     "ma_axis_stats": (ctypes.c_int, [vp, i32, i64, i64, i64, i32, vp, vp]),
     "ma_axis_apply": (ctypes.c_int, [vp, i32, i64, i64, i64, vp, vp, vp, i32, vp]),
     "ma_channel_mean": (ctypes.c_int, [vp, i32, i64, i32, vp, vp]),
+    # ---- harmonic / percussive separation (data.features hpss, soft_mask, harmonic) ----
+    "ma_median_filter": (ctypes.c_int, [vp, i32, i64, i64, i64, i64, i64, i64, i32, vp, i64, i64, i64, vp]),
+    "ma_soft_mask": (ctypes.c_int, [vp, vp, i32, i64, ctypes.c_double, ctypes.c_double, ctypes.c_double, i32, vp, vp, vp, vp, vp, vp]),
+    "ma_stft_frames_c32": (ctypes.c_int, [vp, i64, i64, i64, i32, i32, vp, i32, i32, vp, i64, vp]),
+    "ma_istft_rows_c32": (ctypes.c_int, [vp, i64, i32, i64, i64, vp, vp]),
+    "ma_istft_ola_c32": (ctypes.c_int, [vp, i64, i32, i64, i32, vp, i32, vp, i64, vp]),
 }
 
 FRAME_POWER_TILE, FRAME_POWER_MAX_RATIO, CHANNEL_MEAN_MAX = 16, 32, 8  # MA_FRAME_POWER_TILE, MA_FRAME_POWER_MAX_RATIO, MA_CHANNEL_MEAN_MAX
 DTYPE_F32, DTYPE_F64, DTYPE_I32, DTYPE_I64 = 0, 1, 2, 3  # MA_DTYPE_*
+MEDIAN_MAX_K, MEDIAN_SEGMENT = 127, 64  # MA_MEDIAN_MAX_K, MA_MEDIAN_SEGMENT (the outputs of a line that one workgroup stages)
 AXIS_MAX, AXIS_MIN, AXIS_L0, AXIS_SUM, AXIS_SUMSQ, AXIS_MEAN, AXIS_STD = range(7)  # MA_AXIS_*
 
 IIR_MAX_ORDER = 16  # MA_IIR_MAX_ORDER

@@ -25,7 +25,8 @@ def stft(waveforms, n_fft=512, win_length=None, hop_length=None, window="hann", 
 
     Returns (..., 1 + n_fft/2, 1 + N // hop) complex64 (or a trailing (…, 2) real/imag stack when
     return_complex is False, spectrum.py:275-278).  For a 1-D wave the memory layout is the
-    reference's Fortran order (spectrum.py:252).
+    reference's Fortran order (spectrum.py:252).  n_fft up to 1024 runs in the fused stft kernels; a power of two above that
+    (features.harmonic's 2048) goes through a framing launch and the power-of-two FFT (_stft_pow2).
     """
     t = _host.require_gpu()
     lib = _lib.load()
@@ -45,6 +46,11 @@ def stft(waveforms, n_fft=512, win_length=None, hop_length=None, window="hann", 
     n_frames = lib.ma_num_frames(n, n_fft, hop_length, int(bool(center)))
     _lib.check(min(n_frames, 0), "stft")
     n_freq = n_fft // 2 + 1
+    if n_fft > 1024 and n_fft & (n_fft - 1) == 0:
+        spec = _stft_pow2(t, lib, x, n_fft, hop_length, win, bool(center), pad_mode, n_frames).transpose(1, 2)
+        if not return_complex:
+            spec = t.stack((spec.real, spec.imag), -1)
+        return _finish(spec, lead, was_numpy)
     out = t.empty((x.shape[0], n_frames, n_freq, 2), dtype=t.float32, device=x.device)
     rc = lib.ma_stft_f32(_host.ptr(x), x.shape[0], n, x.stride(0), n_fft, hop_length, _host.ptr(win),
                          int(bool(center)), _lib.PAD_MODES[pad_mode], _lib.STFT_FRAME_MAJOR, _host.ptr(out),
@@ -54,6 +60,33 @@ def stft(waveforms, n_fft=512, win_length=None, hop_length=None, window="hann", 
     if not return_complex:
         spec = t.stack((spec.real, spec.imag), -1)
     return _finish(spec, lead, was_numpy)
+
+
+def _stft_pow2(t, lib, x, n_fft, hop_length, win, center, pad_mode, n_frames):
+    """A power-of-two n_fft above the fused stft kernels' 1024 (features.harmonic's 2048): the windowed frames as complex rows
+    (ma_stft_frames_c32), the batched power-of-two FFT of the resampler (ma_fft_pow2_c32, at most 65535 rows a call), and the first
+    n_fft / 2 + 1 bins copied out -> (B, n_frames, n_freq) complex64, the frame-major memory of the fused path."""
+    import ctypes
+
+    b, n = x.shape
+    n_freq = n_fft // 2 + 1
+    if n_frames > 65535:
+        raise NotImplementedError("stft: n_fft=%d with %d frames per row is not built" % (n_fft, n_frames))
+    spec = t.empty((b, n_frames, n_freq), dtype=t.complex64, device=x.device)
+    step = max(1, 65535 // n_frames)
+    frames = t.empty((min(b, step), n_frames, n_fft, 2), dtype=t.float32, device=x.device)
+    tmp = t.empty_like(frames)
+    for b0 in range(0, b, step):
+        rows = min(step, b - b0)
+        xs = x[b0:b0 + rows]
+        _lib.check(lib.ma_stft_frames_c32(_host.ptr(xs), rows, n, xs.stride(0), n_fft, hop_length, _host.ptr(win), int(center),
+                                          _lib.PAD_MODES[pad_mode], _host.ptr(frames), n_frames, _host.current_stream_ptr()), "stft")
+        res = ctypes.c_void_p()
+        _lib.check(lib.ma_fft_pow2_c32(_host.ptr(frames), _host.ptr(tmp), rows * n_frames, n_fft, 0, ctypes.byref(res),
+                                       _host.current_stream_ptr()), "stft")
+        done = frames if res.value == frames.data_ptr() else tmp
+        spec[b0:b0 + rows] = t.view_as_complex(done)[:rows, :, :n_freq]
+    return spec
 
 
 def frame(x, frame_length=2048, hop_length=64):
@@ -87,6 +120,11 @@ def istft(stft_matrix, n_fft=None, win_length=None, hop_length=None, window="han
     """Inverse STFT — same signature and defaults as spectrum.py:346-354: irfft of every frame, synthesis window, overlap-add,
     division by the window sum-square, centre trimming or `length`.  stft_matrix (..., 1 + n_fft/2, frames) complex64, NumPy
     (returns float64 like the reference's np.float_ buffer, :429) or a device tensor (returns float32).  Arithmetic is float32."""
+    return _istft(stft_matrix, n_fft, win_length, hop_length, window, center, length, False)
+
+
+def _istft(stft_matrix, n_fft, win_length, hop_length, window, center, length, through_fft):
+    """istft; through_fft: the frames by _istft_pow2 instead of ma_istft_f32 (features.harmonic)."""
     import math
 
     t = _host.require_gpu()
@@ -121,6 +159,10 @@ def istft(stft_matrix, n_fft=None, win_length=None, hop_length=None, window="han
         raise ValueError("istft output would be empty")
     b = D.shape[0]
     out = t.empty((b, out_len), dtype=t.float32, device=D.device)
+    if through_fft:
+        _istft_pow2(t, lib, D, n_fft, frames_total, n_frames, hop_length, win, start, out)
+        out = out.reshape(lead + (out_len,))
+        return out.cpu().numpy().astype(np.float64) if was_numpy else out
     ws_bytes = lib.ma_istft_workspace_bytes(b, n_frames, n_fft)
     _lib.check(min(ws_bytes, 0), "istft")
     ws = _host.workspace(ws_bytes, D.device)
@@ -129,6 +171,30 @@ def istft(stft_matrix, n_fft=None, win_length=None, hop_length=None, window="han
     _lib.check(rc, "istft")
     out = out.reshape(lead + (out_len,))
     return out.cpu().numpy().astype(np.float64) if was_numpy else out
+
+
+def _istft_pow2(t, lib, D, n_fft, frames_total, n_frames, hop_length, win, start, out):
+    """The frames of istft through the inverse power-of-two FFT instead of ma_istft_f32's term-by-term sums (features.harmonic: at
+    n_fft = 2048 those sums round several times worse than everything else in it): Hermitian rows, ma_fft_pow2_c32, and the same
+    overlap-add on their real parts.  D (B, n_freq, frames_total) complex64 contiguous; fills out (B, out_len)."""
+    import ctypes
+
+    if n_fft < 2048 or n_fft & (n_fft - 1) or n_frames > 65535:
+        raise NotImplementedError("istft through the FFT needs a power-of-two n_fft >= 2048 and at most 65535 frames")
+    b = D.shape[0]
+    step = max(1, 65535 // n_frames)
+    rows = t.empty((min(b, step), n_frames, n_fft, 2), dtype=t.float32, device=D.device)
+    tmp = t.empty_like(rows)
+    for b0 in range(0, b, step):
+        nb = min(step, b - b0)
+        _lib.check(lib.ma_istft_rows_c32(_host.ptr(t.view_as_real(D[b0:b0 + nb])), nb, n_fft, frames_total, n_frames, _host.ptr(rows),
+                                         _host.current_stream_ptr()), "istft")
+        res = ctypes.c_void_p()
+        _lib.check(lib.ma_fft_pow2_c32(_host.ptr(rows), _host.ptr(tmp), nb * n_frames, n_fft, 1, ctypes.byref(res),
+                                       _host.current_stream_ptr()), "istft")
+        ob = out[b0:b0 + nb]
+        _lib.check(lib.ma_istft_ola_c32(res, nb, n_fft, n_frames, hop_length, _host.ptr(win), start, _host.ptr(ob), out.shape[1],
+                                        _host.current_stream_ptr()), "istft")
 
 
 def _pad_shape(y_shift, data_shape):
