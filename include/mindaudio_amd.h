@@ -31,8 +31,9 @@ extern "C" {
  * 3: ma_ctc_grad_workspace_bytes returns twice the size (alpha and beta side by side, round 4); ma_ffn_train_bf16 accepts ldu == 0
  *    (no tape: u / h are scratch rows); ma_init is per device ordinal; ma_subsample_fused_pack_bf16 takes the float32 conv1 weight
  *    (round 5); ma_attn_out_convmodule_bf16 writes x_out instead of updating x in place (round 5).
+ * 4: the development hook of the two-queue corruption hunt (a dynamic-LDS override of the grouped split-K launch) was removed.
  * The Python binding refuses a library of another version (mindaudio_amd/_lib.py). */
-#define MA_ABI_VERSION 3
+#define MA_ABI_VERSION 4
 
 typedef void* ma_stream_t; /* hipStream_t */
 
@@ -550,9 +551,6 @@ typedef struct ma_tn_item {
   int32_t with_colsum, reserved;
 } ma_tn_item_t;
 int ma_gemm_tn_partial_group_bf16(const ma_tn_item_t* items, int32_t n, ma_stream_t stream);
-/* Development aid of tools/wg_hunt.py (the two-queue corruption hunt): launch the grouped kernel with `bytes` of dynamic
- * LDS (<= 80 KiB; 0 = what it needs), so that its two workgroups per CU leave no LDS for another kernel's workgroups. */
-int ma_debug_tn_group_lds(int32_t bytes);
 
 /* Weight-gradient products WITHOUT split-K (round 4): out (Mo, No) float32 = A^T B, colsum (Mo, may be NULL) = column sums of A,
  * for up to ma_gemm_tn_direct_max_items() products in ONE grid of 256 x 256 tiles, each tile with the full contraction - no partial

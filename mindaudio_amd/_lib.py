@@ -9,7 +9,7 @@ import threading
 
 from . import _build
 
-ABI_VERSION = 3  # MA_ABI_VERSION of include/mindaudio_amd.h this binding was written against (3: round-5, see the header)
+ABI_VERSION = 4  # MA_ABI_VERSION of include/mindaudio_amd.h this binding was written against (see the header for what each changed)
 MA_OK = 0
 MA_ERR_INVALID_ARG = -1
 MA_ERR_NFFT_TOO_LARGE = -2
@@ -228,7 +228,6 @@ PROTOTYPES = {
                                              ctypes.POINTER(TrainEpilogue), vp]),
     "ma_conv2d_3x3s2_dinput_bf16": (ctypes.c_int, [vp, i64, i64, i64, i64, vp, vp, vp, vp, vp]),
     "ma_gemm_tn_partial_group_bf16": (ctypes.c_int, [ctypes.POINTER(TnItem), i32, vp]),
-    "ma_debug_tn_group_lds": (ctypes.c_int, [i32]),
     "ma_gemm_tn_direct_max_items": (i32, []),
     "ma_gemm_tn_direct_group_bf16": (ctypes.c_int, [ctypes.POINTER(TnDirectItem), i32, vp]),
     "ma_convmid_bwd_parts": (i32, [i64, i64]),

@@ -135,17 +135,6 @@ class BucketedAllReduce:
         return covered
 
 
-class _PoolEvent:
-    __slots__ = ("ev",)
-
-    def __init__(self):
-        self.ev = torch.cuda.Event()
-
-    def record_on(self, stream):
-        self.ev.record(stream)
-        return self.ev
-
-
 _LAYER_W = (("ffm_w1", "feed_forward_macaron.w_1"), ("ffm_w2", "feed_forward_macaron.w_2"),
             ("o_w", "self_attn.linear_out"), ("ff_w1", "feed_forward.w_1"), ("ff_w2", "feed_forward.w_2"))
 _LAYER_LN = ("norm_ff_macaron", "norm_mha", "norm_conv", "norm_ff", "norm_final")
@@ -205,11 +194,6 @@ def bucket_spans(fp, L):
     return spans + [fp.span(["after_norm.g", "ctc_b"]), fp.span(embed_names + ["pos_w"])]
 
 
-# tools/wg_hunt.py, wg_twin.py, race_hunt.py, race_pairs.py ONLY (the two-hardware-queue corruption reproducer): keys
-# "wg_stream" and "split_k_sums_on_second_stream".  Not an API: ConformerCTCTrainStep takes no such option.
-_TWO_QUEUE_REPRODUCER = {}
-
-
 class ConformerCTCTrainStep:
     """step(batch columns) -> (loss, cond, loss_scale, overflow, lr): one optimizer step of the ASR model.
 
@@ -238,22 +222,17 @@ class ConformerCTCTrainStep:
         # models/conformer.py:293-313) run one launch per reference cell - the same policy as the evaluation forward (round 6;
         # until then this constructor refused them).
         self.fused = bool(fused) and not self.x32 and enc.d == 256
-        # The step runs on ONE stream.  Rounds 3-4 also had a constructor option that put the weight-gradient products (and, in round 3,
-        # the per-block batched sums) on a second stream: 0.4-14 % of fresh processes then saw a corrupted LayerNorm backward, narrowed
-        # in round 4 to ONE kernel pair on two hardware queues (tn_reduce_batch_kernel beside layernorm_bwd_kernel) and
-        # never explained.  The option is gone (VERDICT r4 #6c); the code path survives only for the reproducer scripts under tools/,
-        # which set the module-level _TWO_QUEUE_REPRODUCER hook below before constructing an engine.
-        self._wg_on = bool(_TWO_QUEUE_REPRODUCER.get("wg_stream")) and self.fused
-        self._wg_split_ok = bool(_TWO_QUEUE_REPRODUCER.get("split_k_sums_on_second_stream"))
-        self._wg, self._wg_keep, self._wg_pool, self._wg_next, self._wg_done, self._dw_par = None, [], [], 0, {}, 0
-        self._wg_stream, self._wg_seen = None, {}
-        self._wg_queue, self._main = [], None
+        # The step runs on ONE stream; the only other queue the product uses is RCCL's (own_stream below).  The round-3/4 arm that put
+        # the weight-gradient products on a second stream was deleted in this commit, with the scripts that drove it.  The corruption it
+        # showed was never explained (DESIGN §"Round 4's two-queue victim", profiles/r06_two_queue_hunt.txt).
+        # _tn_queue: the block's split-K weight-gradient products (dw_group_blocks = 0, or a hidden size that is no multiple of 256),
+        # issued as one grouped launch by _layer_done; _dw_par: which half of the plan's arena the current block uses (_layer_begin)
+        self._tn_queue, self._dw_par = [], 0
         self.K, self.O = (X32, X32) if self.x32 else (K, ops)
         self.model, self.enc = model, enc
         self.dev = next(model.parameters()).device
         if self.dev.type == "cuda":
             _host.require_gpu()  # (+ the library's one-time kernel set-up, ma_init, before any stream of the step exists)
-        self._wg_from = 2  # first step of a batch shape that may use the second stream (tools/wg_hunt.py sets 0)
         # dw_group_blocks = G > 0 (fused bf16 path, d_model and hidden multiples of 256): the eight weight-gradient products of a block
         # are not issued when the block's backward pass is done but together with those of the next G - 1 blocks, as ONE grid of
         # 256 x 256 tiles with the full contraction each (ma_gemm_tn_direct_group_bf16: 39 tiles per block, G = 6 fills the 256 CUs) -
@@ -274,11 +253,6 @@ class ConformerCTCTrainStep:
         # the LayerNorm (chain) behind it) is ONE launch (ma_ffn_train_bf16, the evaluation forward's hidden-slice-owner kernel with the
         # training work in its loop) instead of two: h is not read back for the second product
         self.ffn_one_launch = self.fused  # (and hidden % 256 == 0: settled below, once the model has been read)
-        if self._wg_on and self.dev.type == "cuda":
-            import ctypes
-
-            self._wg_stream = torch.cuda.Stream(device=self.dev)
-            self._wg_ptr = ctypes.c_void_p(self._wg_stream.cuda_stream)
         self.L = len(enc.encoders)
         self.d, self.heads = enc.d, enc.heads
         self.V = model.ctc.ctc_lo.out_features
@@ -310,9 +284,6 @@ class ConformerCTCTrainStep:
         self.block_table_max_bytes = 128 << 30
         self.block_table_max_blocks = 64          # kMaxBlocks of csrc/block_table.hip: encoder blocks + decoder layers + 3 segments
         self._table_bytes, self._table_warned, self._recording_tb, self._walk_shapes = {}, set(), None, set()
-        if self._wg_on and not self._dw_direct and not self._wg_split_ok:
-            raise ValueError("the two-queue reproducer needs the direct weight-gradient groups (dw_group_blocks > 0, d_model and hidden "
-                             "multiples of 256) unless split_k_sums_on_second_stream is set as well (DESIGN 4.6.3)")
         self.ks = enc.kernel
         self.f2 = enc.embed.out.in_features // self.d
         self.p_drop, self.p_pos = float(dropout_rate), float(positional_dropout_rate)
@@ -754,8 +725,8 @@ class ConformerCTCTrainStep:
         total += (att_bytes + 255) // 256 * 256
         off["dpos_all"] = (total, self._t2_cur * self.L * self.d * 4, 0)
         total += (self._t2_cur * self.L * self.d * 4 + 255) // 256 * 256
-        # Two copies of the arena, used by alternate blocks: with the weight-gradient products on their own stream (_wg) block li's
-        # partials are still being summed there while the main stream's LayerNorm / attention backward of block li - 1 write theirs.
+        # Two copies of the arena, used by alternate blocks (_layer_begin): block li's partials and block li - 1's never share bytes.
+        # (Needed when the sums ran on a second stream; kept on the one stream so that every launch keeps its addresses.)
         half = (total + 255) // 256 * 256
         arena = self.__dict__.get("_dw_arena")
         if arena is None or arena.numel() < 2 * half:
@@ -873,7 +844,7 @@ class ConformerCTCTrainStep:
         configuration the table does not cover), else a dict with `state` "record" (walk AND fill) or "replay", the table and the
         buffers at the blocks' boundary, which live at fixed addresses for as long as the table does."""
         plan = self._dw_cur
-        if not (self.block_tables and self.fused and self._dw_direct and self._wg is None and plan is not None and not self.x32):
+        if not (self.block_tables and self.fused and self._dw_direct and plan is not None and not self.x32):
             return None
         key = (b, t2, tuple(att_shape), self.ffn_one_launch, self.ffn_bwd_one_launch, self.ln_final_chained,
                self.ln_bwd_fused, self.dw_group_blocks, self.p_drop, self.p_pos, self.bn_momentum, id(plan["arena"]),
@@ -1015,9 +986,8 @@ class ConformerCTCTrainStep:
                 o, nbytes, _ = plan["off"][sfx]
                 o += self._dw_par * plan["half"]
                 if self.fused:
-                    # queued: the block's eight products leave as ONE grouped launch when its backward pass is done (_layer_done) - on
-                    # the weight-gradient stream behind one event pair, or on the main stream
-                    self._wg_queue.append((dy, x, plan["arena"][o:o + nbytes]))
+                    # queued: the block's eight products leave as ONE grouped launch when its backward pass is done (_layer_done)
+                    self._tn_queue.append((dy, x, plan["arena"][o:o + nbytes]))
                     return
                 self.K.gemm_tn_partial(dy, x, plan["arena"][o:o + nbytes], with_colsum=True)
                 return
@@ -1058,7 +1028,7 @@ class ConformerCTCTrainStep:
             self.drop_block_tables()
             self._dq = self._dq_dec = None
             self._dq_blocks.clear()
-            self._wg_queue.clear()
+            self._tn_queue.clear()
             torch.cuda.synchronize(self.dev)
             torch.cuda.empty_cache()
             self._oom_freed_to = torch.cuda.memory_allocated(self.dev)  # (what the retry starts from; read by the tests)
@@ -1156,22 +1126,13 @@ class ConformerCTCTrainStep:
         xs = xs_pad.to(f32).contiguous()
         enc = self.enc
         fp._grad_alloc.zero_()
-        self._wg_next = 0
-        self._wg_done.clear()
-        self._wg_queue.clear()  # (a step that raised mid-backward must not leave stale products / pinned operands behind)
-        self._wg_keep.clear()
+        self._tn_queue.clear()  # (a step that raised mid-backward must not leave stale products / pinned operands behind)
         if self._dq is not None:
             self._dq.clear()
         if self._dq_dec is not None:
             self._dq_dec.clear()
         self._dq_blocks.clear()
         self._dec_bucket_pending = False
-        # (experimental second stream: used from step _wg_from of a batch shape on - round 3's mitigation, kept; tools/wg_hunt.py sets 0)
-        key = (b, t, idim)
-        seen = self._wg_seen.get(key, 0)
-        self._wg_seen[key] = seen + 1
-        self._wg = self._wg_stream if (self._wg_stream is not None and seen >= self._wg_from) else None
-        self._main = torch.cuda.current_stream() if self._wg is not None else None
 
         # ================= forward =================
         F = self._encoder_forward(xs, xs_masks, xs_chunk_masks, seed)
@@ -1232,20 +1193,7 @@ class ConformerCTCTrainStep:
         dact2 = self._dX(de, "out_w")                  # (m, f2*c) bf16
         K.relu_bwd(dact2, a2)
         dy2 = dact2.view(m * f2, c)
-        if self._wg is not None:
-            # the weight gradient of conv2 beside its input gradient and conv1's weight gradient (all three only need dy2 / act1)
-            need = K.conv2d_dw_workspace_bytes(dy2.shape[0], c, c)
-            if getattr(self, "_wg_ws", None) is None or self._wg_ws.numel() < need:
-                self._wg_ws = torch.empty(need, dtype=torch.uint8, device=self.dev)
-            self._wg.wait_event(self._wg_event().record_on(self._main))
-            prev = _host.swap_pinned(self._wg_ptr)
-            try:
-                K.conv2d_dw(dy2, act1, fp.g("conv2_w"), fp.g("conv2_b"), ws=self._wg_ws)
-            finally:
-                _host.swap_pinned(prev)
-            self._wg_keep.append((dy2, act1, dact2))
-        else:
-            K.conv2d_dw(dy2, act1, fp.g("conv2_w"), fp.g("conv2_b"))
+        K.conv2d_dw(dy2, act1, fp.g("conv2_w"), fp.g("conv2_b"))
         if self.fused:
             dact1 = K.conv2_dinput(dy2, self.wt["conv2_w"], act1)   # implicit GEMM per input-position parity class: no dcol
         else:
@@ -1429,10 +1377,7 @@ class ConformerCTCTrainStep:
                 # (what _layer_done / _flush_direct do besides launching: the finished groups' gradient buckets go on the wire)
                 self._dq_blocks.append(li)
                 if len(self._dq_blocks) >= self.dw_group_blocks or li == 0:
-                    for blk in self._dq_blocks:
-                        self.reducer.launch(*self.fp.span(self.layer_names[blk]))
-                    self._launch_deferred_dec_bucket()
-                    self._dq_blocks.clear()
+                    self._launch_group_buckets()
             return
         if tb is not None:
             with tb["table"].recording(seed):
@@ -1947,68 +1892,26 @@ class ConformerCTCTrainStep:
                 if len(self._dq_blocks) >= self.dw_group_blocks or li == 0:
                     self._flush_direct()
                 return
-            if self._wg is not None:
-                # behind the block's products on their stream AND the main stream's partials (LayerNorm / attention backward) and
-                # direct sums (depthwise convolution, BatchNorm); the bucket goes on the wire behind the sums
-                self._wg.wait_event(self._wg_event().record_on(self._main))
-                prev = _host.swap_pinned(self._wg_ptr)
-                try:
-                    self.K.gemm_tn_partial_group(self._wg_queue, with_colsum=True)  # the block's eight products: one grid
-                finally:
-                    _host.swap_pinned(prev)
-                # (dy / x stay referenced until the step's join: the caching allocator only orders reuse on the allocating stream)
-                self._wg_keep.extend(self._wg_queue)
-                self._wg_queue.clear()
-                _lib.check(_lib.load().ma_reduce_splits_batch_f32(items.data_ptr(), block_item.data_ptr(), n_blocks,
-                                                                  self._wg.cuda_stream), "reduce_splits_batch")
-                if self.reducer.world > 1 or self.reducer.force:
-                    with torch.cuda.stream(self._wg):
-                        self.reducer.launch(*self.fp.span(self.layer_names[li]))
-                else:
-                    self.reducer.launch(*self.fp.span(self.layer_names[li]))
-                done = self._wg_event()
-                done.ev.record(self._wg)
-                self._wg_done[li] = done
-                if li == 0:  # the blocks are done: what follows on the main stream (dW_pos, the embed layer) reads / adds to dpos_all
-                    self._main.wait_event(done.ev)  # and to gradients in the same flat buffer
-                return
-            if self._wg_queue:
-                self.K.gemm_tn_partial_group(self._wg_queue, with_colsum=True)  # the block's eight products: one grid
-                self._wg_queue.clear()
+            if self._tn_queue:
+                self.K.gemm_tn_partial_group(self._tn_queue, with_colsum=True)  # the block's eight products: one grid
+                self._tn_queue.clear()
             _lib.check(_lib.load().ma_reduce_splits_batch_f32(items.data_ptr(), block_item.data_ptr(), n_blocks,
-                                                              torch.cuda.current_stream().cuda_stream), "reduce_splits_batch")
+                                                              _host.current_stream_ptr()), "reduce_splits_batch")
         self.reducer.launch(*self.fp.span(self.layer_names[li]))
 
     def _flush_direct(self):
-        if self._wg is not None:
-            # the group's products (and its gradient buckets) on the second stream, behind what the main stream has produced so far;
-            # the step's join (_embed_done) puts the optimizer behind them
-            self._wg.wait_event(self._wg_event().record_on(self._main))
-            prev = _host.swap_pinned(self._wg_ptr)
-            try:
-                if self._dq is not None:
-                    self._dq.launch()
-            finally:
-                _host.swap_pinned(prev)
-            if self._dq is not None:
-                self._wg_keep.extend(self._dq.keep)  # (operands stay referenced until the join)
-            if self.reducer.world > 1 or self.reducer.force:
-                with torch.cuda.stream(self._wg):
-                    for b in self._dq_blocks:
-                        self.reducer.launch(*self.fp.span(self.layer_names[b]))
-                    self._launch_deferred_dec_bucket()
-            else:
-                for b in self._dq_blocks:
-                    self.reducer.launch(*self.fp.span(self.layer_names[b]))
-                self._launch_deferred_dec_bucket()
-        else:
-            if self._dq is not None:
-                self._dq.launch()
-            for b in self._dq_blocks:
-                self.reducer.launch(*self.fp.span(self.layer_names[b]))
-            self._launch_deferred_dec_bucket()
+        """The group's direct weight-gradient products as one grid, then its gradient buckets."""
+        if self._dq is not None:
+            self._dq.launch()
+        self._launch_group_buckets()
         if self._dq is not None:
             self._dq.clear()
+
+    def _launch_group_buckets(self):
+        """The finished group's gradient buckets go on the wire, then the deferred decoder bucket (walked and replayed alike)."""
+        for b in self._dq_blocks:
+            self.reducer.launch(*self.fp.span(self.layer_names[b]))
+        self._launch_deferred_dec_bucket()
         self._dq_blocks.clear()
 
     def _launch_deferred_dec_bucket(self):
@@ -2021,35 +1924,9 @@ class ConformerCTCTrainStep:
     def _layer_begin(self, li):
         """Backward of block li starts: its partial sums go to arena half li & 1, which block li + 2 used."""
         self._dw_par = li & 1
-        if self._wg is not None:
-            prev = self._wg_done.pop(li + 2, None)
-            if prev is not None:
-                self._main.wait_event(prev.ev)
-
-    def _wg_event(self):
-        """An event from the step's pool (events are re-recorded every step: creating one costs more than recording it)."""
-        if self._wg_next == len(self._wg_pool):
-            self._wg_pool.append(_PoolEvent())
-        e = self._wg_pool[self._wg_next]
-        self._wg_next += 1
-        return e
 
     def _embed_done(self):
         self.reducer.launch(*self.fp.span(["after_norm.g", "ctc_b"]))
-        if self._wg is not None:
-            # the front bucket holds conv2's weight gradient (second stream) and the main stream's sums: behind both; then the main
-            # stream continues behind everything the second stream has done in this step
-            self._wg.wait_event(self._wg_event().record_on(self._main))
-            if self.reducer.world > 1 or self.reducer.force:
-                with torch.cuda.stream(self._wg):
-                    self.reducer.launch(*self.fp.span(self.embed_names + ["pos_w"]))
-            else:
-                self.reducer.launch(*self.fp.span(self.embed_names + ["pos_w"]))
-            done = self._wg_event()
-            done.ev.record(self._wg)
-            self._main.wait_event(done.ev)
-            self._wg_keep.clear()
-            return
         self.reducer.launch(*self.fp.span(self.embed_names + ["pos_w"]))
 
     # ---- one optimizer step ------------------------------------------------------------------------------------------

@@ -139,7 +139,7 @@ def test_new_entry_points_declared_exported_and_bound():
     for name in names:
         assert re.search(r"\b%s\s*\(" % name, header), name
         assert name in _lib.PROTOTYPES and hasattr(lib, name), name
-    assert "#define MA_ABI_VERSION 3" in header and lib.ma_abi_version() == _lib.ABI_VERSION == 3
+    assert "#define MA_ABI_VERSION 4" in header and lib.ma_abi_version() == _lib.ABI_VERSION == 4
     # host-only entry points: the transform length and the workspace of the example's reverb (48 000 samples, 16 000 taps)
     assert lib.ma_aug_fft_conv_length(48000, 16000) == 65536
     assert lib.ma_aug_fft_conv_length(48000, 48000) == 131072

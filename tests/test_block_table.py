@@ -178,7 +178,7 @@ def test_replayed_backward_launches_the_gradient_buckets_where_the_walked_one_do
         eng = object.__new__(E.ConformerCTCTrainStep)
         log = []
         eng.L, eng.d, eng.hidden, eng.K, eng.p_drop = blocks, 256, 2048, None, 0.1
-        eng.dw_group_blocks, eng._dw_direct, eng._wg, eng._dq, eng._dq_blocks = group, True, None, None, []
+        eng.dw_group_blocks, eng._dw_direct, eng._dq, eng._dq_blocks = group, True, None, []
         eng.layer_names = [["l%d.first" % i, "l%d.last" % i] for i in range(blocks)]
         eng.fp = SimpleNamespace(span=lambda names: (names[0], names[-1]))
         eng.reducer = SimpleNamespace(launch=lambda lo, hi: log.append(("bucket", lo, hi)))

@@ -58,7 +58,7 @@ def test_entry_points_declared_exported_and_bound():
         assert re.search(r"\b%s\s*\(" % name, text), name
         assert hasattr(lib, name), name
         assert name in _lib.PROTOTYPES, name
-    assert _lib.ABI_VERSION == 3
+    assert _lib.ABI_VERSION == 4
 
 
 def _cfg(mode, ctc_weight):

@@ -117,7 +117,7 @@ def test_new_entry_points_declared_exported_bound():
         assert re.search(r"\b%s\s*\(" % sym, header), "header lacks %s" % sym
         assert hasattr(lib, sym), "library does not export %s" % sym
         assert sym in _lib.PROTOTYPES
-    assert _lib.ABI_VERSION == 3 and lib.ma_abi_version() == 3
+    assert _lib.ABI_VERSION == 4 and lib.ma_abi_version() == 4
     assert lib.ma_cohort_stats_workspace_bytes(4700, 400000) >= 256 * 400000 * 4
     assert lib.ma_cohort_stats_workspace_bytes(0, 10) < 0
     assert lib.ma_running_mean_sub_workspace_bytes(1000, 192) > 0 and lib.ma_running_mean_sub_workspace_bytes(1000, 100) < 0
