@@ -1475,6 +1475,49 @@ int ma_istft_rows_c32(const float* spec, int64_t batch, int32_t n_fft, int64_t f
 int ma_istft_ola_c32(const float* rows, int64_t batch, int32_t n_fft, int64_t n_frames, int32_t hop, const float* window,
                      int32_t start, float* out, int64_t out_len, ma_stream_t stream);
 
+/* ---- Conv-TasNet separation (mindaudio/models/conv_tasnet.py, mindaudio/loss/separation_loss.py) -------------------------------------
+ * The 1 x 1 convolutions are ma_gemm_bf16 calls; these are the launches between them.  An activation is (M * K, channels) float32,
+ * channels contiguous and a multiple of 64 (at most 8192), utterance m in the rows [m * K, (m + 1) * K), no halo rows.
+ *
+ * Global layer norm statistics travel as PARTIALS: for a (M, K, C) tensor, ma_tasnet_stat_parts(K, C) = P workgroups per utterance
+ * each leave three float64 - (count, sum, sum of (v - its own mean)^2) of its tile - at part[(m * P + p) * 3].  A consumer joins its
+ * utterance's P partials itself in index order; mean = sum / count, var = M2 / count (the mean of (v - mean)^2), normalised value =
+ * (v - mean) / sqrt(var + 1e-8), gamma = 1, beta = 0 (conv_tasnet.py:439-463).  No atomics: the same bits from run to run.
+ *
+ * ma_tasnet_encode_f32: x (M, T) float32, row stride ldx; Wt (L, N) float32 = the transposed encoder weight; L even.
+ *   mixture_w[m * K + k, n] = relu(sum_j x[m, k * L/2 + j] * Wt[j, n]),  K = (T - L) / (L / 2) + 1 (floor);  part: P(K, N) partials.
+ * ma_prelu_gln_stats: y = x >= 0 ? x : weight[0] * x (weight: one float32 on the device; y may be x), part: the moments of y.
+ * ma_gln_dwconv_prelu: z[k, c] = prelu(sum_p Wt[p, c] * n[k + (p - 1) * dilation, c]) with n the normalised y (part_in) and n = 0
+ *   outside [0, K) of the SAME utterance; Wt (P, C) float32 = the transposed depthwise weight, P == 3 (else MA_ERR_UNSUPPORTED);
+ *   part_out: the moments of z.  z must not be y.
+ * ma_gln_apply_bf16: out (M * K, C) bf16 = the normalised y, rounded to nearest even.
+ * ma_tasnet_decode_f32: score (M * K, C * N) float32 (channel c * N + n), mixture_w (M * K, N), basis (L, N) float32 (the Dense
+ *   weight); frame_k[l] = sum_n relu(score) * mixture_w * basis[l, n].  out (M, C, (K + 1) * L / 2):
+ *     MA_TASNET_OVERLAP_PAIRED  out[k * L/2 + j] = frame_k[j] + frame_k[j + L/2], then L / 2 zeros - what the reference's 0 / 1 matrix
+ *                               product computes (conv_tasnet.py:113-119, 187) followed by its pad;
+ *     MA_TASNET_OVERLAP_TRUE    out[k * L/2 + j] += frame_k[j], j < L: the overlap-add.
+ *   L even and <= 64, N % 64 == 0 and <= 768.
+ * ma_si_snr_pairwise: source, estimate (B, C, T) float32, lengths (B) int64 -> out (B, C, C) float64, out[b, i, j] = SI-SNR in dB of
+ *   estimate i against target j over the first lengths[b] samples, lengths[b] clamped to [0, T] (separation_loss.py:188-216: both
+ *   zero-meaned by sum / length; a length of 0 gives 10 log10(EPS) = -80 dB for every pair;
+ *   EPS = 1e-8 added to the target energy, to the noise energy and inside the logarithm), everything in float64.
+ * All: MA_ERR_INVALID_ARG for a null pointer, a dimension < 1 or a misaligned base (16 bytes), MA_ERR_UNSUPPORTED for a shape outside
+ * the above; nothing is launched on a refusal. */
+#define MA_TASNET_OVERLAP_PAIRED 0
+#define MA_TASNET_OVERLAP_TRUE 1
+int32_t ma_tasnet_stat_parts(int64_t K, int32_t C);
+int ma_tasnet_encode_f32(const float* x, int64_t M, int64_t T, int64_t ldx, const float* Wt, int32_t L, int32_t N, float* mixture_w,
+                         double* part, ma_stream_t stream);
+int ma_prelu_gln_stats(const float* x, int64_t M, int64_t K, int32_t C, const float* weight, float* y, double* part,
+                       ma_stream_t stream);
+int ma_gln_dwconv_prelu(const float* y, int64_t M, int64_t K, int32_t C, const double* part_in, const float* Wt, int32_t P,
+                        int32_t dilation, const float* weight, float* z, double* part_out, ma_stream_t stream);
+int ma_gln_apply_bf16(const float* y, int64_t M, int64_t K, int32_t C, const double* part, void* out, ma_stream_t stream);
+int ma_tasnet_decode_f32(const float* score, const float* mixture_w, int64_t M, int64_t K, int32_t C, int32_t N, const float* basis,
+                         int32_t L, int32_t overlap, float* out, ma_stream_t stream);
+int ma_si_snr_pairwise(const float* source, const float* estimate, const int64_t* lengths, int64_t B, int32_t C, int64_t T, double* out,
+                       ma_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

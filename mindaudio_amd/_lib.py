@@ -396,6 +396,14 @@ PROTOTYPES = {
     "ma_stft_frames_c32": (ctypes.c_int, [vp, i64, i64, i64, i32, i32, vp, i32, i32, vp, i64, vp]),
     "ma_istft_rows_c32": (ctypes.c_int, [vp, i64, i32, i64, i64, vp, vp]),
     "ma_istft_ola_c32": (ctypes.c_int, [vp, i64, i32, i64, i32, vp, i32, vp, i64, vp]),
+    # ---- Conv-TasNet separation ----
+    "ma_tasnet_stat_parts": (i32, [i64, i32]),
+    "ma_tasnet_encode_f32": (ctypes.c_int, [vp, i64, i64, i64, vp, i32, i32, vp, vp, vp]),
+    "ma_prelu_gln_stats": (ctypes.c_int, [vp, i64, i64, i32, vp, vp, vp, vp]),
+    "ma_gln_dwconv_prelu": (ctypes.c_int, [vp, i64, i64, i32, vp, vp, i32, i32, vp, vp, vp, vp]),
+    "ma_gln_apply_bf16": (ctypes.c_int, [vp, i64, i64, i32, vp, vp, vp]),
+    "ma_tasnet_decode_f32": (ctypes.c_int, [vp, vp, i64, i64, i32, i32, vp, i32, i32, vp, vp]),
+    "ma_si_snr_pairwise": (ctypes.c_int, [vp, vp, vp, i64, i32, i64, vp, vp]),
 }
 
 FRAME_POWER_TILE, FRAME_POWER_MAX_RATIO, CHANNEL_MEAN_MAX = 16, 32, 8  # MA_FRAME_POWER_TILE, MA_FRAME_POWER_MAX_RATIO, MA_CHANNEL_MEAN_MAX

@@ -1,3 +1,4 @@
 from .conformer import ConformerEncoder  # noqa: F401
+from .conv_tasnet import ConvTasNet  # noqa: F401
 from .ecapatdnn import EcapaTDNN  # noqa: F401
 from .ecapatdnn import Classifier  # noqa: F401

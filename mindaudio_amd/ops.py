@@ -980,3 +980,61 @@ def aam_margin(cosine, targets, margin=0.0, scale=1.0, easy_margin=False):
                                        _host.ptr(out), _host.current_stream_ptr())
     _lib.check(rc, "aam_margin")
     return out
+
+
+def si_snr_pairwise(source, estimate, lengths):
+    """(B, C, C) float64 SI-SNR in dB of estimate i against target j over the first lengths[b] samples (ma_si_snr_pairwise):
+    source, estimate (B, C, T) float32 device tensors, lengths (B) integers in [1, T].  Lengths given on the host (a list, an array
+    or a CPU tensor) are checked against that range; lengths that already live on the device are not read back - the kernel clamps
+    them to [0, T], and an utterance of length 0 comes out as 10 log10(1e-8) = -80 dB for every pair."""
+    t = _host.torch()
+    for name, v in (("source", source), ("estimate", estimate)):
+        if not isinstance(v, t.Tensor) or v.dtype != t.float32 or v.dim() != 3:
+            raise ValueError("%s must be a (B, C, T) float32 tensor" % name)
+    if source.shape != estimate.shape:
+        raise ValueError("source and estimate differ in shape")
+    if not estimate.is_cuda:
+        raise ValueError("estimate must be a tensor on the HIP device")
+    b, c, n = estimate.shape
+    lens = t.as_tensor(lengths)
+    if lens.shape != (b,) or lens.is_floating_point():
+        raise ValueError("lengths must hold one integer per utterance")
+    if not lens.is_cuda and b and (int(lens.min()) < 1 or int(lens.max()) > n):
+        raise ValueError("lengths must lie in [1, T]")
+    _host.require_gpu()
+    est = estimate.contiguous()
+    src = source.to(est.device).contiguous()
+    lens = lens.to(device=est.device, dtype=t.int64).contiguous()
+    out = t.empty((b, c, c), dtype=t.float64, device=est.device)
+    rc = _lib.load().ma_si_snr_pairwise(_host.ptr(src), _host.ptr(est), _host.ptr(lens), b, c, n, _host.ptr(out),
+                                        _host.current_stream_ptr())
+    _lib.check(rc, "si_snr_pairwise")
+    return out
+
+
+def si_snr_pit(source, estimate, lengths):
+    """SI-SNR with permutation-invariant assignment (separation_loss.py:176-250).  Returns (loss, max_snr (B, 1), reordered estimate,
+    perm (B, C), pairwise (B, C, C)): the best of itertools.permutations(range(C)) per utterance (the first wins ties),
+    max_snr = best sum / C, loss = -mean(max_snr), reordered[b, j] = estimate[b, perm[b, j]] with the samples at and beyond
+    lengths[b] zeroed.  The pairwise table comes from the kernel; choosing among the C! sums and the gather are torch ops on
+    (B, C!) and (B, C, T).  `estimate` is not modified."""
+    import itertools
+
+    t = _host.torch()
+    if getattr(estimate, "ndim", 0) == 3 and estimate.shape[1] > 4:  # refused before anything reaches the device
+        raise NotImplementedError("permutation-invariant SI-SNR is built for 1 to 4 sources")
+    pair = si_snr_pairwise(source, estimate, lengths)
+    b, c, n = estimate.shape
+    dev = pair.device
+    perms = t.tensor(list(itertools.permutations(range(c))), dtype=t.int64, device=dev)  # (C!, C): target j <- estimate perm[j]
+    tgt = t.arange(c, device=dev)
+    snr_set = pair[:, perms, tgt].sum(-1)  # (B, C!)
+    # (torch.max does not promise the first index among equal values; the smallest index of the maximum does)
+    best = snr_set.max(dim=1, keepdim=True).values
+    idx = (snr_set == best).to(t.int64).argmax(dim=1)
+    max_snr = (best / c).to(t.float32)
+    perm = perms[idx]  # (B, C)
+    lens = t.as_tensor(lengths).to(device=dev, dtype=t.int64)
+    mask = (t.arange(n, device=dev)[None, :] < lens[:, None]).to(estimate.dtype)[:, None, :]
+    reordered = t.gather(estimate.to(dev), 1, perm[:, :, None].expand(b, c, n)) * mask
+    return -max_snr.mean(), max_snr, reordered, perm, pair

@@ -17,14 +17,16 @@ Parameter names follow the reference's cell attributes (mindaudio/models/conform
 wrappers `Dense.dense`, `Conv1d.conv1d`, `Conv2d.conv2d`, `nn.SequentialCell` indices, BatchNorm `gamma/beta/moving_*`,
 `nn.Embedding.embedding_table`; `convert_names` maps them onto the names of mindaudio_amd.conformer.asr_model.ASRModel.
 `convert_ecapa_names` / `ecapa_to_reference_names` do the same for EcapaTDNN (mindaudio/models/ecapatdnn.py), which
-`load_mindspore_checkpoint` picks when it is handed that module.
+`load_mindspore_checkpoint` picks when it is handed that module, and `convert_conv_tasnet_names` /
+`conv_tasnet_to_reference_names` for ConvTasNet (mindaudio/models/conv_tasnet.py).
 """
 import re
 
 import numpy as np
 
 __all__ = ["read_mindspore_ckpt", "write_mindspore_ckpt", "convert_names", "to_reference_names", "read_epoch_num",
-           "load_mindspore_checkpoint", "convert_ecapa_names", "ecapa_to_reference_names"]
+           "load_mindspore_checkpoint", "convert_ecapa_names", "ecapa_to_reference_names", "convert_conv_tasnet_names",
+           "conv_tasnet_to_reference_names"]
 
 _DTYPES = {"Float32": np.float32, "Float16": np.float16, "Float64": np.float64, "Int32": np.int32, "Int64": np.int64,
            "Int16": np.int16, "Int8": np.int8, "UInt8": np.uint8, "UInt16": np.uint16, "UInt32": np.uint32,
@@ -254,6 +256,51 @@ def _is_ecapa(module):
     return type(module).__name__ == "EcapaTDNN"
 
 
+_TASNET_ALIAS = re.compile(r"(^|\.)(network|net)\.")
+
+
+def convert_conv_tasnet_names(ref_params):
+    """Reference ConvTasNet (mindaudio/models/conv_tasnet.py) parameter names -> mindaudio_amd.models.ConvTasNet's state dict.
+    The cell attributes already carry this package's names (encoder.conv1d_U, separator.bottleneck_conv1x1,
+    separator.temporal_conv_net.<r>.<x>.{conv1x1, prelu, dsconv.depthwise_conv, dsconv.prelu, dsconv.pointwise_conv},
+    separator.mask_conv1x1, decoder.basis_signals); what differs is nn.PReLU's leaf (`w` -> `weight`) and the unit axis MindSpore's
+    nn.Conv1d keeps in its weight ((out, in, 1, k) -> (out, in, k); (out, in, k) is accepted as it is).  The reference registers the
+    same cells a second time inside SequentialCells (`separator.network.*`, `<block>.net.*`): a checkpoint that carries those
+    duplicate names has them ignored, like the optimizer state.  The global layer norm's gamma / beta are NumPy constants in the
+    reference, not parameters, so no name exists for them.
+    Not verified against a file MindSpore wrote (none can be produced here): which of the duplicate paths it saves is inferred from
+    the cell definitions."""
+    out = {}
+    for name, arr in ref_params.items():
+        n = _strip(name)
+        if _SKIP.match(n) or _TASNET_ALIAS.search(n):
+            continue
+        if n.endswith(".prelu.w"):
+            n = n[:-1] + "weight"
+        elif n.endswith(".weight") and arr.ndim == 4 and arr.shape[2] == 1:
+            arr = arr[:, :, 0, :]
+        out[n] = arr
+    return out
+
+
+def conv_tasnet_to_reference_names(state, prefix=""):
+    """Inverse of `convert_conv_tasnet_names`: a ConvTasNet state dict of this package -> {reference name: ndarray in MindSpore's
+    layout} (Conv1d weights with the unit axis, the PReLU leaf `w`)."""
+    out = {}
+    for k, v in state.items():
+        a = v.detach().float().cpu().numpy() if hasattr(v, "detach") else np.asarray(v)
+        if k.endswith(".prelu.weight"):
+            k = k[:-len("weight")] + "w"
+        elif k.endswith(".weight") and a.ndim == 3:
+            a = a[:, :, None, :]
+        out[prefix + k] = a
+    return out
+
+
+def _is_conv_tasnet(module):
+    return type(module).__name__ == "ConvTasNet"
+
+
 def read_epoch_num(path):
     """`int(param_dict.get("epoch_num", 0))` of examples/conformer/train.py:121 - the number of finished epochs the reference's
     ModelCheckpoint appends to every file (`append_info=[{"epoch_num": ...}]`, train.py:157-163)."""
@@ -267,7 +314,10 @@ def load_mindspore_checkpoint(module, path, strict=True):
     import torch
 
     raw = read_mindspore_ckpt(path)
-    params = convert_ecapa_names(raw) if _is_ecapa(module) else convert_names(raw)
+    if _is_conv_tasnet(module):
+        params = convert_conv_tasnet_names(raw)
+    else:
+        params = convert_ecapa_names(raw) if _is_ecapa(module) else convert_names(raw)
     own = module.state_dict()
     state, unexpected = {}, []
     for k, v in params.items():
