@@ -832,7 +832,7 @@ int ma_relpos_attention_bwd_qmask_bf16(const void* qkv, int64_t ld_qkv, const vo
 
 /* nn.Embedding -> x * xscale + pe[l] -> dropout (layers/embedding.py:16-62): out (rows, D) float32, rows = batch * L,
  * token ids clamped into [0, V).  Backward: dtable (V, D) float32 += scatter of xscale * keep/(1-p) * g, every table row summed by
- * one workgroup in row order (no float atomics). */
+ * one workgroup in row order (no float atomics); D <= 1024, MA_ERR_UNSUPPORTED beyond. */
 int ma_embed_posenc_f32(const int32_t* tokens, const float* table, const float* pe, int64_t rows, int32_t L, int32_t D,
                         int32_t V, float xscale, float p, uint32_t seed, uint32_t salt, float* out, ma_stream_t stream);
 int ma_embed_bwd_f32(const int32_t* tokens, const float* g, int64_t rows, int32_t D, int32_t V, float xscale, float p,

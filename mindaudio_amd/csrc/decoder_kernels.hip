@@ -899,6 +899,7 @@ int ma_embed_posenc_f32(const int32_t* tokens, const float* table, const float* 
 int ma_embed_bwd_rows_f32(const int32_t* tokens, const float* g, const float* row_keep, int64_t rows, int32_t D, int32_t V, float xscale,
                           float p, uint32_t seed, uint32_t salt, float* dtable, ma_stream_t stream) {
   if (!tokens || !g || !dtable || rows < 1 || D < 1 || V < 1 || p < 0.0f || p >= 1.0f) return MA_ERR_INVALID_ARG;
+  if (D > 1024) return MA_ERR_UNSUPPORTED;  // (embed_bwd_kernel<4> covers 4 x 256 features: wider rows would lose the rest)
   if (D <= 256)
     MA_LAUNCH(embed_bwd_kernel<1>, dim3(256), dim3(256), 0, (hipStream_t)stream, tokens, g, D, V, xscale, seed, salt, d_thresh(p),
               p > 0.0f ? 1.0f / (1.0f - p) : 1.0f, dtable, rows, row_keep);
