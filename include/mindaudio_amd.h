@@ -210,6 +210,27 @@ typedef struct ma_gemm_epilogue {
 int ma_gemm_bf16(const void* A, int64_t lda, const void* W, int64_t ldw, void* out, int64_t ldo,
                  int64_t M, int64_t N, int64_t K, const ma_gemm_epilogue_t* epi, ma_stream_t stream);
 
+/* Which kernel ma_gemm_bf16 would run for these arguments: a host-side query that launches nothing (tests assert through it that a
+ * shape reaches the kernel they mean to test).  `out` is read for its alignment only; `cus` is the compute-unit count to decide for
+ * (<= 0: the current device's).  Returns a negative MA_ERR_* where ma_gemm_bf16 would refuse the same arguments, else
+ *   MA_GEMM_KERNEL_* | MA_GEMM_VARIANT_EPI1 (the instantiation with the column affine / second activation / sigmoid / tanh)
+ *                    | im2col << MA_GEMM_VARIANT_IM2COL_SHIFT (0 plain A, 1 the 3x3 stride-2 Conv2d, 2 Conv1d taps)
+ *                    | MA_GEMM_VARIANT_NT (bf16 tiles leave through non-temporal stores).
+ * The launch switches on the same decision: the two cannot disagree. */
+#define MA_GEMM_KERNEL_WS512 1          /* weight-stationary, K = 512 */
+#define MA_GEMM_KERNEL_8PH_ROWMAJOR 2   /* 256 x 256 tiles, 8-phase schedule, row-major tile order */
+#define MA_GEMM_KERNEL_8PH_BLOCKED 3    /* ... blocked tile order */
+#define MA_GEMM_KERNEL_TILE_128X128X2 4 /* 128 x 128 tiles, 2-stage ring */
+#define MA_GEMM_KERNEL_TILE_64X128X2 5  /* 64 x 128 tiles, 2-stage ring */
+#define MA_GEMM_KERNEL_TILE_64X128X3 6  /* 64 x 128 tiles, 3-stage ring */
+#define MA_GEMM_KERNEL_TILE_128X128X3 7 /* development builds only */
+#define MA_GEMM_VARIANT_KERNEL_MASK 0xf
+#define MA_GEMM_VARIANT_EPI1 0x10
+#define MA_GEMM_VARIANT_IM2COL_SHIFT 5
+#define MA_GEMM_VARIANT_NT 0x100
+int32_t ma_gemm_bf16_variant(int64_t M, int64_t N, int64_t K, int64_t ldo, const ma_gemm_epilogue_t* epi, const void* out,
+                             int32_t cus);
+
 /* 3x3, stride 2, valid Conv2d (layers/subsampling.py:43) as an implicit GEMM.
  *   act device bf16 NHWC (batch, H, Wd, C), C % 64 == 0;  W device bf16 (Cout, 3, 3, C) i.e. k = (kh, kw, c);
  *   out (batch, Ho, Wo, Cout), Ho = (H-3)/2+1, Wo = (Wd-3)/2+1, dtype per epilogue. */
@@ -350,6 +371,10 @@ int ma_cast_f32_bf16(const float* x, void* y, int64_t n, ma_stream_t stream);
 int ma_conv1d_taps_bf16(const void* act, int64_t lda, int64_t rows, int64_t C, int32_t taps, int32_t dilation,
                         const void* W, void* out, int64_t ldo, int64_t N, const ma_gemm_epilogue_t* epi,
                         ma_stream_t stream);
+
+/* The kernel ma_conv1d_taps_bf16 would run: the sibling of ma_gemm_bf16_variant, same encoding (taps == 1 is a plain GEMM). */
+int32_t ma_conv1d_taps_bf16_variant(int64_t rows, int64_t C, int32_t taps, int32_t dilation, int64_t ldo, int64_t N,
+                                    const ma_gemm_epilogue_t* epi, const void* out, int32_t cus);
 
 /* ---- ECAPA-TDNN forward (mindaudio/models/ecapatdnn.py:7-433): the pieces between its convolutions ------------
  * Activations: (batch, T + 2*halo, C) bf16, zero halo frames around every utterance (see ma_conv1d_taps_bf16). */

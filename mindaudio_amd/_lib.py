@@ -123,6 +123,10 @@ class GemmEpilogue(ctypes.Structure):
 
 SCORE_NORMS = {None: 0, "none": 0, "z-norm": 1, "t-norm": 2, "s-norm": 3}  # MA_SCORE_NORM_*
 ACT_NONE, ACT_SWISH, ACT_RELU, ACT_SIGMOID, ACT_TANH = 0, 1, 2, 3, 4
+# ma_gemm_bf16_variant / ma_conv1d_taps_bf16_variant: MA_GEMM_KERNEL_* | flags
+GEMM_KERNEL_WS512, GEMM_KERNEL_8PH_ROWMAJOR, GEMM_KERNEL_8PH_BLOCKED = 1, 2, 3
+GEMM_KERNEL_TILE_128X128X2, GEMM_KERNEL_TILE_64X128X2, GEMM_KERNEL_TILE_64X128X3 = 4, 5, 6
+GEMM_VARIANT_KERNEL_MASK, GEMM_VARIANT_EPI1, GEMM_VARIANT_IM2COL_SHIFT, GEMM_VARIANT_NT = 0xf, 0x10, 5, 0x100
 
 # name -> (restype, argtypes); must list every symbol include/mindaudio_amd.h declares
 PROTOTYPES = {
@@ -145,6 +149,8 @@ PROTOTYPES = {
                                           ctypes.c_void_p]),
     "ma_gemm_bf16": (ctypes.c_int, [ctypes.c_void_p, i64, ctypes.c_void_p, i64, ctypes.c_void_p, i64, i64, i64, i64,
                                     ctypes.POINTER(GemmEpilogue), ctypes.c_void_p]),
+    "ma_gemm_bf16_variant": (i32, [i64, i64, i64, i64, ctypes.POINTER(GemmEpilogue), ctypes.c_void_p, i32]),
+    "ma_conv1d_taps_bf16_variant": (i32, [i64, i64, i32, i32, i64, i64, ctypes.POINTER(GemmEpilogue), ctypes.c_void_p, i32]),
     "ma_conv2d_3x3s2_nhwc_bf16": (ctypes.c_int, [ctypes.c_void_p, i64, i64, i64, i64, ctypes.c_void_p, i64,
                                                  ctypes.c_void_p, ctypes.POINTER(GemmEpilogue), ctypes.c_void_p]),
     "ma_layernorm_f32": (ctypes.c_int, [ctypes.c_void_p, i64, i64, i64, ctypes.c_void_p, ctypes.c_void_p, f32,

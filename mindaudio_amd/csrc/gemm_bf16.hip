@@ -788,6 +788,19 @@ static int launch_gemm_tile(const GemmParams& p, hipStream_t stream) {
   return MA_OK;
 }
 
+// Tile order of the 8-phase kernel for `tiles_n` column tiles: true = blocked (blk_rows x blk_cols tiles per block), false = row-major.
+// The one place that decides it: the kernel choice (gemm_pick) and the launch both ask here.
+static bool g8_block_order(int tiles_n, int* blk_rows, int* blk_cols) {
+  static int mode = -1;  // MA_G8_BLOCK=0: row-major tile order (A/B switch of tools/)
+  if (mode < 0) mode = (getenv("MA_G8_BLOCK") && getenv("MA_G8_BLOCK")[0] == '0') ? 0 : 1;
+  *blk_rows = *blk_cols = 0;
+  if (!mode || tiles_n < 8) return false;  // (up to 7 column tiles the row-major resident set is already >= 4.5 rows deep)
+  const int nb = (tiles_n + 5) / 6;
+  *blk_cols = (tiles_n + nb - 1) / nb;
+  *blk_rows = 32 / *blk_cols > 1 ? 32 / *blk_cols : 1;
+  return true;
+}
+
 template <int EPI>
 static int launch_gemm_8ph(const GemmParams& p, hipStream_t stream) {
   constexpr int ring = 2 * k8Buf, stage_c = 256 * (256 * 2 + 16);  // K-tile buffers / staged bf16 C tile
@@ -795,16 +808,7 @@ static int launch_gemm_8ph(const GemmParams& p, hipStream_t stream) {
   MA_LDS_ATTR_T(gemm_bf16_8ph_kernel<EPI>, lds);
   const int tiles_n = (p.N + 255) / 256, tiles = ((p.M + 255) / 256) * tiles_n;
   GemmParams q = p;
-  q.blk_rows = q.blk_cols = 0;
-  {
-    static int mode = -1;  // MA_G8_BLOCK=0: row-major tile order (A/B switch of tools/)
-    if (mode < 0) mode = (getenv("MA_G8_BLOCK") && getenv("MA_G8_BLOCK")[0] == '0') ? 0 : 1;
-    if (mode && tiles_n >= 8) {  // (up to 7 column tiles the row-major resident set is already >= 4.5 rows deep)
-      const int nb = (tiles_n + 5) / 6;
-      q.blk_cols = (tiles_n + nb - 1) / nb;
-      q.blk_rows = 32 / q.blk_cols > 1 ? 32 / q.blk_cols : 1;
-    }
-  }
+  g8_block_order(tiles_n, &q.blk_rows, &q.blk_cols);
   MA_LAUNCH((gemm_bf16_8ph_kernel<EPI>), dim3(tiles), dim3(k8Threads), lds, stream, q);
   return MA_OK;
 }
@@ -816,36 +820,71 @@ static int launch_gemm_8ph(const GemmParams& p, hipStream_t stream) {
 #define MA_GEMM_FORCE 0  // development builds only (tools/lib_variant.sh): 1 = never the 256 x 256 kernel, 2 = always when legal,
                          // 3 / 6 = 128 x 128 tiles with 2 / 3 stages, 4 / 5 = 64 x 128 tiles with 2 / 3 stages
 #endif
+// Which kernel a product runs (MA_GEMM_KERNEL_* of the header; `cus` = the device's CU count).  The decision only: launch_gemm
+// switches on the value, ma_gemm_bf16_variant / ma_conv1d_taps_bf16_variant report it.
 template <int IM2COL, int EPI>
-static int launch_gemm(const GemmParams& p, hipStream_t stream) {
+static int gemm_pick(const GemmParams& p, int cus) {
   // 256 x 256 tiles (8-phase kernel) when they fill the chip: plain A operand
   if constexpr (IM2COL == 0 && EPI != 2 && MA_GEMM_FORCE != 1) {
     const int64_t t256 = (int64_t)((p.M + 255) / 256) * ((p.N + 255) / 256);
     // K >= 1024 (with fewer K-tiles the 128 x 128 kernel's shorter prologue / epilogue wins: ECAPA's 512 -> 512 layers 2.49 vs 2.79 ms
     // per forward) and at most 1/8 of the column tiles' width outside the matrix (tools/gemm_bench.py, tools/ecapa_bench.py)
     const int64_t n_pad = (int64_t)((p.N + 255) / 256) * 256 - p.N;
-    if (p.K >= MA_G8_MIN_K && 8 * n_pad <= p.N && (MA_GEMM_FORCE == 2 || t256 >= (int64_t)(0.9 * num_cus())))
-      return launch_gemm_8ph<EPI>(p, stream);
+    if (p.K >= MA_G8_MIN_K && 8 * n_pad <= p.N && (MA_GEMM_FORCE == 2 || t256 >= (int64_t)(0.9 * cus))) {
+      int br, bc;
+      return g8_block_order((p.N + 255) / 256, &br, &bc) ? MA_GEMM_KERNEL_8PH_BLOCKED : MA_GEMM_KERNEL_8PH_ROWMAJOR;
+    }
   }
-  if constexpr (MA_GEMM_FORCE == 3) return launch_gemm_tile<128, 128, 2, IM2COL, EPI>(p, stream);
-  if constexpr (MA_GEMM_FORCE == 4) return launch_gemm_tile<64, 128, 2, IM2COL, EPI>(p, stream);
-  if constexpr (MA_GEMM_FORCE == 5) return launch_gemm_tile<64, 128, 3, IM2COL, EPI>(p, stream);
-  if constexpr (MA_GEMM_FORCE == 6) return launch_gemm_tile<128, 128, 3, IM2COL, EPI>(p, stream);
+  if constexpr (MA_GEMM_FORCE == 3) return MA_GEMM_KERNEL_TILE_128X128X2;
+  if constexpr (MA_GEMM_FORCE == 4) return MA_GEMM_KERNEL_TILE_64X128X2;
+  if constexpr (MA_GEMM_FORCE == 5) return MA_GEMM_KERNEL_TILE_64X128X3;
+  if constexpr (MA_GEMM_FORCE == 6) return MA_GEMM_KERNEL_TILE_128X128X3;
   // ONE column tile, a long contraction and many rows (ECAPA's attention TDNN: 80 896 x 128 x 1536 / 3072, ecapatdnn.py:284-297): 632
   // tiles of 128 rows are 1.23 rounds of the 512 resident workgroups - the second round runs at a quarter of the chip; 64-row tiles with
   // the 3-stage ring: 91.5 -> 79.1 us (round 5, tools/ecapa_bench.py under rocprofv3 with -DMA_GEMM_FORCE variants; the tap convolution
   // of the same launch family is fastest on 128 x 128: it is excluded)
-  if (IM2COL == 0 && p.N <= 128 && p.K >= 1024 && p.M >= 16384) return launch_gemm_tile<64, 128, 3, IM2COL, EPI>(p, stream);
+  if (IM2COL == 0 && p.N <= 128 && p.K >= 1024 && p.M >= 16384) return MA_GEMM_KERNEL_TILE_64X128X3;
   // 128 x 128 tiles unless they would leave most CUs without a workgroup (N = 256 .. 768 at M ~ 8k)
   const int64_t big = (int64_t)((p.M + 127) / 128) * ((p.N + 127) / 128);
   // measured on MI355X (tools/gemm_bench.py): 2 workgroups/CU beat a deeper ring for the 128x128 tile; the
   // 64x128 tile prefers 3 workgroups/CU (2 stages) when there are enough tiles to fill them, else the 3-stage ring
   // (re-measured with the lean epilogue, tools/gemm_tiles.py: 76 800 x 512 x 512 64 vs 70 us on the 64-row tile; the 128 x 128 x 3-stage
   // choice for long K with one tile per CU went: 15 936 x 256 x 4864 49 vs 59 us, x 2048 25 vs 30 us on the 64-row tile with 2 stages)
-  if (big >= 2 * num_cus() && p.K >= 512) return launch_gemm_tile<128, 128, 2, IM2COL, EPI>(p, stream);
+  if (big >= 2 * cus && p.K >= 512) return MA_GEMM_KERNEL_TILE_128X128X2;
   const int64_t small = (int64_t)((p.M + 63) / 64) * ((p.N + 127) / 128);
-  if (small >= (int64_t)(1.9 * num_cus())) return launch_gemm_tile<64, 128, 2, IM2COL, EPI>(p, stream);
-  return launch_gemm_tile<64, 128, 3, IM2COL, EPI>(p, stream);
+  if (small >= (int64_t)(1.9 * cus)) return MA_GEMM_KERNEL_TILE_64X128X2;
+  return MA_GEMM_KERNEL_TILE_64X128X3;
+}
+
+template <int IM2COL, int EPI>
+static int launch_gemm(const GemmParams& p, int kernel, hipStream_t stream) {
+  switch (kernel) {
+    case MA_GEMM_KERNEL_8PH_ROWMAJOR:
+    case MA_GEMM_KERNEL_8PH_BLOCKED:
+      if constexpr (IM2COL == 0 && EPI != 2 && MA_GEMM_FORCE != 1) return launch_gemm_8ph<EPI>(p, stream);
+      break;
+    case MA_GEMM_KERNEL_TILE_128X128X2:
+      if constexpr (MA_GEMM_FORCE < 3 || MA_GEMM_FORCE == 3)  // (a forced build instantiates its one tile kernel)
+        return launch_gemm_tile<128, 128, 2, IM2COL, EPI>(p, stream);
+      break;
+    case MA_GEMM_KERNEL_TILE_64X128X2:
+      if constexpr (MA_GEMM_FORCE < 3 || MA_GEMM_FORCE == 4)
+        return launch_gemm_tile<64, 128, 2, IM2COL, EPI>(p, stream);
+      break;
+    case MA_GEMM_KERNEL_TILE_64X128X3:
+      if constexpr (MA_GEMM_FORCE < 3 || MA_GEMM_FORCE == 5)
+        return launch_gemm_tile<64, 128, 3, IM2COL, EPI>(p, stream);
+      break;
+    case MA_GEMM_KERNEL_TILE_128X128X3:
+      if constexpr (MA_GEMM_FORCE == 6) return launch_gemm_tile<128, 128, 3, IM2COL, EPI>(p, stream);
+      break;
+    default: break;
+  }
+  return MA_ERR_UNSUPPORTED;
+}
+template <int IM2COL, int EPI>
+static int launch_gemm(const GemmParams& p, hipStream_t stream) {
+  return launch_gemm<IM2COL, EPI>(p, gemm_pick<IM2COL, EPI>(p, num_cus()), stream);
 }
 
 // Non-temporal stores for the bf16 output tiles (round 6).  A resident round of tiles writes as many bytes as an XCD's L2 holds
@@ -888,6 +927,69 @@ static int fill_epilogue(GemmParams& p, const ma_gemm_epilogue_t* e) {
 MA_LDS_ATTR(gemm_ws512_kernel<true>, kWsLds);
 MA_LDS_ATTR(gemm_ws512_kernel<false>, kWsLds);
 
+// Grid of the weight-stationary kernel: the largest multiple of 8 XCDs x N / 128 column blocks within the CU count (0: it does not fit)
+static int ws512_grid(int N, int cus) {
+  const int ncb = N / kWsCols;
+  const int grid = cus - cus % (8 * ncb);
+  return grid >= 8 * ncb ? grid : 0;
+}
+
+// ma_gemm_bf16's checks of everything but the operands, and the parameters the kernel choice reads (shared with the variant query)
+static int gemm_plain_params(GemmParams& p, const void* out, int64_t ldo, int64_t M, int64_t N, int64_t K, const ma_gemm_epilogue_t* epi) {
+  if (!out || M < 1 || N < 1 || K < 1 || M > 0x7fffffff || N > 0x7fffffff) return MA_ERR_INVALID_ARG;
+  if (K % BK != 0 || ldo < N) return MA_ERR_UNSUPPORTED;
+  if (epi && epi->bias && (reinterpret_cast<uintptr_t>(epi->bias) & 15)) return MA_ERR_INVALID_ARG;
+  p.out = const_cast<void*>(out);
+  p.ldo = ldo;
+  p.M = (int32_t)M;
+  p.N = (int32_t)N;
+  p.K = (int32_t)K;
+  const int rc = fill_epilogue(p, epi);
+  if (rc != MA_OK) return rc;
+  p.nt_out = gemm_nt_choice(p);
+  return MA_OK;
+}
+
+static int variant_bits(const GemmParams& p, int kernel, int epi, int im2col) {
+  return kernel | (epi ? MA_GEMM_VARIANT_EPI1 : 0) | (im2col << MA_GEMM_VARIANT_IM2COL_SHIFT) | (p.nt_out ? MA_GEMM_VARIANT_NT : 0);
+}
+
+// The variant ma_gemm_bf16 runs for filled parameters on a device of `cus` CUs
+static int gemm_plain_variant(const GemmParams& p, int cus) {
+  // K = 512 with >= 16 k rows and bf16 output (ECAPA's 1 x 1 convolutions at C = 512): the weight-stationary persistent kernel
+  if (p.K == kWsK && (p.N % kWsCols) == 0 && p.N <= 1024 && p.M >= 16384 && p.out_bf16 && !p.residual && p.alpha == 1.0f &&
+      (p.ldo & 7) == 0 && (reinterpret_cast<uintptr_t>(p.out) & 15) == 0 && (!p.bias || (reinterpret_cast<uintptr_t>(p.bias) & 15) == 0) &&
+      ws512_grid(p.N, cus) > 0)
+    return variant_bits(p, MA_GEMM_KERNEL_WS512, 1, 0);  // (its epilogue is the EPI = 1 set)
+  if (p.col_scale || p.act2 || p.act > 2) return variant_bits(p, gemm_pick<0, 1>(p, cus), 1, 0);
+  return variant_bits(p, gemm_pick<0, 0>(p, cus), 0, 0);
+}
+
+// ma_conv1d_taps_bf16's checks of everything but the operands, and the parameters the kernel choice reads
+static int taps_params(GemmParams& p, int64_t rows, int64_t C, int32_t taps, int32_t dilation, const void* out, int64_t ldo, int64_t N,
+                       const ma_gemm_epilogue_t* epi) {
+  if (!out || rows < 1 || C < 1 || N < 1 || taps < 1 || !(taps & 1) || dilation < 1) return MA_ERR_INVALID_ARG;
+  if (C % BK != 0 || ldo < N || rows > 0x7fffffff) return MA_ERR_UNSUPPORTED;
+  p.out = const_cast<void*>(out);
+  p.ldw = (int64_t)taps * C;
+  p.ldo = ldo;
+  p.M = (int32_t)rows;
+  p.N = (int32_t)N;
+  p.K = (int32_t)(taps * C);
+  p.C = (int32_t)C;
+  p.taps = taps;
+  p.dil = dilation;
+  const int rc = fill_epilogue(p, epi);
+  if (rc != MA_OK) return rc;
+  p.nt_out = gemm_nt_choice(p);
+  return MA_OK;
+}
+
+static int taps_variant(const GemmParams& p, int cus) {
+  if (p.taps == 1) return variant_bits(p, gemm_pick<0, 1>(p, cus), 1, 0);  // a plain GEMM: eligible for the 256 x 256 kernel
+  return variant_bits(p, gemm_pick<2, 1>(p, cus), 1, 2);
+}
+
 }  // namespace ma
 
 using namespace ma;
@@ -901,32 +1003,30 @@ int ma_gemm_bf16(const void* A, int64_t lda, const void* W, int64_t ldw, void* o
   if (epi && epi->bias && (reinterpret_cast<uintptr_t>(epi->bias) & 15)) return MA_ERR_INVALID_ARG;
   if ((reinterpret_cast<uintptr_t>(A) & 15) || (reinterpret_cast<uintptr_t>(W) & 15)) return MA_ERR_INVALID_ARG;
   GemmParams p = GemmParams{};
+  const int rc = gemm_plain_params(p, out, ldo, M, N, K, epi);
+  if (rc != MA_OK) return rc;
   p.A = reinterpret_cast<const uint16_t*>(A);
   p.W = reinterpret_cast<const uint16_t*>(W);
-  p.out = out;
   p.lda = lda;
   p.ldw = ldw;
-  p.ldo = ldo;
-  p.M = (int32_t)M;
-  p.N = (int32_t)N;
-  p.K = (int32_t)K;
-  const int rc = fill_epilogue(p, epi);
-  if (rc != MA_OK) return rc;
-  p.nt_out = gemm_nt_choice(p);
-  // K = 512 with >= 16 k rows and bf16 output (ECAPA's 1 x 1 convolutions at C = 512): the weight-stationary persistent kernel
-  if (K == kWsK && (N % kWsCols) == 0 && N <= 1024 && M >= 16384 && p.out_bf16 && !p.residual && p.alpha == 1.0f && (ldo & 7) == 0 &&
-      (reinterpret_cast<uintptr_t>(out) & 15) == 0 && (!p.bias || (reinterpret_cast<uintptr_t>(p.bias) & 15) == 0)) {
-    const int ncb = (int)(N / kWsCols);
-    int grid = num_cus();
-    grid -= grid % (8 * ncb);
-    if (grid >= 8 * ncb) {
-      if (p.row_scale) MA_LAUNCH(gemm_ws512_kernel<true>, dim3((unsigned)grid), dim3(kWsThreads), kWsLds, (hipStream_t)stream, p);
-      else MA_LAUNCH(gemm_ws512_kernel<false>, dim3((unsigned)grid), dim3(kWsThreads), kWsLds, (hipStream_t)stream, p);
-      return MA_OK;
-    }
+  const int variant = gemm_plain_variant(p, num_cus());
+  const int kernel = variant & MA_GEMM_VARIANT_KERNEL_MASK;
+  if (kernel == MA_GEMM_KERNEL_WS512) {
+    const int grid = ws512_grid(p.N, num_cus());
+    if (p.row_scale) MA_LAUNCH(gemm_ws512_kernel<true>, dim3((unsigned)grid), dim3(kWsThreads), kWsLds, (hipStream_t)stream, p);
+    else MA_LAUNCH(gemm_ws512_kernel<false>, dim3((unsigned)grid), dim3(kWsThreads), kWsLds, (hipStream_t)stream, p);
+    return MA_OK;
   }
-  if (p.col_scale || p.act2 || p.act > 2) return launch_gemm<0, 1>(p, (hipStream_t)stream);
-  return launch_gemm<0, 0>(p, (hipStream_t)stream);
+  if (variant & MA_GEMM_VARIANT_EPI1) return launch_gemm<0, 1>(p, kernel, (hipStream_t)stream);
+  return launch_gemm<0, 0>(p, kernel, (hipStream_t)stream);
+}
+
+int32_t ma_gemm_bf16_variant(int64_t M, int64_t N, int64_t K, int64_t ldo, const ma_gemm_epilogue_t* epi, const void* out,
+                             int32_t cus) {
+  GemmParams p = GemmParams{};
+  const int rc = gemm_plain_params(p, out, ldo, M, N, K, epi);
+  if (rc != MA_OK) return rc;
+  return gemm_plain_variant(p, cus > 0 ? cus : num_cus());
 }
 
 int ma_conv1d_taps_bf16(const void* act, int64_t lda, int64_t rows, int64_t C, int32_t taps, int32_t dilation,
@@ -936,23 +1036,22 @@ int ma_conv1d_taps_bf16(const void* act, int64_t lda, int64_t rows, int64_t C, i
   if (C % BK != 0 || lda < C || (lda & 7) || ldo < N || rows > 0x7fffffff) return MA_ERR_UNSUPPORTED;
   if ((reinterpret_cast<uintptr_t>(act) & 15) || (reinterpret_cast<uintptr_t>(W) & 15)) return MA_ERR_INVALID_ARG;
   GemmParams p = GemmParams{};
+  const int rc = taps_params(p, rows, C, taps, dilation, out, ldo, N, epi);
+  if (rc != MA_OK) return rc;
   p.A = reinterpret_cast<const uint16_t*>(act);
   p.W = reinterpret_cast<const uint16_t*>(W);
-  p.out = out;
   p.lda = lda;
-  p.ldw = (int64_t)taps * C;
-  p.ldo = ldo;
-  p.M = (int32_t)rows;
-  p.N = (int32_t)N;
-  p.K = (int32_t)(taps * C);
-  p.C = (int32_t)C;
-  p.taps = taps;
-  p.dil = dilation;
-  const int rc = fill_epilogue(p, epi);
+  const int kernel = taps_variant(p, num_cus()) & MA_GEMM_VARIANT_KERNEL_MASK;
+  if (taps == 1) return launch_gemm<0, 1>(p, kernel, (hipStream_t)stream);
+  return launch_gemm<2, 1>(p, kernel, (hipStream_t)stream);
+}
+
+int32_t ma_conv1d_taps_bf16_variant(int64_t rows, int64_t C, int32_t taps, int32_t dilation, int64_t ldo, int64_t N,
+                                    const ma_gemm_epilogue_t* epi, const void* out, int32_t cus) {
+  GemmParams p = GemmParams{};
+  const int rc = taps_params(p, rows, C, taps, dilation, out, ldo, N, epi);
   if (rc != MA_OK) return rc;
-  p.nt_out = gemm_nt_choice(p);
-  if (taps == 1) return launch_gemm<0, 1>(p, (hipStream_t)stream);  // a plain GEMM: eligible for the 256 x 256 kernel
-  return launch_gemm<2, 1>(p, (hipStream_t)stream);
+  return taps_variant(p, cus > 0 ? cus : num_cus());
 }
 
 static int splitk_plan(int64_t M, int64_t N, int64_t K, int* kt_split) {
