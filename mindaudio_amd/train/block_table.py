@@ -4,11 +4,13 @@
 between `segment(backward, block)` marks is issued as usual AND appended to the table, and every tensor the kernel wrappers allocate
 meanwhile is kept referenced by the table (so that the caching allocator can never hand a recorded address to anybody else).  From the
 next step of that batch shape on the engine issues each block with one `ma_conformer_block_fwd_train` / `_bwd_train` call.
+`TableEntry` is one batch shape's table with its state, `BlockTables` the owner of all entries of an engine.
 
 What is recorded is the reference's training step over the encoder blocks (/root/reference/mindaudio/utils/train_one_step.py:13-48,
 models/conformer.py:109-156); the recorder adds no arithmetic of its own."""
 import ctypes
 import struct
+import warnings
 
 from .. import _lib
 
@@ -201,3 +203,140 @@ class BlockTable:
         rc = self.lib.ma_conformer_block_bwd_train(self.handle, block, seed, stream)
         if rc != 0:
             _lib.check(rc, "conformer_block_bwd_train(block %d, call %d)" % (block, self.lib.ma_block_table_failed_call(self.handle)))
+
+
+# ---- the tables of an engine -----------------------------------------------------------------------------------------------------
+SEEN, RECORD, REPLAY, WALK = "seen", "record", "replay", "walk"
+
+
+# One batch shape's launch table: SEEN (walked from Python, counted) -> RECORD (walked AND filled) -> REPLAY (one C call per block), or
+# WALK: a shape the table cannot cover or could not be recorded for, walked from Python for good.
+class TableEntry:
+    """From RECORD on the entry owns the buffers at the blocks' boundary - they live at fixed addresses for as long as the table
+    does - and `dec`, the decoder's part of the recording."""
+
+    _BUFFERS = ("table", "x_in", "a_in", "mask_rows", "att_mask", "pos_all", "g", "out", "dec")
+
+    def __init__(self, key):
+        self.key, self.state, self.sightings, self.table = key, SEEN, 0, None
+        self._release()
+
+    def _release(self):
+        if self.table is not None:
+            self.table.clear()  # (the recorder's kept tensors: other references to the table must not keep them pinned)
+        for name in self._BUFFERS:
+            setattr(self, name, None)
+
+    def sighted(self, min_sightings, segments, max_segments):
+        """One more step of a SEEN shape: RECORD when this step is the one to record (the caller then calls `record`), WALK when the
+        step has more launch segments than a table holds, else SEEN."""
+        # (the first step(s) warm the wrappers' pooled buffers and tell a recurring shape from a one-off: a loader that pads to the
+        # batch maximum produces many shapes that never come back, and recording each would pin 2-4 GB apiece)
+        self.sightings += 1
+        if self.sightings < max(2, int(min_sightings)):
+            return SEEN
+        if segments > int(max_segments):
+            self.state = WALK
+            return WALK
+        return RECORD
+
+    def record(self, table, b, t2, att_shape, d, L, dev):
+        import torch
+
+        m, f32, bf = b * t2, dict(dtype=torch.float32, device=dev), dict(dtype=torch.bfloat16, device=dev)
+        self.state, self.table = RECORD, table
+        self.x_in, self.a_in = torch.empty((m, d), **f32), torch.empty((m, d), **bf)
+        self.mask_rows, self.att_mask = torch.empty(m, **f32), torch.empty(att_shape, **f32)
+        self.pos_all, self.g = torch.empty((t2, L * d), **bf), torch.empty((m, d), **f32)
+
+    def restart(self):  # (a recorded step that raised before its backward pass was complete: start over on an empty table)
+        if self.table.recorded:
+            self.table = type(self.table)()
+
+    def replay(self):
+        self.state = REPLAY
+
+    def walk(self):  # (for good: the table and every buffer go, the key and the count stay)
+        self._release()
+        self.state = WALK
+
+    def drop(self):  # (the entry leaves its plan: nothing of it may be used again)
+        self._release()
+        self.state = None
+
+
+# Every launch table of one engine.  Entries hang on the batch shape's block-sums plan (`plan.tables`, at most two per plan;
+# `plan.table`: the one in use) and go with it; this object keeps what spans plans.
+class BlockTables:
+    """The ledger of device bytes the recorded tables pin and its budget, the entry being recorded (with the BatchNorm running
+    statistics of before that step), the shapes walked for good after running out of memory, and the warnings already given."""
+
+    def __init__(self, max_bytes, min_sightings, max_blocks, make_table=BlockTable):
+        self.max_bytes, self.min_sightings, self.max_blocks, self._make_table = max_bytes, min_sightings, max_blocks, make_table
+        self.bytes, self.warned, self.recording, self.walk_shapes, self.bn_snapshot = {}, set(), None, set(), None
+
+    def warn(self, msg):
+        if msg not in self.warned:
+            self.warned.add(msg)
+            warnings.warn(msg, RuntimeWarning, stacklevel=3)
+
+    def entry_for(self, plan, key, segments, dims, bn_stats):
+        """The entry to run this step from, None while the shape is walked from Python.  key[:3] = (b, t2, attention-mask shape);
+        `dims` = (d, L, device) of the boundary buffers; `bn_stats` = the (mean, var) tensors to snapshot when recording starts."""
+        tb = plan.table = plan.tables.get(key)
+        if tb is None:
+            while len(plan.tables) >= 2:  # (e.g. the padding-mask and the chunk-mask form of one shape)
+                self.drop(plan.tables, next(iter(plan.tables)))
+            tb = plan.table = plan.tables[key] = TableEntry(key)
+        if key[:3] in self.walk_shapes:
+            tb.state = WALK
+        if tb.state == SEEN:
+            state = tb.sighted(self.min_sightings, segments, self.max_blocks)
+            if state == WALK:
+                self.warn("block tables: %d launch segments > the table's %d: this configuration is walked from Python"
+                          % (segments, self.max_blocks))
+            if state == RECORD:
+                tb.record(self._make_table(), key[0], key[1], key[2], *dims)
+                self.recording = tb
+                self.bn_snapshot = [(m.clone(), v.clone()) for m, v in bn_stats]
+        return tb if tb.state in (RECORD, REPLAY) else None
+
+    def recorded(self, tb):
+        """End of a recorded step: the table replays from the next step on - unless the recorder met a call it cannot replay or the
+        byte budget of all tables is spent: then THIS shape is walked for good (the tables recorded so far stay)."""
+        # (dropping the oldest table instead made a loader's round-robin over its buckets re-record a shape on every step)
+        self.recording = None
+        if tb.table.broken is not None:
+            self.warn("block tables: %s - this batch shape is walked from Python" % tb.table.broken)
+            return tb.walk()
+        nbytes, pinned = tb.table.nbytes(), sum(self.bytes.values())
+        if self.bytes and pinned + nbytes > int(self.max_bytes):
+            self.warn("block tables: %.1f GB of launch tables are recorded (block_table_max_bytes); further batch shapes are "
+                      "walked from Python" % (pinned / 2 ** 30))
+            return tb.walk()
+        tb.replay()
+        self.bytes[tb] = nbytes
+
+    def drop(self, tables, key):
+        tb = tables.pop(key, None)
+        if tb is not None:
+            self.bytes.pop(tb, None)
+            tb.drop()
+
+    def forget_plan(self, plan):  # (it leaves its cache: the ledger must not keep its tables - and their buffers - alive)
+        for key in list(plan.tables):
+            self.drop(plan.tables, key)
+        plan.table = None
+
+    def drop_all(self, plans):
+        for plan in plans:
+            self.forget_plan(plan)
+        self.bytes.clear()
+        self.recording = None
+
+    def out_of_memory(self, plans):
+        """The recording step ran out of memory: every table goes, its shape is walked for good (the caller restores bn_snapshot)."""
+        _lib.set_recording(None)
+        self.walk_shapes.add(self.recording.key[:3])
+        self.drop_all(plans)
+        self.warn("block tables: out of memory while recording a batch shape - tables dropped, the shape is walked from Python")

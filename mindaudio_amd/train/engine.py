@@ -19,6 +19,8 @@ import torch
 from .. import _host, _lib, ops
 from . import kernels as K
 from . import kernels_x32 as X32
+from . import plans
+from .block_table import RECORD, REPLAY, BlockTables
 
 _PAD = 64  # every entry of the flat buffers starts on a 64-element boundary (16-byte aligned in bf16 and f32)
 
@@ -275,15 +277,14 @@ class ConformerCTCTrainStep:
         # (ma_conformer_block_fwd_train / _bwd_train) from the argument table filled while the second step was walked from Python -
         # same calls, same buffers, same order; 4.2 -> ~1.5 ms of host time per step (train/block_table.py, csrc/block_table.hip)
         self.block_tables = self.fused and self._dw_direct
-        self.block_table_min_sightings = 2        # a shape is recorded at its n-th step (>= 2), replayed from the next one on
-        # device bytes all recorded tables together may pin.  A table keeps every buffer of its step (3-5 GB at the yaml's buckets);
+        # block_table_min_sightings: a shape is recorded at its n-th step (>= 2), replayed from the next one on
+        # block_table_max_bytes: device bytes all recorded tables together may pin.  A table keeps every buffer of its step (3-5 GB at the yaml's buckets);
         # the 16 buckets of conformer.yaml together are ~70 GB of the 288.  When the budget is reached the NEW shape stays walked
         # from Python (round 6; until then the oldest table was dropped - under the loader's round-robin over its buckets that is the
         # table needed next: every step evicted, re-walked and re-recorded a shape, 39 ms per hybrid step instead of 9.4,
         # tools/bucket_cycle_bench.py)
-        self.block_table_max_bytes = 128 << 30
-        self.block_table_max_blocks = 64          # kMaxBlocks of csrc/block_table.hip: encoder blocks + decoder layers + 3 segments
-        self._table_bytes, self._table_warned, self._recording_tb, self._walk_shapes = {}, set(), None, set()
+        # block_table_max_blocks: kMaxBlocks of csrc/block_table.hip: encoder blocks + decoder layers + 3 segments
+        self._tables = BlockTables(max_bytes=128 << 30, min_sightings=2, max_blocks=64)
         self.ks = enc.kernel
         self.f2 = enc.embed.out.in_features // self.d
         self.p_drop, self.p_pos = float(dropout_rate), float(positional_dropout_rate)
@@ -307,17 +308,42 @@ class ConformerCTCTrainStep:
             raise ValueError("ctc_weight != 1.0 needs model.decoder")
         self.Ld = len(self.dec.decoders) if self.dec is not None else 0
         self.dec_hidden = self.dec.decoders[0].feed_forward.w_1.out_features if self.dec is not None else 0
-        self.last_acc = None
+        self.last_acc = self.last_loss_ctc = self.last_loss_att = None
         # decoder_fused_launches: the TransformerDecoder's layers on the fused launches of the encoder blocks (dense + dropout + residual
         # + LayerNorm in one launch on packed weights; LayerNorm backward + the next dropout backward in one): 16 + 16 -> 10 + 12
         # launches per layer (round 6).  False: one launch per reference cell (what the float32 validation mode always runs).
         self.decoder_fused_launches = True
         self.decoder_embed_row_mask = True  # the embedding's backward skips the padded label rows (their gradient is exactly zero)
-        self._dec_long_dw, self._dec_bucket_pending, self._dec_rows = True, False, 1
+        self._dec_bucket_pending, self._dec_rows = False, 1
+        # does the ENCODER's backward run from its launch table in this step?  (reset by forward_backward, set by the decoder's half)
+        # forward_only_fused_front: encoder_forward_train runs both subsampling convolutions in one launch
+        self._enc_replay_now, self.forward_only_fused_front = False, True
+        # built on first use and kept: the transposed and fragment-packed weight copies with the item tables of their batched launches
+        # (_wt_plan: None = not built yet, False = a weight the batched transpose does not cover), the packed convolution weights
+        # (False = shape not covered)
+        self.wt, self.pk, self.dec_fused = {}, {}, False
+        self._wt_plan = self._pack_plan = self._pack_arena = self._conv2_pk = self._sub_pk = None
+        # per batch shape (train/plans.py), the last 64 shapes each - the yaml has 16 buckets.  The reference trains on static shapes
+        # (MindSpore graph mode): examples/conformer/conformer.yaml:71-72 has 16 (frame bucket, batch) pairs and pads the labels to
+        # token_max_length, so 16 plans - with their launch tables: the tape and temporaries of one step, 2 - 4 GB - cover a whole
+        # epoch (~45 of 288 GB).  _dw_plan: the last one looked up; _dw_cur / _front_cur: what the running step uses (None: immediate sums)
+        self._dw_plans = plans.PlanCache(64, lambda need, old: need, torch.uint8, self.dev, on_drop=self._tables.forget_plan)
+        self._front_plans = plans.PlanCache(64, lambda need, old: max(need, int(1.25 * old)), torch.uint8, self.dev)
+        self._dec_ln_plans = plans.PlanCache(64, lambda need, old: max(need, 2 * old), torch.float32, self.dev)
+        self._dw_plan = self._dw_cur = self._front_cur = None
+        # _step_host: (pinned loss, pinned overflow flag, event) of enqueue_step -> finish_step; _oom_freed_to: bytes allocated when a
+        # recording step that ran out of memory is run again (read by the tests)
+        self._t2_cur, self._step_host, self._oom_freed_to = 0, None, None
         self._build_flat()
         self.flag = self.fp.flag  # zeroed with the gradients at the start of forward_backward
         self.reducer = BucketedAllReduce(self.fp.grad, self.world, self.pg, force_collective)
         self.refresh_weights()
+
+    # (the launch tables' three limits live with their owner; tests and tools set them on the engine)
+    block_table_max_bytes = property(lambda self: self._tables.max_bytes, lambda self, v: setattr(self._tables, "max_bytes", v))
+    block_table_min_sightings = property(lambda self: self._tables.min_sightings,
+                                         lambda self, v: setattr(self._tables, "min_sightings", v))
+    block_table_max_blocks = property(lambda self: self._tables.max_blocks, lambda self, v: setattr(self._tables, "max_blocks", v))
 
     # ---- flat parameter layout ------------------------------------------------------------------------------------
     def _build_flat(self):
@@ -505,8 +531,6 @@ class ConformerCTCTrainStep:
         if cast:
             _lib.check(_lib.load().ma_cast_f32_bf16(fp.master.data_ptr(), fp.bf16.data_ptr(), fp.size,
                                                     torch.cuda.current_stream().cuda_stream), "cast")
-        if not hasattr(self, "wt"):
-            self.wt = {}
         names = ["conv2_w", "out_w", "ctc_w"]
         for i in range(self.L):
             names += ["l%d.%s" % (i, s) for s in ("ffm_w1", "ffm_w2", "qkv_w", "o_w", "pw1_w", "pw2_w", "ff_w1", "ff_w2")]
@@ -515,19 +539,15 @@ class ConformerCTCTrainStep:
             names.append("dec.out_w")
             for i in range(self.Ld):
                 names += ["d%d.%s" % (i, w) for w in _DEC_W]
-            if getattr(self, "_kv_all", None) is not None and not self.x32:
+            if self._kv_all is not None:
                 names.append("dec.ca_kv_all")  # (a view of the Ld contiguous ca_kv_w tensors, not an entry of the flat index)
                 alias["dec.ca_kv_all"] = self._kv_all["w"]
         wv = lambda n: alias[n] if n in alias else fp.w(n)  # noqa: E731
-        if getattr(self, "_wt_plan", None) is None:
-            # one launch for all of them (ma_transpose_batch_bf16): the item list and the workgroup -> item map are built once, the
-            # bf16 mirror and the transposed copies never move
-            import ctypes
-
-            import numpy as np
-
-            items, block_item, first = [], [], 0
-            for i, n in enumerate(names):
+        if self._wt_plan is None:
+            # one launch for all of them (ma_transpose_batch_bf16): the item table is built once, the bf16 mirror and the transposed
+            # copies never move
+            items = []
+            for n in names:
                 w = wv(n)
                 rows, cols = w.shape
                 self.wt[n] = torch.zeros((cols, K.pad64(rows)), dtype=torch.bfloat16, device=self.dev)
@@ -537,21 +557,12 @@ class ConformerCTCTrainStep:
                 if not ok:
                     items = None
                     break
-                items.append(_lib.TransposeItem(w.data_ptr(), self.wt[n].data_ptr(), w.stride(0), self.wt[n].stride(0), rows, cols,
-                                                first, tc))
-                block_item += [i] * (tr * tc)
-                first += tr * tc
-            if items is None:
-                self._wt_plan = False
-            else:
-                raw = (_lib.TransposeItem * len(items))(*items)
-                dev_items = torch.from_numpy(np.frombuffer(bytes(raw), dtype=np.uint8).copy()).to(self.dev)
-                dev_map = torch.tensor(block_item, dtype=torch.int32, device=self.dev)
-                self._wt_plan = (dev_items, dev_map, first)
+                items.append((_lib.TransposeItem(w.data_ptr(), self.wt[n].data_ptr(), w.stride(0), self.wt[n].stride(0), rows, cols,
+                                                 0, tc), tr * tc))
+            self._wt_plan = plans.ItemTable(items, self.dev) if items is not None else False
         if self._wt_plan:
-            dev_items, dev_map, n_blocks = self._wt_plan
-            _lib.check(_lib.load().ma_transpose_batch_bf16(dev_items.data_ptr(), dev_map.data_ptr(), n_blocks,
-                                                           torch.cuda.current_stream().cuda_stream), "transpose_batch")
+            _lib.check(_lib.load().ma_transpose_batch_bf16(*self._wt_plan.args, torch.cuda.current_stream().cuda_stream),
+                       "transpose_batch")
         else:
             for n in names:
                 if n not in self.wt:
@@ -583,10 +594,8 @@ class ConformerCTCTrainStep:
     def _pack_weights(self):
         """One launch re-packs every block's dense weights (bf16 mirror and transposed copies -> MFMA-fragment order)."""
         lib = _lib.load()
-        if getattr(self, "_pack_plan", None) is None:
-            import numpy as np
-
-            items, block_item, first, total = [], [], 0, 0
+        if self._pack_plan is None:
+            items, total = [], 0
             self.pk = {}
             specs = []
             # the embed layer Linear(f2 * d -> d) (subsampling.py:46-47): 64 rows x 256 outputs per workgroup on a packed weight
@@ -612,7 +621,7 @@ class ConformerCTCTrainStep:
                     specs.append(("l%d.%s" % (li, key), w, n, k, kind, pieces, total))
                     total += pieces * 16 * (2 if kind == 2 else 1)
             self.dec_fused = False
-            if self.dec is not None and self.d == 256 and self.dec_hidden % 256 == 0 and getattr(self, "_kv_all", None) is not None:
+            if self.dec is not None and self.d == 256 and self.dec_hidden % 256 == 0 and self._kv_all is not None:
                 dec_specs, ok = [], True
                 w_all = self._kv_all["w"]
                 pieces = int(lib.ma_pack_item_pieces(0, w_all.shape[0], w_all.shape[1]))
@@ -632,21 +641,14 @@ class ConformerCTCTrainStep:
                 if ok:  # (a shape a pack kind does not cover: the decoder keeps its one-launch-per-cell walk)
                     specs += dec_specs
                     self.dec_fused = True
-            arena = torch.empty(total, dtype=torch.uint8, device=self.dev)
+            arena = self._pack_arena = torch.empty(total, dtype=torch.uint8, device=self.dev)
             for name, w, n, k, kind, pieces, off in specs:
                 self.pk[name] = arena[off:off + pieces * 16 * (2 if kind in (2, 3) else 1)]
-                nblk = (pieces + 255) // 256
-                items.append(_lib.PackItem(w.data_ptr(), arena.data_ptr() + off, w.stride(0), n, k, kind, first))
-                block_item += [len(items) - 1] * nblk
-                first += nblk
-            raw = (_lib.PackItem * len(items))(*items)
-            self._pack_plan = (torch.from_numpy(np.frombuffer(bytes(raw), dtype=np.uint8).copy()).to(self.dev),
-                               torch.tensor(block_item, dtype=torch.int32, device=self.dev), first, arena)
-        dev_items, dev_map, n_blocks, _ = self._pack_plan
-        _lib.check(lib.ma_pack_batch_bf16(dev_items.data_ptr(), dev_map.data_ptr(), n_blocks,
-                                          torch.cuda.current_stream().cuda_stream), "pack_batch")
+                items.append((_lib.PackItem(w.data_ptr(), arena.data_ptr() + off, w.stride(0), n, k, kind, 0), (pieces + 255) // 256))
+            self._pack_plan = plans.ItemTable(items, self.dev)
+        _lib.check(lib.ma_pack_batch_bf16(*self._pack_plan.args, torch.cuda.current_stream().cuda_stream), "pack_batch")
         # the subsampling layer's second convolution runs on its own fragment order (conv2_packed.hip, as the evaluation forward)
-        if getattr(self, "_conv2_pk", None) is None:
+        if self._conv2_pk is None:
             self._conv2_pk = ops.conv2d_3x3s2_pack(self.fp.w("conv2_w").view(self.d, 3, 3, self.d))
         elif isinstance(self._conv2_pk, torch.Tensor):
             _lib.check(lib.ma_conv2d_3x3s2_pack_bf16(self.fp.w("conv2_w").data_ptr(), self.d, self.d, self._conv2_pk.data_ptr(),
@@ -658,285 +660,35 @@ class ConformerCTCTrainStep:
     def _salt(self, layer, site):
         return (layer + 1) * 16 + site
 
-    # Batch shapes whose plan - and block launch table: the tape and temporaries of one step, 2 - 4 GB - stay resident.  The reference
-    # trains on static shapes (MindSpore graph mode): examples/conformer/conformer.yaml:71-72 has 16 (frame bucket, batch) pairs and pads
-    # the labels to token_max_length, so 16 plans cover a whole epoch (~45 of 288 GB).
-    _DW_PLANS_KEPT = 64  # (batch shapes whose plans - and launch tables - stay: the yaml has 16 buckets; least recently used first out)
-
-    _DW_SUFFIXES = ("ffm_w1", "ffm_w2", "qkv_w", "o_w", "pw1_w", "pw2_w", "ff_w1", "ff_w2")
-
-    _LN_SITES = ("norm_final", "norm_ff", "norm_conv", "norm_mha", "norm_ff_macaron")
-
     def _dw_plan_for(self, m):
-        """Deferred parameter-gradient sums of a block (bf16 mode): the eight weight-gradient products write their split-K partials
-        (and one partial bias-gradient vector per split) and the five LayerNorm backward launches their per-workgroup (dgamma | dbeta)
-        partials into ONE arena that all blocks share, and ONE launch per block adds them into the flat gradient in a fixed order
-        (ma_reduce_splits_batch_f32) instead of a 6 us reduction launch per product / per LayerNorm.  The arena is sized for the
-        largest row count seen so far; the per-m offsets and device item tables are re-derived when m changes (one plan is kept)."""
-        if self.x32:
-            return None
-        cur = self.__dict__.get("_dw_plan")
-        if cur is not None and cur["m"] == m and cur.get("t2") == self._t2_cur:
-            return cur
-        # the last few shapes' plans are kept (bucketed batches come back: a plan carries the shape's block launch table), as long as
-        # the shared arena they point into is the one they were derived for
-        plans = self.__dict__.setdefault("_dw_plans", {})
-        kept = plans.pop((m, self._t2_cur), None)
-        if kept is not None and kept["arena"] is self.__dict__.get("_dw_arena"):
-            plans[(m, self._t2_cur)] = kept  # (most recently used last)
-            self._dw_plan = kept
-            return kept
-        import numpy as np
-
-        lib, fp = _lib.load(), self.fp
-        off, total = {}, 0
-        for sfx in () if self._dw_direct else self._DW_SUFFIXES:  # (direct products write the flat gradient themselves)
-            mo, no = fp.w("l0." + sfx).shape
-            nbytes = int(lib.ma_gemm_tn_workspace_bytes(mo, no, m))
-            off[sfx] = (total, nbytes, int(lib.ma_gemm_tn_splits(mo, no, m)))
-            total += (nbytes + 255) // 256 * 256
-        ln_parts = int(lib.ma_layernorm_bwd_parts(m))
-        fused_parts = int(lib.ma_gemm_rows_train_parts(m))  # sites whose backward rides on an input-gradient product (ln_bwd_fused)
-        ffn_parts = int(lib.ma_ffn_train_parts(m))          # ... or on the feed-forward module's one-launch backward
-        most = max(ln_parts, fused_parts, ffn_parts)
-        for site in self._LN_SITES:
-            # (the region keeps the largest size; the item's split count is what the site's producer really writes)
-            parts = fused_parts if (self.fused and self.ln_bwd_fused and site != "norm_final") else ln_parts
-            if self.ffn_bwd_one_launch and site in ("norm_ff", "norm_ff_macaron"):
-                parts = ffn_parts
-            off[site] = (total, most * 512 * 4, parts)
-            total += most * 512 * 4
-        # the depthwise convolution's per-workgroup (d_dw_w | d_dw_b) partials (fused path)
-        cm_parts = int(lib.ma_convmid_bwd_parts(m // self._t2_cur, self._t2_cur))
-        cm_width = self.d * (self.ks + 1)
-        off["convmid"] = (total, cm_parts * cm_width * 4, cm_parts)
-        total += (cm_parts * cm_width * 4 + 255) // 256 * 256
-        # the attention backward's workspace (its dpos / du / dv partials are reduced by the block's launch too) and the buffer the
-        # positional projections' gradients of all blocks accumulate in
-        import ctypes
-
-        b_att = m // self._t2_cur
-        att_bytes = int(lib.ma_relpos_attention_bwd_workspace_bytes(b_att, self._t2_cur, self.heads, self.d // self.heads))
-        dp_off, bias_off, tp_, pph = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int32(), ctypes.c_int32()
-        _lib.check(lib.ma_relpos_attention_bwd_layout(b_att, self._t2_cur, self.heads, self.d // self.heads, ctypes.byref(dp_off),
-                                                      ctypes.byref(bias_off), ctypes.byref(tp_), ctypes.byref(pph)), "attention layout")
-        total = (total + 255) // 256 * 256
-        off["att_ws"] = (total, att_bytes, 0)
-        total += (att_bytes + 255) // 256 * 256
-        off["dpos_all"] = (total, self._t2_cur * self.L * self.d * 4, 0)
-        total += (self._t2_cur * self.L * self.d * 4 + 255) // 256 * 256
-        # Two copies of the arena, used by alternate blocks (_layer_begin): block li's partials and block li - 1's never share bytes.
-        # (Needed when the sums ran on a second stream; kept on the one stream so that every launch keeps its addresses.)
-        half = (total + 255) // 256 * 256
-        arena = self.__dict__.get("_dw_arena")
-        if arena is None or arena.numel() < 2 * half:
-            arena = self._dw_arena = torch.empty(2 * half, dtype=torch.uint8, device=self.dev)
-        layers = []
-        for li in range(self.L):
-            items, block_item, first = [], [], 0
-            base = arena.data_ptr() + (li & 1) * half
-
-            def add(part_ptr, out, mn, ldo, n_cols, splits, pstride, tall, accumulate=True):
-                nonlocal first
-                nblk = (mn + 15) // 16 if tall else (mn + 1023) // 1024
-                items.append(_lib.ReduceItem(part_ptr, out.data_ptr(), mn, ldo, n_cols, splits, 1.0,
-                                             (1 if accumulate else 0) | (2 if tall else 0), first, pstride))
-                block_item.extend([len(items) - 1] * nblk)
-                first += nblk
-
-            for sfx in () if self._dw_direct else self._DW_SUFFIXES:
-                g = fp.g("l%d.%s" % (li, sfx))
-                gb = fp.g("l%d.%s" % (li, sfx.replace("_w", "_b")))
-                mo, no = g.shape
-                o, nbytes, splits = off[sfx]
-                add(base + o, g, mo * no, g.stride(0), no, splits, 0, False)
-                add(base + o + splits * mo * no * 4, gb, mo, mo, mo, splits, 0, False)   # bias: partial column sums
-            for site in self._LN_SITES:
-                o, nbytes, parts = off[site]
-                if site == "norm_final" and self._chain_final() and li < self.L - 1:
-                    parts = ffn_parts  # written by block li + 1's macaron backward launch (ln_final_chained)
-                gg = fp.g("l%d.%s.g" % (li, site))  # (g | b): 2 x 256 contiguous floats of the flat gradient
-                assert fp.index["l%d.%s.b" % (li, site)][0] == fp.index["l%d.%s.g" % (li, site)][0] + 256
-                add(base + o, gg, 512, 512, 512, parts, 512, True)
-            if self.fused:
-                o, nbytes, parts = off["convmid"]
-                add(base + o, fp.g("l%d.dw_w" % li), self.d * self.ks, self.d * self.ks, self.d * self.ks, parts, cm_width, True)
-                add(base + o + self.d * self.ks * 4, fp.g("l%d.dw_b" % li), self.d, self.d, self.d, parts, cm_width, True)
-                t2, d, dk = self._t2_cur, self.d, self.d // self.heads
-                ws_ptr = base + off["att_ws"][0]
-                dpos_l = arena[off["dpos_all"][0]:off["dpos_all"][0] + off["dpos_all"][1]].view(torch.float32).view(t2, self.L * d)
-                # dpos[t][c] of block li += sum over the batch of dp_part[b][t][c]
-                # (stored, not accumulated: every block writes its own 256 columns once per step, so dpos_all needs no zero fill)
-                # ("tall": one partial per utterance in flight per thread group - as a short item, 64 workgroups walked the 40
-                # partials in five dependent rounds of HBM latency, the longest chain of the block's batched sum)
-                add(ws_ptr + dp_off.value * 4, dpos_l[:, li * d:(li + 1) * d], t2 * d, self.L * d, d, b_att, tp_.value * d, True,
-                    accumulate=False)
-                for h in range(self.heads):  # du[h], dv[h] += sum over the (utterance, query block) partials of head h
-                    hb = ws_ptr + (bias_off.value + h * pph.value * 128) * 4
-                    add(hb, fp.g("l%d.u" % li)[h], dk, dk, dk, pph.value, 128, True)
-                    add(hb + dk * 4, fp.g("l%d.v" % li)[h], dk, dk, dk, pph.value, 128, True)
-            raw = (_lib.ReduceItem * len(items))(*items)
-            layers.append((torch.from_numpy(np.frombuffer(bytes(raw), dtype=np.uint8).copy()).to(self.dev),
-                           torch.tensor(block_item, dtype=torch.int32, device=self.dev), first))
-        self._dw_plan = dict(m=m, t2=self._t2_cur, arena=arena, off=off, layers=layers, half=half)
-        for k in [k for k, v in plans.items() if v["arena"] is not arena]:
-            self._forget_plan(plans.pop(k))  # (the arena grew: the older plans' tables name the old one)
-        plans[(m, self._t2_cur)] = self._dw_plan
-        while len(plans) > self._DW_PLANS_KEPT:
-            self._forget_plan(plans.pop(next(iter(plans))))
-        if self.fused:
-            o, nb, _ = off["att_ws"]
-            self._dw_plan["att_ws"] = (arena[o:o + nb], arena[half + o:half + o + nb])
-            o, nb, _ = off["dpos_all"]
-            self._dw_plan["dpos_all"] = arena[o:o + nb].view(torch.float32).view(self._t2_cur, self.L * self.d)
+        """The block-sums plan of (m, t2) (plans.block_sums_plan; bf16 mode)."""
+        self._dw_plan = None if self.x32 else self._dw_plans.get((m, self._t2_cur)) or plans.block_sums_plan(
+            self._dw_plans, m, self._t2_cur, self.fp, self.dev, self.L, self.d, self.heads, self.ks, self.fused, self.ln_bwd_fused,
+            self.ffn_bwd_one_launch, self._chain_final(), self._dw_direct)
         return self._dw_plan
 
     def _front_plan_for(self, m, t2):
-        """The three weight gradients outside the blocks (CTC head, embed layer, positional projections): split-K partials into one
-        arena, one batched sum at the end of the backward pass instead of five reduction launches (fused bf16 path)."""
-        # (one plan per batch shape, the last _DW_PLANS_KEPT of them on one grow-only arena: with ONE cached plan every change of
-        # bucket rebuilt it - an allocation and two synchronous host-to-device copies per step of a real epoch)
-        plans = self.__dict__.setdefault("_front_plans", {})
-        cur = plans.get((m, t2))
-        if cur is not None:
-            plans[(m, t2)] = plans.pop((m, t2))
-            self._front_plan = cur
-            return cur
-        import numpy as np
-
-        lib, fp = _lib.load(), self.fp
-        prods = (("ctc", self.Vp, self.d, m, self.V, fp.g("ctc_w"), fp.g("ctc_b")),
-                 ("out", self.d, self.f2 * self.d, m, self.d, fp.g("out_w"), fp.g("out_b")),
-                 ("pos", self.L * self.d, self.d, t2, self.L * self.d, fp.g("pos_w"), None))
-        off, total = {}, 0
-        for name, mo, no, kc, mo_store, _, _ in prods:
-            nbytes = int(lib.ma_gemm_tn_workspace_bytes(mo, no, kc))
-            off[name] = (total, nbytes, int(lib.ma_gemm_tn_splits(mo, no, kc)))
-            total += (nbytes + 255) // 256 * 256
-        arena = self.__dict__.get("_front_arena")
-        if arena is None or arena.numel() < total:
-            arena = self._front_arena = torch.empty(max(total, int(1.25 * (arena.numel() if arena is not None else 0))),
-                                                    dtype=torch.uint8, device=self.dev)
-            plans.clear()  # (their item tables name the old arena)
-        items, block_item, first = [], [], 0
-        for name, mo, no, kc, mo_store, gw, gb in prods:
-            o, _, splits = off[name]
-            for part, out, mn, ldo, ncols in ((arena.data_ptr() + o, gw, mo_store * no, gw.stride(0), no),) + \
-                    (((arena.data_ptr() + o + splits * mo_store * no * 4, gb, mo_store, mo_store, mo_store),) if gb is not None else ()):
-                nblk = (mn + 1023) // 1024
-                items.append(_lib.ReduceItem(part, out.data_ptr(), mn, ldo, ncols, splits, 1.0, 1, first, 0))
-                block_item.extend([len(items) - 1] * nblk)
-                first += nblk
-        raw = (_lib.ReduceItem * len(items))(*items)
-        self._front_plan = plans[(m, t2)] = dict(key=(m, t2), arena=arena, off=off, n_blocks=first,
-                                                 items=torch.from_numpy(np.frombuffer(bytes(raw), dtype=np.uint8).copy()).to(self.dev),
-                                                 block_item=torch.tensor(block_item, dtype=torch.int32, device=self.dev))
-        while len(plans) > self._DW_PLANS_KEPT:
-            plans.pop(next(iter(plans)))
-        return self._front_plan
+        return self._front_plans.get((m, t2)) or plans.front_plan(self._front_plans, m, t2, self.fp, self.dev, self.L, self.d, self.f2,
+                                                                  self.V, self.Vp)
 
     def _front_dW(self, name, dy, x, rows_store=None, with_colsum=True):
-        o, nbytes, _ = self._front_cur["off"][name]
-        self.K.gemm_tn_partial(dy, x, self._front_cur["arena"][o:o + nbytes], with_colsum=with_colsum, rows_store=rows_store)
+        o, nbytes, _ = self._front_cur.off[name]
+        self.K.gemm_tn_partial(dy, x, self._front_cur.arena[o:o + nbytes], with_colsum=with_colsum, rows_store=rows_store)
 
     def _block_table_for(self, b, t2, att_shape):
-        """The launch table of the current batch shape: None (the blocks are walked from Python: first step of a shape, or a
-        configuration the table does not cover), else a dict with `state` "record" (walk AND fill) or "replay", the table and the
-        buffers at the blocks' boundary, which live at fixed addresses for as long as the table does."""
+        """The launch-table entry of the current batch shape (block_table.TableEntry: RECORD = walk AND fill, or REPLAY), or None."""
+        # (None: the blocks are walked from Python - first step(s) of a shape, or a configuration the table does not cover)
         plan = self._dw_cur
         if not (self.block_tables and self.fused and self._dw_direct and plan is not None and not self.x32):
             return None
         key = (b, t2, tuple(att_shape), self.ffn_one_launch, self.ffn_bwd_one_launch, self.ln_final_chained,
-               self.ln_bwd_fused, self.dw_group_blocks, self.p_drop, self.p_pos, self.bn_momentum, id(plan["arena"]),
+               self.ln_bwd_fused, self.dw_group_blocks, self.p_drop, self.p_pos, self.bn_momentum, id(plan.arena),
                self.decoder_fused_launches, self.decoder_embed_row_mask)
-        tables = plan.setdefault("tables", {})
-        tb = plan["table"] = tables.get(key)  # (plan["table"]: the one in use, for tests and tools)
-        if tb is None:
-            while len(tables) >= 2:  # (e.g. the padding-mask and the chunk-mask form of one shape)
-                self._drop_table(tables, next(iter(tables)))
-            tb = plan["table"] = tables[key] = dict(key=key, state="seen", sightings=0)
-        if key[:3] in self._walk_shapes:
-            tb["state"] = "walk"
-        if tb["state"] == "walk":  # a shape the table cannot cover (or could not be recorded for): walked from Python for good
-            return None
-        if tb["state"] == "seen":
-            # the first step(s) of a shape warm the wrappers' pooled buffers and tell a recurring shape from a one-off (a loader that pads
-            # to the batch maximum produces many shapes that never come back: recording each would pin 2-4 GB apiece)
-            tb["sightings"] += 1
-            if tb["sightings"] < max(2, int(self.block_table_min_sightings)):
-                return None
-            blocks = self.L + self.Ld + 3
-            if blocks > int(self.block_table_max_blocks):
-                self._table_warn("block tables: %d launch segments > the table's %d: this configuration is walked from Python"
-                                 % (blocks, self.block_table_max_blocks))
-                tb["state"] = "walk"
-                return None
-            from .block_table import BlockTable
-
-            m, d, f32, bf = b * t2, self.d, torch.float32, torch.bfloat16
-            tb.update(state="record", table=BlockTable(),
-                      x_in=torch.empty((m, d), dtype=f32, device=self.dev), a_in=torch.empty((m, d), dtype=bf, device=self.dev),
-                      mask_rows=torch.empty(m, dtype=f32, device=self.dev),
-                      att_mask=torch.empty(att_shape, dtype=f32, device=self.dev),
-                      pos_all=torch.empty((t2, self.L * d), dtype=bf, device=self.dev),
-                      g=torch.empty((m, d), dtype=f32, device=self.dev))
-            self._recording_tb = (tables, key)
-            self._bn_snapshot = [(m_.clone(), v_.clone()) for m_, v_ in zip(self.bn_mean, self.bn_var)]
-        return tb
-
-    def _forget_plan(self, plan):
-        for tb in plan.get("tables", {}).values():  # (the byte ledger must not keep a dropped plan's tables - and their buffers - alive)
-            self._table_bytes.pop(id(tb), None)
-            tb.clear()
-
-    def _table_warn(self, msg):
-        if msg not in self._table_warned:
-            self._table_warned.add(msg)
-            import warnings
-
-            warnings.warn(msg, RuntimeWarning, stacklevel=3)
-
-    def _drop_table(self, tables, key):
-        tb = tables.pop(key, None)
-        if tb is not None:
-            self._table_bytes.pop(id(tb), None)
-            tb.clear()
-
-    def _table_recorded(self, tb):
-        """End of a recorded step: the table replays from the next step on - unless the recorder met a call it cannot replay (then the
-        shape is walked for good) or the byte budget of all tables is spent (then THIS shape stays walked, the recorded ones stay)."""
-        table = tb["table"]
-        self._recording_tb = None
-        if table.broken is not None:
-            self._table_warn("block tables: %s - this batch shape is walked from Python" % table.broken)
-            for k in [k for k in tb if k not in ("key", "sightings")]:
-                del tb[k]
-            tb["state"] = "walk"
-            return
-        nbytes = table.nbytes()
-        if self._table_bytes and sum(n for n, _ in self._table_bytes.values()) + nbytes > int(self.block_table_max_bytes):
-            # over the budget: this shape is walked from Python from now on; the tables recorded so far stay
-            self._table_warn("block tables: %.1f GB of launch tables are recorded (block_table_max_bytes); further batch shapes are "
-                             "walked from Python" % (sum(n for n, _ in self._table_bytes.values()) / 2 ** 30))
-            table.clear()
-            for k in [k for k in tb if k not in ("key", "sightings")]:
-                del tb[k]
-            tb["state"] = "walk"
-            return
-        tb["state"] = "replay"
-        self._table_bytes[id(tb)] = (nbytes, tb)
+        return self._tables.entry_for(plan, key, self.L + self.Ld + 3, (self.d, self.L, self.dev), zip(self.bn_mean, self.bn_var))
 
     def drop_block_tables(self):
         """Forget every recorded launch table (and the buffers they pin); the next steps of every shape are walked and re-recorded."""
-        for plan in self._dw_plans.values() if hasattr(self, "_dw_plans") else ():
-            for tb in (plan.pop("tables", None) or {}).values():
-                table = tb.get("table")
-                if table is not None and hasattr(table, "clear"):
-                    table.clear()  # (the recorder's kept tensors: other references to the dict must not keep them pinned)
-                tb.clear()
-            plan.pop("table", None)
-        self._table_bytes.clear()
-        self._recording_tb = None
+        self._tables.drop_all(self._dw_plans.plans.values())
 
     def _chain_final(self):
         """norm_final's backward as the second stage of the block above's macaron backward launch (needs the one-launch forms)."""
@@ -944,22 +696,22 @@ class ConformerCTCTrainStep:
 
     def _ln_partials(self, site):
         """The arena slice that LayerNorm `site` of the current block writes its per-workgroup partials to (None: immediate sums)."""
-        plan = getattr(self, "_dw_cur", None)
+        plan = self._dw_cur
         if plan is None:
             return None
-        o, nbytes, _ = plan["off"][site]
-        o += self._dw_par * plan["half"]
-        return plan["arena"][o:o + nbytes].view(torch.float32)
+        o, nbytes, _ = plan.off[site]
+        o += self._dw_par * plan.half
+        return plan.arena[o:o + nbytes].view(torch.float32)
 
     def _dW(self, dy, x, wname, bname):
         """grad[wname] (N, K) += dy^T x ; grad[bname] += column sums of dy.  dy (M, N), x (M, K) bf16."""
         fp = self.fp
-        plan = getattr(self, "_dw_cur", None)
+        plan = self._dw_cur
         if self._dw_direct and wname[0] == "d" and wname[1].isdigit() and bname is not None and \
                 self.K.gemm_tn_direct_ok(dy, x, fp.g(wname)):
             # a decoder layer's weight gradient: with the other 41 of the decoder in ONE grid at the end of its backward pass
             # (they were 43 split-K products + 88 reduction launches of ~10 us each: the hybrid step's decoder is launch-bound)
-            if self._dec_long_dw and not self.block_tables and dy.shape[0] > 4 * self._dec_rows:
+            if not self.block_tables and dy.shape[0] > 4 * self._dec_rows:
                 # a decoder product over the ENCODER's rows (ca_kv_w: dkv^T memory, 10 200 rows against the decoder's 1 240): in the
                 # decoder's grid its 2 tiles per layer ran 400 us with 244 CUs idle behind them (the grid lasts as long as its longest
                 # tile).  It joins the encoder's first direct group instead - 234 + 12 tiles, still one resident round, every tile with a
@@ -977,19 +729,19 @@ class ConformerCTCTrainStep:
             return
         if plan is not None and wname[0] == "l" and bname is not None:
             sfx = wname.split(".", 1)[1]
-            if self._dw_direct and sfx in self._DW_SUFFIXES and self.K.gemm_tn_direct_ok(dy, x, fp.g(wname)):
+            if self._dw_direct and sfx in plans.DW_SUFFIXES and self.K.gemm_tn_direct_ok(dy, x, fp.g(wname)):
                 if self._dq is None:
                     self._dq = self.K.DirectGroup()
                 self._dq.add(dy, x, fp.g(wname), fp.g(bname))  # issued with the group (_layer_done)
                 return
-            if sfx in plan["off"]:
-                o, nbytes, _ = plan["off"][sfx]
-                o += self._dw_par * plan["half"]
+            if sfx in plan.off:
+                o, nbytes, _ = plan.off[sfx]
+                o += self._dw_par * plan.half
                 if self.fused:
                     # queued: the block's eight products leave as ONE grouped launch when its backward pass is done (_layer_done)
-                    self._tn_queue.append((dy, x, plan["arena"][o:o + nbytes]))
+                    self._tn_queue.append((dy, x, plan.arena[o:o + nbytes]))
                     return
-                self.K.gemm_tn_partial(dy, x, plan["arena"][o:o + nbytes], with_colsum=True)
+                self.K.gemm_tn_partial(dy, x, plan.arena[o:o + nbytes], with_colsum=True)
                 return
         self.K.gemm_tn(dy, x, fp.g(wname), colsum=fp.g(bname) if bname else None)
 
@@ -1010,33 +762,28 @@ class ConformerCTCTrainStep:
         # A step that RECORDS a block launch table pins every buffer it allocates (2-4 GB per shape).  If that is what runs the device
         # out of memory: drop every table, give the memory back, walk this shape from Python for good and run the step again - with the
         # BatchNorm running statistics of before the attempt (the only state a forward pass changes besides the gradients).
-        # (snapshot taken by _block_table_for when a shape enters its recording step)
+        # (snapshot taken by the tables' owner when a shape enters its recording step)
+        self._enc_replay_now = False
         with _host.pinned_stream():
-            oom_key = None
             try:
                 return self._forward_backward(*args)
             except torch.OutOfMemoryError:
                 # Only NOTE the failure here: while this block runs, the exception's traceback keeps the failed attempt's frames - its
                 # tape, activations and the recording table's pinned buffers - alive, so nothing could be given back from in here
                 # (the PyTorch FAQ's out-of-memory recovery pattern).
-                rec = self._recording_tb
-                if rec is None:
+                if self._tables.recording is None:
                     raise
-                oom_key = rec[1]
             # (outside the handler: the traceback and with it every tensor of the failed attempt are gone)
-            _lib.set_recording(None)
-            self.drop_block_tables()
+            self._tables.out_of_memory(self._dw_plans.plans.values())
             self._dq = self._dq_dec = None
             self._dq_blocks.clear()
             self._tn_queue.clear()
             torch.cuda.synchronize(self.dev)
             torch.cuda.empty_cache()
             self._oom_freed_to = torch.cuda.memory_allocated(self.dev)  # (what the retry starts from; read by the tests)
-            for (m0, v0), m, v in zip(self._bn_snapshot, self.bn_mean, self.bn_var):
+            for (m0, v0), m, v in zip(self._tables.bn_snapshot, self.bn_mean, self.bn_var):
                 m.copy_(m0)
                 v.copy_(v0)
-            self._table_warn("block tables: out of memory while recording a batch shape - tables dropped, the shape is walked from Python")
-            self._walk_shapes.add(oom_key[:3])
             return self._forward_backward(*args)
 
     def _encoder_forward(self, xs, xs_masks, xs_chunk_masks, seed, tables=True):
@@ -1051,14 +798,14 @@ class ConformerCTCTrainStep:
         b = xs.shape[0]
         enc = self.enc
         act1 = None
-        if not tables and self.fused and xs.shape[2] == 80 and getattr(self, "forward_only_fused_front", True):
+        if not tables and self.fused and xs.shape[2] == 80 and self.forward_only_fused_front:
             # nothing reads conv1's output again without a backward pass: both convolutions in one launch (subsample_fused.hip)
-            if getattr(self, "_sub_pk", None) is None:
+            if self._sub_pk is None:
                 self._sub_pk = ops.subsample_fused_pack(fp.p("conv1_w").reshape(d, 9).contiguous(), fp.w("conv2_w").view(d, 3, 3, d), 80)
             act2 = ops.subsample_fused(xs, self._sub_pk, fp.p("conv1_b"), fp.p("conv2_b"), enc.cmvn_mean, enc.cmvn_istd)
         else:
             act1 = ops.subsample_conv1(xs, fp.p("conv1_w"), fp.p("conv1_b"), enc.cmvn_mean, enc.cmvn_istd)
-            if self.fused and isinstance(getattr(self, "_conv2_pk", None), torch.Tensor):
+            if self.fused and isinstance(self._conv2_pk, torch.Tensor):
                 act2 = ops.conv2d_3x3s2_packed(act1, self._conv2_pk, fp.p("conv2_b"), relu=True)
             else:
                 act2 = ops.conv2d_3x3s2_nhwc(act1, fp.w("conv2_w").view(d, 3, 3, d), fp.p("conv2_b"), relu=True)
@@ -1072,14 +819,14 @@ class ConformerCTCTrainStep:
         chunked = xs_chunk_masks is not None and xs_chunk_masks.dim() == 3 and xs_chunk_masks.shape[1] == t2 and t2 > 1
         tb = self._block_table_for(b, t2, (b, t2, t2) if chunked else (b, t2)) if tables else None
         if tb is not None:  # (the blocks' inputs live at the table's addresses: conversion and placement in one launch)
-            mask2d = tb["mask_rows"].view(b, t2).copy_(xs_masks.reshape(b, t2))
+            mask2d = tb.mask_rows.view(b, t2).copy_(xs_masks.reshape(b, t2))
         else:
             mask2d = xs_masks.reshape(b, t2).to(f32).contiguous()
         mask_rows = mask2d.reshape(m)
         # (B, T') padding mask, or the (B, T', T') chunk masks of the streaming configuration (models/conformer.py:251-252)
         att_mask = enc._attention_mask(mask2d, xs_chunk_masks, b, t2, f32)
         if tb is not None and att_mask is not mask2d:
-            att_mask = tb["att_mask"].copy_(att_mask)
+            att_mask = tb.att_mask.copy_(att_mask)
         hlens = mask2d.sum(1).to(torch.int32)
         a2 = act2.view(m, f2 * c)
         if self.fused and "out_w.r" in self.pk:
@@ -1087,14 +834,14 @@ class ConformerCTCTrainStep:
         else:
             e = ops.gemm(a2, fp.w("out_w"), bias=fp.p("out_b"), alpha=math.sqrt(d), out_dtype=f32)
         if pp > 0:
-            x = K.dropout_add(None, e, 1.0, pp, seed, self._salt(-1, 0), out=tb["x_in"] if tb is not None else None)
+            x = K.dropout_add(None, e, 1.0, pp, seed, self._salt(-1, 0), out=tb.x_in if tb is not None else None)
         else:
-            x = e if tb is None else tb["x_in"].copy_(e)
+            x = e if tb is None else tb.x_in.copy_(e)
         pe = enc.pe[:t2].to(f32).contiguous()
         if pp > 0:
             pe = K.dropout_add(None, pe, 1.0, pp, seed, self._salt(-1, 1))
         pe_bf = ops.cast_bf16(pe)
-        pos_all = ops.gemm(pe_bf, fp.w("pos_w"), out=tb["pos_all"] if tb is not None else None)  # (t2, L*256) bf16
+        pos_all = ops.gemm(pe_bf, fp.w("pos_w"), out=tb.pos_all if tb is not None else None)  # (t2, L*256) bf16
         ctx_ = dict(seed=seed, b=b, t2=t2, m=m, mask_rows=mask_rows, att_mask=att_mask, pos_all=pos_all, table=tb, keep_tape=tables)
         if self.fused:
             x, enc_bf, tape = self._blocks_forward_fused(x, ctx_)
@@ -1166,10 +913,10 @@ class ConformerCTCTrainStep:
             d_enc = self._dX(dlog, "ctc_w")            # (m, 256) bf16
         else:                                                   # + the decoder's gradient w.r.t. the encoder output
             d_enc = self._dX(dlog, "ctc_w", residual=d_mem, out_dtype=f32, out=d_mem)
-        g = tb["g"] if tb is not None else torch.empty((m, d), dtype=f32, device=self.dev)
+        g = tb.g if tb is not None else torch.empty((m, d), dtype=f32, device=self.dev)
         K.layernorm_bwd(x, fp.p("after_norm.g"), d_enc, g, fp.g("after_norm.g"), fp.g("after_norm.b"), accumulate=False)
         if self.fused and self._dw_cur is not None:
-            dpos_all = self._dw_cur["dpos_all"]  # (every element is written by the blocks' batched sums)
+            dpos_all = self._dw_cur.dpos_all  # (every element is written by the blocks' batched sums)
         else:
             dpos_all = torch.zeros((t2, L * d), dtype=f32, device=self.dev)
         if self.fused:
@@ -1186,8 +933,7 @@ class ConformerCTCTrainStep:
         if front:
             self._front_dW("out", de, a2)
             fpl = self._front_cur  # the three sums in one launch
-            _lib.check(_lib.load().ma_reduce_splits_batch_f32(fpl["items"].data_ptr(), fpl["block_item"].data_ptr(), fpl["n_blocks"],
-                                                              _host.current_stream_ptr()), "front reduce")
+            fpl.sums.reduce("front reduce")
         else:
             self._dW(de, a2, "out_w", "out_b")
         dact2 = self._dX(de, "out_w")                  # (m, f2*c) bf16
@@ -1294,20 +1040,17 @@ class ConformerCTCTrainStep:
         seed, b, t2, mask_rows, att_mask, pos_all, pd = c["seed"], c["b"], c["t2"], c["mask_rows"], c["att_mask"], c["pos_all"], self.p_drop
         hid = self.hidden
         tb = c.get("table")
-        a = ops.layernorm(x, fp.p("l0.norm_ff_macaron.g"), fp.p("l0.norm_ff_macaron.b"), out=tb["a_in"] if tb is not None else None)
-        if tb is not None and tb["state"] == "replay":  # one C call per block: the launches recorded at this batch shape
+        a = ops.layernorm(x, fp.p("l0.norm_ff_macaron.g"), fp.p("l0.norm_ff_macaron.b"), out=tb.a_in if tb is not None else None)
+        if tb is not None and tb.state == REPLAY:  # one C call per block: the launches recorded at this batch shape
             stream = _host.current_stream_ptr()
             for li in range(L):
-                tb["table"].forward(li, seed, stream)
-            return tb["out"]
+                tb.table.forward(li, seed, stream)
+            return tb.out
         if tb is not None:
-            if tb["table"].recorded:  # (a recorded step that raised before its backward pass was complete: start over)
-                from .block_table import BlockTable
-
-                tb["table"] = BlockTable()
-            with tb["table"].recording(seed):
-                tb["out"] = self._blocks_forward_walk(x, a, c, tb["table"])
-            return tb["out"]
+            tb.restart()  # (a recorded step that raised before its backward pass was complete starts over)
+            with tb.table.recording(seed):
+                tb.out = self._blocks_forward_walk(x, a, c, tb.table)
+            return tb.out
         return self._blocks_forward_walk(x, a, c, None)
 
     def _blocks_forward_walk(self, x, a, c, rec):
@@ -1370,19 +1113,19 @@ class ConformerCTCTrainStep:
         seed, b, t2, mask_rows, att_mask, pos_all, pd = c["seed"], c["b"], c["t2"], c["mask_rows"], c["att_mask"], c["pos_all"], self.p_drop
         hid = self.hidden
         tb = c.get("table")
-        if tb is not None and tb["state"] == "replay":
+        if tb is not None and tb.state == REPLAY:
             stream = _host.current_stream_ptr()
             for li in reversed(range(L)):
-                tb["table"].backward(li, seed, stream)
+                tb.table.backward(li, seed, stream)
                 # (what _layer_done / _flush_direct do besides launching: the finished groups' gradient buckets go on the wire)
                 self._dq_blocks.append(li)
                 if len(self._dq_blocks) >= self.dw_group_blocks or li == 0:
                     self._launch_group_buckets()
             return
         if tb is not None:
-            with tb["table"].recording(seed):
-                self._blocks_backward_walk(g, tape, dpos_all, c, tb["table"])
-            self._table_recorded(tb)
+            with tb.table.recording(seed):
+                self._blocks_backward_walk(g, tape, dpos_all, c, tb.table)
+            self._tables.recorded(tb)
             return
         self._blocks_backward_walk(g, tape, dpos_all, c, None)
 
@@ -1445,7 +1188,7 @@ class ConformerCTCTrainStep:
             dctx = K.dense_plain(do, PK("o_w.tk"), d, d)
             # (dpos / du / dv: the partial sums stay in the plan's workspace and are added by the block's reduction launch)
             dqkv = K.attention_bwd(A["qkv"], pos_all[:, li * d:(li + 1) * d], P("u"), P("v"), att_mask, A["ctx"], dctx, A["lse"], b, t2,
-                                   None, None, None, self.heads, d // self.heads, ws=self._dw_cur["att_ws"][self._dw_par])
+                                   None, None, None, self.heads, d // self.heads, ws=self._dw_cur.att_ws[self._dw_par])
             self._dW(dqkv, A["a"], pre + "qkv_w", pre + "qkv_b")
             if self.ln_bwd_fused:
                 dy = K.dense_lnbwd(dqkv, PK("qkv_w.tr"), 3 * d, A["x_in"], P("norm_mha.g"), g, self._ln_partials("norm_mha"),
@@ -1484,11 +1227,11 @@ class ConformerCTCTrainStep:
         # Does the ENCODER's backward run from its launch table in this step?  Its first direct group then already holds the product
         # the decoder's walk would queue (_decoder_walk_fused: the memory-side weight gradient) - also when the decoder itself is
         # walked from Python because this batch's label length is not the recorded one, which is the common case on real data.
-        self._enc_replay_now = tb is not None and tb["state"] == "replay"
-        if tb is not None and not self.len_norm and tb["state"] in ("record", "replay"):
-            dtb = tb.get("dec")
-            if tb["state"] == "record":
-                dtb = tb["dec"] = dict(L1=L1, ls={},
+        self._enc_replay_now = tb is not None and tb.state == REPLAY
+        if tb is not None and not self.len_norm and tb.state in (RECORD, REPLAY):
+            dtb = tb.dec
+            if tb.state == RECORD:
+                dtb = tb.dec = dict(L1=L1, ls={},
                                        toks=torch.empty(md, dtype=torch.int32, device=self.dev),
                                        sub=torch.empty(tuple(ys_sub_masks.shape), dtype=f32, device=self.dev),
                                        pe=dec.pe[:L1].to(f32).contiguous().clone(),
@@ -1506,14 +1249,14 @@ class ConformerCTCTrainStep:
         # (conversion and placement in one launch each; the positional table is constant)
         toks, sub, pe = dtb["toks"].copy_(ys_in_pad.reshape(-1)), dtb["sub"].copy_(ys_sub_masks), dtb["pe"]
         tgt, tmask = dtb["tgt"].copy_(ys_out_pad.reshape(-1)), dtb["tmask"].copy_(ys_masks.reshape(-1))
-        if tb["state"] == "record":
-            with tb["table"].recording(seed):
-                dtb["out"] = self._decoder_walk(mem_bf, enc_mask2d, b_, t2, L1, toks, sub, pe, tgt, tmask, gscale, seed, tb["table"],
+        if tb.state == RECORD:
+            with tb.table.recording(seed):
+                dtb["out"] = self._decoder_walk(mem_bf, enc_mask2d, b_, t2, L1, toks, sub, pe, tgt, tmask, gscale, seed, tb.table,
                                                 dtb["ls"])
             dtb["bucket_deferred"] = self._dec_bucket_pending  # (the replayed steps launch the bucket where the walked one did)
             stats, d_mem = dtb["out"]
         else:
-            table, stream, L, Ld = tb["table"], _host.current_stream_ptr(), self.L, self.Ld
+            table, stream, L, Ld = tb.table, _host.current_stream_ptr(), self.L, self.Ld
             table.forward(L + Ld, seed, stream)
             for li in range(Ld):
                 table.forward(L + li, seed, stream)
@@ -1551,7 +1294,7 @@ class ConformerCTCTrainStep:
         seg = (lambda backward, blk: rec.segment(backward, blk)) if rec is not None else (lambda backward, blk: None)
         L, Ld = self.L, self.Ld
         self._dec_rows = md  # (what _dW compares a product's contraction length with)
-        if self.fused and getattr(self, "dec_fused", False) and self.decoder_fused_launches:
+        if self.fused and self.dec_fused and self.decoder_fused_launches:
             return self._decoder_walk_fused(mem_bf, emask, b, t2, L1, toks, sub, pe, tgt, tmask, gscale, seed, rec, ls, seg)
         seg(False, L + Ld)
         x = K.embed_posenc(toks, fp.p("dec.embed"), pe, L1, xscale, pp, seed, salt(-1, 0))
@@ -1649,50 +1392,7 @@ class ConformerCTCTrainStep:
         return stats[0] / (stats[2] if self.len_norm else b), d_mem
 
     def _dec_ln_plan(self, md):
-        """The decoder's 3 Ld + 1 LayerNorm backwards leave their per-workgroup (dgamma | dbeta) partials in one arena and ONE batched
-        launch adds them into the flat gradient at the end of the decoder's backward pass (19 reduction launches of 5.6 us fewer per
-        hybrid step; the encoder blocks do the same per block, _dw_plan_for).
-        One plan per row count md = B x (longest label + 1), which changes from batch to batch on real data: the plans of the last
-        _DEC_LN_PLANS_KEPT row counts stay (building one costs two synchronous host-to-device copies - the item tables - i.e. the
-        host's whole lead over the device), all on one grow-only arena; a launch table that recorded a plan keeps it alive itself."""
-        plans = self.__dict__.setdefault("_dec_ln_plans", {})
-        cur = plans.get(md)
-        if cur is not None:
-            plans[md] = plans.pop(md)  # (most recently used last)
-            self._dec_ln = cur
-            return cur
-        import numpy as np
-
-        fp = self.fp
-        parts = int(_lib.load().ma_layernorm_bwd_parts(md))
-        sites = ["dec.after_norm"] + ["d%d.%s" % (li, ln) for li in range(self.Ld) for ln in ("norm1", "norm2", "norm3")]
-        need = len(sites) * parts * 512
-        arena = self.__dict__.get("_dec_ln_arena")
-        if arena is None or arena.numel() < need:
-            # (a larger arena: the plans built on the old one go - recorded tables hold theirs, and through it the old arena)
-            arena = self._dec_ln_arena = torch.empty(max(need, 2 * (arena.numel() if arena is not None else 0)), dtype=torch.float32,
-                                                     device=self.dev)
-            plans.clear()
-        items, block_item, first, bufs = [], [], 0, {}
-        for i, site in enumerate(sites):
-            gg = fp.g(site + ".g")  # (g | b): 2 x 256 contiguous floats of the flat gradient
-            assert fp.index[site + ".b"][0] == fp.index[site + ".g"][0] + 256
-            bufs[site] = arena[i * parts * 512:(i + 1) * parts * 512]
-            nblk = (512 + 15) // 16
-            items.append(_lib.ReduceItem(bufs[site].data_ptr(), gg.data_ptr(), 512, 512, 512, parts, 1.0, 1 | 2, first, 512))
-            block_item += [i] * nblk
-            first += nblk
-        raw = (_lib.ReduceItem * len(items))(*items)
-        cur = dict(md=md, arena=arena, bufs=bufs, n_blocks=first,
-                   items=torch.from_numpy(np.frombuffer(bytes(raw), dtype=np.uint8).copy()).to(self.dev),
-                   block_item=torch.tensor(block_item, dtype=torch.int32, device=self.dev))
-        plans[md] = cur
-        while len(plans) > self._DEC_LN_PLANS_KEPT:
-            plans.pop(next(iter(plans)))
-        self._dec_ln = cur
-        return cur
-
-    _DEC_LN_PLANS_KEPT = 64
+        return self._dec_ln_plans.get(md) or plans.dec_ln_plan(self._dec_ln_plans, md, self.fp, self.dev, self.Ld)
 
     def _decoder_walk_fused(self, mem_bf, emask, b, t2, L1, toks, sub, pe, tgt, tmask, gscale, seed, rec, ls, seg):
         """_decoder_walk on the fused launches the encoder blocks already use (round 6; bf16 mode, d_model 256): per layer 10 forward
@@ -1766,22 +1466,21 @@ class ConformerCTCTrainStep:
         g = tt.empty((md, d), dtype=f32, device=self.dev)
         dlp = self._dec_ln_plan(md)  # (the LayerNorm backwards' partial sums: one batched reduction at the end)
         if rec is not None:
-            # the recorded launches name this plan's arena and item table: they must outlive the plan of the next label width
-            # (_dec_ln_plan keeps ONE; a batch with another longest transcript replaced it and the table's next replay faulted)
+            # the recorded launches name this plan's arena and item table: they must outlive the plan's place in its cache
             rec.keep.append(dlp)
-        lnp = dlp["bufs"]
+        lnp = dlp.bufs
         # after_norm's backward emits the dropout backward of the last layer's feed-forward join
         _, dyf = K.layernorm_bwd_next(x, fp.p("dec.after_norm.g"), dy, g, None, None, (1.0, pd, seed, salt(Ld - 1, 3), None),
                                       accumulate=False, eps=eps, partials=lnp["dec.after_norm"])
         d_mem = tt.empty((m, d), dtype=f32, device=self.dev)  # (stored by ONE product behind the layers: no fill, no accumulation)
         # dkv_all lives with the batch shape's plan, at ONE address for walked, recorded and replayed steps alike: the encoder's
         # first direct group reads it (below), and that group may be a recorded launch of another step's
-        plan = getattr(self, "_dw_cur", None)
-        merge = plan is not None and self._dw_direct and self._dec_long_dw
+        plan = self._dw_cur
+        merge = plan is not None and self._dw_direct
         if merge:
-            dkv_all = plan.get("dkv_all")
+            dkv_all = plan.dkv_all
             if dkv_all is None or tuple(dkv_all.shape) != (m, Ld * 2 * d):
-                dkv_all = plan["dkv_all"] = torch.empty((m, Ld * 2 * d), dtype=torch.bfloat16, device=self.dev)
+                dkv_all = plan.dkv_all = torch.empty((m, Ld * 2 * d), dtype=torch.bfloat16, device=self.dev)
             merge = K.gemm_tn_direct_ok(dkv_all, mem_bf, self._kv_all["gw"])
         else:
             dkv_all = tt.empty((m, Ld * 2 * d), dtype=torch.bfloat16, device=self.dev)
@@ -1832,7 +1531,7 @@ class ConformerCTCTrainStep:
         if merge:
             # (a replayed encoder backward has the item in its recorded group - same operands, same addresses; queueing it here as
             # well would leave it in a group nobody launches, with operands that die with this step)
-            if not getattr(self, "_enc_replay_now", False):
+            if not self._enc_replay_now:
                 if self._dq is None:
                     self._dq = K.DirectGroup()
                 self._dq.add(dkv_all, mem_bf, self._kv_all["gw"], self._kv_all["gb"])
@@ -1841,8 +1540,7 @@ class ConformerCTCTrainStep:
             K.gemm_tn(dkv_all, mem_bf, self._kv_all["gw"], colsum=self._kv_all["gb"])
         # (tmask: the padded label positions - their rows of g are exactly zero, the label mask keeps them out of every valid position)
         K.embed_bwd(toks, g, fp.g("dec.embed"), xscale, pp, seed, salt(-1, 0), row_keep=tmask if self.decoder_embed_row_mask else None)
-        _lib.check(_lib.load().ma_reduce_splits_batch_f32(dlp["items"].data_ptr(), dlp["block_item"].data_ptr(), dlp["n_blocks"],
-                                                          _host.current_stream_ptr()), "decoder LayerNorm sums")
+        dlp.sums.reduce("decoder LayerNorm sums")
         if self._dq_dec is not None:  # the decoder layers' weight gradients: one grid
             self._dq_dec.launch()
             self._dq_dec.clear()
@@ -1880,14 +1578,12 @@ class ConformerCTCTrainStep:
     def _layer_done(self, li):
         """Backward of block li is complete: its slice of the flat gradient can go on the wire while earlier blocks
         are still being differentiated."""
-        plan = getattr(self, "_dw_cur", None)
+        plan = self._dw_cur
         if plan is not None:  # the split sums of this block's weight gradients, one launch
-            items, block_item, n_blocks = plan["layers"][li]
             if self._dw_direct:
                 # the block's partial sums (LayerNorm, depthwise convolution, attention biases) now; its weight-gradient products
                 # leave with the group, and the group's gradient buckets behind them
-                _lib.check(_lib.load().ma_reduce_splits_batch_f32(items.data_ptr(), block_item.data_ptr(), n_blocks,
-                                                                  _host.current_stream_ptr()), "reduce_splits_batch")
+                plan.layers[li].reduce("reduce_splits_batch")
                 self._dq_blocks.append(li)
                 if len(self._dq_blocks) >= self.dw_group_blocks or li == 0:
                     self._flush_direct()
@@ -1895,8 +1591,7 @@ class ConformerCTCTrainStep:
             if self._tn_queue:
                 self.K.gemm_tn_partial_group(self._tn_queue, with_colsum=True)  # the block's eight products: one grid
                 self._tn_queue.clear()
-            _lib.check(_lib.load().ma_reduce_splits_batch_f32(items.data_ptr(), block_item.data_ptr(), n_blocks,
-                                                              _host.current_stream_ptr()), "reduce_splits_batch")
+            plan.layers[li].reduce("reduce_splits_batch")
         self.reducer.launch(*self.fp.span(self.layer_names[li]))
 
     def _flush_direct(self):
@@ -1916,7 +1611,7 @@ class ConformerCTCTrainStep:
 
     def _launch_deferred_dec_bucket(self):
         """The decoder's gradient bucket when some of its weight gradients ride in the encoder's first direct group (_dW)."""
-        if getattr(self, "_dec_bucket_pending", False):
+        if self._dec_bucket_pending:
             self._dec_bucket_pending = False
             if self.dec_names:
                 self.reducer.launch(*self.fp.span(self.dec_names))
@@ -1987,7 +1682,7 @@ class ConformerCTCTrainStep:
         # What finish_step hands to the host - the overflow flag and the loss - leaves for pinned memory here, with an event behind it:
         # finish_step waits for THAT, not for the stream, so whatever the caller enqueues between enqueue_step and finish_step (the next
         # batch's feature and collate launches, conformer/train.py) runs on the device while the host already reads this step's results.
-        host = self.__dict__.get("_step_host")
+        host = self._step_host
         if host is None:
             host = self._step_host = (torch.empty(1, dtype=torch.float32, pin_memory=True), torch.empty(1, dtype=self.flag.dtype, pin_memory=True),
                                       torch.cuda.Event())
@@ -2004,7 +1699,7 @@ class ConformerCTCTrainStep:
 
     def finish_step(self, loss, scale, lr):
         two = self.lr_step_rule == "mindspore23"
-        host = self.__dict__.get("_step_host")
+        host = self._step_host
         if host is not None:
             host[2].synchronize()
             overflow = bool(int(host[1][0]))  # the reference also hands `cond` back to the host every step

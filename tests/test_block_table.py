@@ -123,7 +123,7 @@ def test_recording_is_per_thread():
 def test_a_launch_the_table_cannot_reissue_marks_the_table_and_is_still_issued():
     """A call the table cannot replay inside a block does not stop the walked step it is met in (the step is complete and correct
     all the same): the launch is issued, the table is marked `broken`, records nothing further, and the engine walks that batch
-    shape from then on (ConformerCTCTrainStep._table_recorded)."""
+    shape from then on (block_table.BlockTables.recorded)."""
     from mindaudio_amd.train.block_table import BlockTable
 
     tab = BlockTable()
@@ -173,6 +173,8 @@ def test_replayed_backward_launches_the_gradient_buckets_where_the_walked_one_do
 
     from mindaudio_amd import _host
     from mindaudio_amd.train import engine as E
+    from mindaudio_amd.train.block_table import REPLAY
+    from mindaudio_amd.train.plans import ItemTable
 
     def make():
         eng = object.__new__(E.ConformerCTCTrainStep)
@@ -182,8 +184,7 @@ def test_replayed_backward_launches_the_gradient_buckets_where_the_walked_one_do
         eng.layer_names = [["l%d.first" % i, "l%d.last" % i] for i in range(blocks)]
         eng.fp = SimpleNamespace(span=lambda names: (names[0], names[-1]))
         eng.reducer = SimpleNamespace(launch=lambda lo, hi: log.append(("bucket", lo, hi)))
-        item = SimpleNamespace(data_ptr=lambda: 0)
-        eng._dw_cur = dict(layers=[(item, item, 1)] * blocks)
+        eng._dw_cur = SimpleNamespace(layers=[ItemTable([(_lib.ReduceItem(), 1)], "cpu")] * blocks)
         eng._dec_bucket_pending, eng.dec_names = dec_pending, ["dec.first", "dec.last"]
         return eng, log
 
@@ -199,7 +200,7 @@ def test_replayed_backward_launches_the_gradient_buckets_where_the_walked_one_do
         # replayed: the table stands in for the block's launches
         replayed, rlog = make()
         table = SimpleNamespace(backward=lambda li, seed, stream: rlog.append(("launches", li)))
-        ctx = dict(seed=1, b=1, t2=1, mask_rows=None, att_mask=None, pos_all=None, table=dict(state="replay", table=table))
+        ctx = dict(seed=1, b=1, t2=1, mask_rows=None, att_mask=None, pos_all=None, table=SimpleNamespace(state=REPLAY, table=table))
         replayed._blocks_backward_fused(None, None, None, ctx)
     finally:
         _host.swap_pinned(prev)

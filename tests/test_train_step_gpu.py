@@ -502,15 +502,15 @@ def test_blocks_issued_from_the_launch_table_change_no_bit():
         losses, states = [], []
         for k in range(12):
             losses.append(float(eng.step(*cols_of(k, "short" if k in (3, 4, 5) else "chunk" if k >= 9 else "plain"))[0]))
-            tb = eng._dw_plan.get("table")
-            states.append(None if tb is None else tb["state"])
+            tb = eng._dw_plan.table
+            states.append(None if tb is None else tb.state)
         torch.cuda.synchronize()
         if tables:
             # shape A: seen, record, replay | shape B (a new plan): seen, record, replay | shape A again: its plan and table were kept
             # | shape A with (B, T', T') chunk masks (same plan, another table): seen, record, replay
             assert states == ["seen", "replay", "replay"] * 2 + ["replay"] * 3 + ["seen", "replay", "replay"], states
-            assert len(eng._dw_plans) == 2 and len(eng._dw_plan["tables"]) == 2
-            tab = eng._dw_plan["table"]["table"]
+            assert len(eng._dw_plans.plans) == 2 and len(eng._dw_plan.tables) == 2
+            tab = eng._dw_plan.table.table
             per_block = [(tab.calls(False, li), tab.calls(True, li)) for li in range(eng.L)]
             assert all(f == 10 and bw >= 10 for f, bw in per_block), per_block
             assert tab.calls(False, eng.L) == 0
@@ -564,7 +564,7 @@ def test_launch_table_budget_eviction_and_unrecordable_shapes_change_no_bit(monk
 
             def oom_once(g, tape, dpos_all, c):
                 tb = c.get("table")
-                if tb is not None and tb["state"] == "record" and not fired[0]:
+                if tb is not None and tb.state == "record" and not fired[0]:
                     fired[0] = torch.cuda.memory_allocated()  # (what the failed attempt holds: its tape + the table's pinned buffers)
                     raise torch.OutOfMemoryError("injected")
                 return real_bwd(g, tape, dpos_all, c)
@@ -574,13 +574,13 @@ def test_launch_table_budget_eviction_and_unrecordable_shapes_change_no_bit(monk
             warnings.simplefilter("always")
             for k, short in enumerate(order):
                 losses.append(float(eng.step(*cols_of(k, short))[0]))
-                tb = eng._dw_plan.get("table")
-                states.append(None if tb is None else tb["state"])
+                tb = eng._dw_plan.table
+                states.append(None if tb is None else tb.state)
         torch.cuda.synchronize()
         if mode == "budget":
             # shape A is recorded and replays to the end; shape B's recording goes over the budget: given back, walked for good
             assert states[1] == "replay" and states[4] == "walk" and states[5] == "walk" and states[9] == "replay", states
-            assert len(eng._table_bytes) == 1 and any("block_table_max_bytes" in str(w.message) for w in caught)
+            assert len(eng._tables.bytes) == 1 and any("block_table_max_bytes" in str(w.message) for w in caught)
         if mode == "broken":
             monkeypatch.setattr(BT.BlockTable, "_add", real_add)
             assert states[1] == "walk" and states[2] == "walk" and states[4] == "replay", states  # shape A walked for good, shape B recorded
@@ -620,9 +620,9 @@ def test_hybrid_step_from_the_launch_table_changes_no_bit():
             losses.append(float(eng.step(*(c.cuda() if c is not None else None for c in step_cols))[0]))
         torch.cuda.synchronize()
         if tables:
-            tb = eng._dw_plan["table"]
-            tab, L, Ld = tb["table"], eng.L, eng.Ld
-            assert tb["state"] == "replay" and "out" in tb["dec"]
+            tb = eng._dw_plan.table
+            tab, L, Ld = tb.table, eng.L, eng.Ld
+            assert tb.state == "replay" and "out" in tb.dec
             counts = [(tab.calls(False, blk), tab.calls(True, blk)) for blk in range(L, L + Ld + 3)]
             assert all(f > 0 and bw > 0 for f, bw in counts[:Ld + 1]) and counts[Ld + 1][0] > 0 and counts[Ld + 2][0] > 0, counts
         out.append((losses, eng.fp.master.clone()))
@@ -666,8 +666,8 @@ def test_hybrid_table_with_label_lengths_that_change_from_batch_to_batch():
             losses.append(float(eng.step(*(c.cuda() if c is not None else None for c in cols_for(k)))[0]))
         torch.cuda.synchronize()
         if tables:
-            tb = eng._dw_plan["table"]
-            assert tb["state"] == "replay" and tb["dec"]["L1"] == 10  # (recorded at the second sighting: width 10)
+            tb = eng._dw_plan.table
+            assert tb.state == "replay" and tb.dec["L1"] == 10  # (recorded at the second sighting: width 10)
             assert eng._dq is None or eng._dq.n == 0  # nothing queued that no launch will take
         out.append((losses, eng.fp.master.clone()))
     assert out[1][0] == out[0][0]

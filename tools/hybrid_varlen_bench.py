@@ -31,7 +31,7 @@ def main():
                                                positional_dropout_rate=0.1), lsm_weight=0.1).to(dev)
     eng = ConformerCTCTrainStep(model, dropout_rate=0.1, positional_dropout_rate=0.1)
     if a.plans_kept:
-        eng._DEC_LN_PLANS_KEPT = a.plans_kept
+        eng._dec_ln_plans.bound = a.plans_kept
     rng = np.random.RandomState(3)
     out = {}
     for name, widths in (("fixed width 30", [30]), ("21 widths 20..40", list(range(20, 41)))):
