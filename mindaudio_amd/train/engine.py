@@ -21,6 +21,7 @@ from . import kernels as K
 from . import kernels_x32 as X32
 from . import plans
 from .block_table import RECORD, REPLAY, BlockTables
+from .grad_schedule import Buckets, GradSchedule, half_of
 
 _PAD = 64  # every entry of the flat buffers starts on a 64-element boundary (16-byte aligned in bf16 and f32)
 
@@ -184,16 +185,9 @@ def decoder_entries(d, hid, Ld, V):
     return ent
 
 
-def bucket_names(fp, L):
-    layer_names = [[n for n in fp.index if n.startswith("l%d." % i)] for i in range(L)]
-    return layer_names, ["conv1_w", "conv1_b", "conv2_w", "conv2_b", "out_w", "out_b"]
-
-
 def bucket_spans(fp, L):
-    """[(lo, hi)] of the gradient buckets in launch order: blocks L-1 .. 0, then the head and the front."""
-    layer_names, embed_names = bucket_names(fp, L)
-    spans = [fp.span(layer_names[li]) for li in reversed(range(L))]
-    return spans + [fp.span(["after_norm.g", "ctc_b"]), fp.span(embed_names + ["pos_w"])]
+    """[(lo, hi)] of the gradient buckets in launch order (from the tables the step launches from, grad_schedule.Buckets)."""
+    return Buckets(fp, L).ctc_order()
 
 
 class ConformerCTCTrainStep:
@@ -227,9 +221,6 @@ class ConformerCTCTrainStep:
         # The step runs on ONE stream; the only other queue the product uses is RCCL's (own_stream below).  The round-3/4 arm that put
         # the weight-gradient products on a second stream was deleted in this commit, with the scripts that drove it.  The corruption it
         # showed was never explained (DESIGN §"Round 4's two-queue victim", profiles/r06_two_queue_hunt.txt).
-        # _tn_queue: the block's split-K weight-gradient products (dw_group_blocks = 0, or a hidden size that is no multiple of 256),
-        # issued as one grouped launch by _layer_done; _dw_par: which half of the plan's arena the current block uses (_layer_begin)
-        self._tn_queue, self._dw_par = [], 0
         self.K, self.O = (X32, X32) if self.x32 else (K, ops)
         self.model, self.enc = model, enc
         self.dev = next(model.parameters()).device
@@ -246,7 +237,6 @@ class ConformerCTCTrainStep:
         # onto a few hardware queues and RCCL's stream was seen sharing the default stream's queue: its kernels then run in line with
         # the backward pass instead of beside it (profiles/r04_rccl_world1_trace.json).  False: always the caller's stream.
         self.own_stream, self._own = own_stream, None
-        self._dq, self._dq_blocks, self._dq_dec = None, [], None
         # ln_bwd_fused: the four input-gradient products of a block that feed a LayerNorm backward (ff_w1 / ffm_w1 / pw1 / qkv
         # transposed, K = 2048 / 512 / 768) carry that LayerNorm backward and the next branch's dropout backward in their epilogue
         # (ma_gemm_rows_train_bf16 mode 5): 48 launches and 48 bf16 round trips of (M, 256) fewer per step
@@ -267,8 +257,8 @@ class ConformerCTCTrainStep:
         # ... and norm_final's backward of block l - 1 as a second stage of that launch's tail for block l's macaron module (the rows of
         # g it has just finished ARE norm_final's output gradient): 11 LayerNorm-backward launches and round trips of g fewer
         self.ln_final_chained = self.ffn_bwd_one_launch
-        self._dw_direct = self.fused and self.dw_group_blocks > 0 and self.d % 256 == 0 and self.hidden % 256 == 0
-        if self._dw_direct:
+        direct = self.fused and self.dw_group_blocks > 0 and self.d % 256 == 0 and self.hidden % 256 == 0
+        if direct:
             # eight products per block in one direct group: keep a group inside the kernel's item table (a full group is also flushed
             # by DirectGroup.add itself - the decoder's 7 products per layer go into ONE group however many layers it has)
             cap = int(_lib.load().ma_gemm_tn_direct_max_items())
@@ -276,7 +266,7 @@ class ConformerCTCTrainStep:
         # block_tables: from the third step of a batch shape on, a block's launches are issued by ONE C call each way
         # (ma_conformer_block_fwd_train / _bwd_train) from the argument table filled while the second step was walked from Python -
         # same calls, same buffers, same order; 4.2 -> ~1.5 ms of host time per step (train/block_table.py, csrc/block_table.hip)
-        self.block_tables = self.fused and self._dw_direct
+        self.block_tables = self.fused and direct
         # block_table_min_sightings: a shape is recorded at its n-th step (>= 2), replayed from the next one on
         # block_table_max_bytes: device bytes all recorded tables together may pin.  A table keeps every buffer of its step (3-5 GB at the yaml's buckets);
         # the 16 buckets of conformer.yaml together are ~70 GB of the 288.  When the budget is reached the NEW shape stays walked
@@ -314,10 +304,8 @@ class ConformerCTCTrainStep:
         # launches per layer (round 6).  False: one launch per reference cell (what the float32 validation mode always runs).
         self.decoder_fused_launches = True
         self.decoder_embed_row_mask = True  # the embedding's backward skips the padded label rows (their gradient is exactly zero)
-        self._dec_bucket_pending, self._dec_rows = False, 1
-        # does the ENCODER's backward run from its launch table in this step?  (reset by forward_backward, set by the decoder's half)
         # forward_only_fused_front: encoder_forward_train runs both subsampling convolutions in one launch
-        self._enc_replay_now, self.forward_only_fused_front = False, True
+        self.forward_only_fused_front = True
         # built on first use and kept: the transposed and fragment-packed weight copies with the item tables of their batched launches
         # (_wt_plan: None = not built yet, False = a weight the batched transpose does not cover), the packed convolution weights
         # (False = shape not covered)
@@ -337,6 +325,8 @@ class ConformerCTCTrainStep:
         self._build_flat()
         self.flag = self.fp.flag  # zeroed with the gradients at the start of forward_backward
         self.reducer = BucketedAllReduce(self.fp.grad, self.world, self.pg, force_collective)
+        # which weight-gradient products wait in which group, when a group leaves and which buckets go on the wire behind it
+        self.grads = GradSchedule(self, self.fp, self.L, self.dw_group_blocks, direct, K.DirectGroup, K.gemm_tn_partial_group)
         self.refresh_weights()
 
     # (the launch tables' three limits live with their owner; tests and tools set them on the engine)
@@ -344,6 +334,7 @@ class ConformerCTCTrainStep:
     block_table_min_sightings = property(lambda self: self._tables.min_sightings,
                                          lambda self, v: setattr(self._tables, "min_sightings", v))
     block_table_max_blocks = property(lambda self: self._tables.max_blocks, lambda self, v: setattr(self._tables, "max_blocks", v))
+    _dw_direct = property(lambda self: self.grads.direct)  # (are the direct weight-gradient groups in use?)
 
     # ---- flat parameter layout ------------------------------------------------------------------------------------
     def _build_flat(self):
@@ -355,8 +346,6 @@ class ConformerCTCTrainStep:
         # BatchNorm running statistics (buffers, not optimised)
         self.bn_mean = [l.conv_module.norm.running_mean.detach().clone().float() for l in self.enc.encoders]
         self.bn_var = [l.conv_module.norm.running_var.detach().clone().float() for l in self.enc.encoders]
-        self.layer_names, self.embed_names = bucket_names(self.fp, self.L)
-        self.dec_names = [n for n in self.fp.index if n.startswith("dec.") or (n[0] == "d" and n[1].isdigit())]
         self._kv_all = None
         if self.dec is not None and self.Ld > 0:
             fp, d, Ld = self.fp, self.d, self.Ld
@@ -694,52 +683,34 @@ class ConformerCTCTrainStep:
         """norm_final's backward as the second stage of the block above's macaron backward launch (needs the one-launch forms)."""
         return self.ln_final_chained and self.ffn_bwd_one_launch and self.ffn_one_launch and self.fused
 
-    def _ln_partials(self, site):
-        """The arena slice that LayerNorm `site` of the current block writes its per-workgroup partials to (None: immediate sums)."""
+    def _ln_partials(self, site, li):
+        """The arena slice that LayerNorm `site` of block li writes its per-workgroup partials to (None: immediate sums)."""
         plan = self._dw_cur
         if plan is None:
             return None
         o, nbytes, _ = plan.off[site]
-        o += self._dw_par * plan.half
+        o += half_of(li) * plan.half
         return plan.arena[o:o + nbytes].view(torch.float32)
 
     def _dW(self, dy, x, wname, bname):
         """grad[wname] (N, K) += dy^T x ; grad[bname] += column sums of dy.  dy (M, N), x (M, K) bf16."""
-        fp = self.fp
-        plan = self._dw_cur
-        if self._dw_direct and wname[0] == "d" and wname[1].isdigit() and bname is not None and \
+        # (here: the FORM of the product - direct, split-K into the plan's arena, immediate; where a queued one waits, and what that
+        # means for the gradient buckets, is the schedule's: train/grad_schedule.py)
+        fp, plan, gs = self.fp, self._dw_cur, self.grads
+        if gs.direct and wname[0] == "d" and wname[1].isdigit() and bname is not None and \
                 self.K.gemm_tn_direct_ok(dy, x, fp.g(wname)):
-            # a decoder layer's weight gradient: with the other 41 of the decoder in ONE grid at the end of its backward pass
-            # (they were 43 split-K products + 88 reduction launches of ~10 us each: the hybrid step's decoder is launch-bound)
-            if not self.block_tables and dy.shape[0] > 4 * self._dec_rows:
-                # a decoder product over the ENCODER's rows (ca_kv_w: dkv^T memory, 10 200 rows against the decoder's 1 240): in the
-                # decoder's grid its 2 tiles per layer ran 400 us with 244 CUs idle behind them (the grid lasts as long as its longest
-                # tile).  It joins the encoder's first direct group instead - 234 + 12 tiles, still one resident round, every tile with a
-                # full-length contraction; the decoder's gradient bucket goes on the wire behind that group (_dec_bucket_pending).
-                # (Only with the launch tables off: a replayed encoder group holds the operands of the step it was recorded in - the
-                # fused decoder walk keeps its one long operand at a fixed address for that, this per-layer form does not.)
-                if self._dq is None:
-                    self._dq = self.K.DirectGroup()
-                self._dq.add(dy, x, fp.g(wname), fp.g(bname))
-                self._dec_bucket_pending = True
-                return
-            if self._dq_dec is None:
-                self._dq_dec = self.K.DirectGroup()
-            self._dq_dec.add(dy, x, fp.g(wname), fp.g(bname))
+            gs.queue_decoder(dy, x, fp.g(wname), fp.g(bname), long_ok=not self.block_tables)
             return
         if plan is not None and wname[0] == "l" and bname is not None:
-            sfx = wname.split(".", 1)[1]
-            if self._dw_direct and sfx in plans.DW_SUFFIXES and self.K.gemm_tn_direct_ok(dy, x, fp.g(wname)):
-                if self._dq is None:
-                    self._dq = self.K.DirectGroup()
-                self._dq.add(dy, x, fp.g(wname), fp.g(bname))  # issued with the group (_layer_done)
+            blk, sfx = wname.split(".", 1)
+            if gs.direct and sfx in plans.DW_SUFFIXES and self.K.gemm_tn_direct_ok(dy, x, fp.g(wname)):
+                gs.queue_block(dy, x, fp.g(wname), fp.g(bname))
                 return
             if sfx in plan.off:
                 o, nbytes, _ = plan.off[sfx]
-                o += self._dw_par * plan.half
+                o += half_of(int(blk[1:])) * plan.half
                 if self.fused:
-                    # queued: the block's eight products leave as ONE grouped launch when its backward pass is done (_layer_done)
-                    self._tn_queue.append((dy, x, plan.arena[o:o + nbytes]))
+                    gs.queue_splitk(dy, x, plan.arena[o:o + nbytes])
                     return
                 self.K.gemm_tn_partial(dy, x, plan.arena[o:o + nbytes], with_colsum=True)
                 return
@@ -763,7 +734,6 @@ class ConformerCTCTrainStep:
         # out of memory: drop every table, give the memory back, walk this shape from Python for good and run the step again - with the
         # BatchNorm running statistics of before the attempt (the only state a forward pass changes besides the gradients).
         # (snapshot taken by the tables' owner when a shape enters its recording step)
-        self._enc_replay_now = False
         with _host.pinned_stream():
             try:
                 return self._forward_backward(*args)
@@ -775,9 +745,7 @@ class ConformerCTCTrainStep:
                     raise
             # (outside the handler: the traceback and with it every tensor of the failed attempt are gone)
             self._tables.out_of_memory(self._dw_plans.plans.values())
-            self._dq = self._dq_dec = None
-            self._dq_blocks.clear()
-            self._tn_queue.clear()
+            self.grads.begin_step()  # (the queued operands of the failed attempt go too)
             torch.cuda.synchronize(self.dev)
             torch.cuda.empty_cache()
             self._oom_freed_to = torch.cuda.memory_allocated(self.dev)  # (what the retry starts from; read by the tests)
@@ -873,13 +841,7 @@ class ConformerCTCTrainStep:
         xs = xs_pad.to(f32).contiguous()
         enc = self.enc
         fp._grad_alloc.zero_()
-        self._tn_queue.clear()  # (a step that raised mid-backward must not leave stale products / pinned operands behind)
-        if self._dq is not None:
-            self._dq.clear()
-        if self._dq_dec is not None:
-            self._dq_dec.clear()
-        self._dq_blocks.clear()
-        self._dec_bucket_pending = False
+        self.grads.begin_step()
 
         # ================= forward =================
         F = self._encoder_forward(xs, xs_masks, xs_chunk_masks, seed)
@@ -946,7 +908,8 @@ class ConformerCTCTrainStep:
             dcol = self._dX(dy2, "conv2_w")            # (B*T2*F2, 9c) bf16
             dact1 = K.col2im_relu(dcol, act1)
         K.conv1_dw(dact1, xs, enc.cmvn_mean, enc.cmvn_istd, fp.g("conv1_w"), fp.g("conv1_b"))
-        self._embed_done()
+        self.grads.front_done()
+        assert self.grads.idle()  # every queued product has left, every bucket is on the wire
         return loss
 
     # ---- the blocks, one launch per reference cell ------------------------------------------------------------------------------
@@ -996,12 +959,11 @@ class ConformerCTCTrainStep:
         K = self.K
         seed, b, t2, mask_rows, att_mask, pos_all, pd = c["seed"], c["b"], c["t2"], c["mask_rows"], c["att_mask"], c["pos_all"], self.p_drop
         for li in reversed(range(L)):
-            self._layer_begin(li)
             pre = "l%d." % li
             W, P, G = (lambda n, pre=pre: fp.w(pre + n)), (lambda n, pre=pre: fp.p(pre + n)), (lambda n, pre=pre: fp.g(pre + n))
             T = tape[li]
             K.layernorm_bwd(T["final_in"], P("norm_final.g"), g, g, G("norm_final.g"), G("norm_final.b"), accumulate=False,
-                            partials=self._ln_partials("norm_final"))
+                            partials=self._ln_partials("norm_final", li))
             self._ffn_bwd(g, T["ff"], "ff", "norm_ff", pre, seed, li, 6)
             # conv module
             C = T["conv"]
@@ -1013,7 +975,7 @@ class ConformerCTCTrainStep:
             self._dW(dy, C["a"], pre + "pw1_w", pre + "pw1_b")
             da = self._dX(dy, pre + "pw1_w")
             K.layernorm_bwd(C["x_in"], P("norm_conv.g"), da, g, G("norm_conv.g"), G("norm_conv.b"), row_scale=mask_rows,
-                            partials=self._ln_partials("norm_conv"))
+                            partials=self._ln_partials("norm_conv", li))
             # MHSA
             A = T["mha"]
             do = K.dropout_bwd(g, 1.0, pd, seed, self._salt(li, 2))
@@ -1025,9 +987,9 @@ class ConformerCTCTrainStep:
             self._dW(dqkv, A["a"], pre + "qkv_w", pre + "qkv_b")
             da = self._dX(dqkv, pre + "qkv_w")
             K.layernorm_bwd(A["x_in"], P("norm_mha.g"), da, g, G("norm_mha.g"), G("norm_mha.b"),
-                            partials=self._ln_partials("norm_mha"))
+                            partials=self._ln_partials("norm_mha", li))
             self._ffn_bwd(g, T["ffm"], "ffm", "norm_ff_macaron", pre, seed, li, 0)
-            self._layer_done(li)
+            self.grads.block_done(li, self._dw_cur)
 
     # ---- the blocks, fused: dense layers on fragment-packed weights with their element-wise neighbours in the epilogue ---------------
     def _blocks_forward_fused(self, x, c):
@@ -1117,10 +1079,7 @@ class ConformerCTCTrainStep:
             stream = _host.current_stream_ptr()
             for li in reversed(range(L)):
                 tb.table.backward(li, seed, stream)
-                # (what _layer_done / _flush_direct do besides launching: the finished groups' gradient buckets go on the wire)
-                self._dq_blocks.append(li)
-                if len(self._dq_blocks) >= self.dw_group_blocks or li == 0:
-                    self._launch_group_buckets()
+                self.grads.block_done(li, self._dw_cur, replayed=True)  # (the finished groups' gradient buckets go on the wire)
             return
         if tb is not None:
             with tb.table.recording(seed):
@@ -1137,7 +1096,6 @@ class ConformerCTCTrainStep:
         for li in reversed(range(L)):
             if rec is not None:
                 rec.segment(True, li)
-            self._layer_begin(li)
             pre = "l%d." % li
             P, G, PK = (lambda n, pre=pre: fp.p(pre + n)), (lambda n, pre=pre: fp.g(pre + n)), (lambda n, pre=pre: self.pk[pre + n])
             T = tape[li]
@@ -1145,71 +1103,69 @@ class ConformerCTCTrainStep:
             def ffn_bwd(dy, F, key, ln, nxt, chain=None):
                 self._dW(dy, F["h"], pre + key + "_w2", pre + key + "_b2")
                 if self.ffn_bwd_one_launch:  # dh -> du -> da -> the LayerNorm backward: one launch (F["u"] holds gk)
-                    du, dy_next = K.ffn_train_bwd(dy, PK(key + ".ft"), hid, F["u"], F["x_in"], P(ln + ".g"), g, self._ln_partials(ln),
+                    du, dy_next = K.ffn_train_bwd(dy, PK(key + ".ft"), hid, F["u"], F["x_in"], P(ln + ".g"), g, self._ln_partials(ln, li),
                                                   nxt=nxt, chain=chain)
                     self._dW(du, F["a"], pre + key + "_w1", pre + key + "_b1")
                     return dy_next
                 du = K.dense_act_drop_bwd(dy, PK(key + "_w2.tk"), hid, F["u"], pd, seed, self._salt(li, 0 if key == "ffm" else 6))
                 self._dW(du, F["a"], pre + key + "_w1", pre + key + "_b1")
                 if self.ln_bwd_fused:  # da = du . W_1 and the LayerNorm backward (+ the next branch's dropout backward): one launch
-                    return K.dense_lnbwd(du, PK(key + "_w1.tr"), hid, F["x_in"], P(ln + ".g"), g, self._ln_partials(ln), nxt=nxt)
+                    return K.dense_lnbwd(du, PK(key + "_w1.tr"), hid, F["x_in"], P(ln + ".g"), g, self._ln_partials(ln, li), nxt=nxt)
                 da = K.dense_plain(du, PK(key + "_w1.tr"), d, hid)
                 if nxt is None:
-                    K.layernorm_bwd(F["x_in"], P(ln + ".g"), da, g, G(ln + ".g"), G(ln + ".b"), partials=self._ln_partials(ln))
+                    K.layernorm_bwd(F["x_in"], P(ln + ".g"), da, g, G(ln + ".g"), G(ln + ".b"), partials=self._ln_partials(ln, li))
                     return None
                 return K.layernorm_bwd_next(F["x_in"], P(ln + ".g"), da, g, G(ln + ".g"), G(ln + ".b"), nxt,
-                                            partials=self._ln_partials(ln))[1]
+                                            partials=self._ln_partials(ln, li))[1]
 
             if chained_dy is not None:  # norm_final's backward ran in block li + 1's macaron launch (ln_final_chained)
                 dy, chained_dy = chained_dy, None
             else:
                 _, dy = K.layernorm_bwd_next(T["final_in"], P("norm_final.g"), g, g, G("norm_final.g"), G("norm_final.b"),
                                              (0.5, pd, seed, self._salt(li, 7), None), accumulate=False,
-                                             partials=self._ln_partials("norm_final"))
+                                             partials=self._ln_partials("norm_final", li))
             do = ffn_bwd(dy, T["ff"], "ff", "norm_ff", (1.0, pd, seed, self._salt(li, 3), mask_rows))
             # conv module
             C = T["conv"]
             self._dW(do, C["w"], pre + "pw2_w", pre + "pw2_b")
             dwv = K.dense_plain(do, PK("pw2_w.tk"), d, d)
             dy = K.convmid_bwd(dwv, C["y"], C["z"], C["stats"], b, t2, P("dw_w"), P("bn_g"), P("bn_b"), G("dw_w"), G("dw_b"), G("bn_g"),
-                               G("bn_b"), partials=self._ln_partials("convmid"))
+                               G("bn_b"), partials=self._ln_partials("convmid", li))
             self._dW(dy, C["a"], pre + "pw1_w", pre + "pw1_b")
             if self.ln_bwd_fused:
-                do = K.dense_lnbwd(dy, PK("pw1_w.tr"), 2 * d, C["x_in"], P("norm_conv.g"), g, self._ln_partials("norm_conv"),
+                do = K.dense_lnbwd(dy, PK("pw1_w.tr"), 2 * d, C["x_in"], P("norm_conv.g"), g, self._ln_partials("norm_conv", li),
                                    nxt=(1.0, pd, seed, self._salt(li, 2), None), row_scale=mask_rows)
             else:
                 da = K.dense_plain(dy, PK("pw1_w.tr"), d, 2 * d)
                 _, do = K.layernorm_bwd_next(C["x_in"], P("norm_conv.g"), da, g, G("norm_conv.g"), G("norm_conv.b"),
                                              (1.0, pd, seed, self._salt(li, 2), None), row_scale=mask_rows,
-                                             partials=self._ln_partials("norm_conv"))
+                                             partials=self._ln_partials("norm_conv", li))
             # MHSA
             A = T["mha"]
             self._dW(do, A["ctx"], pre + "o_w", pre + "o_b")
             dctx = K.dense_plain(do, PK("o_w.tk"), d, d)
             # (dpos / du / dv: the partial sums stay in the plan's workspace and are added by the block's reduction launch)
             dqkv = K.attention_bwd(A["qkv"], pos_all[:, li * d:(li + 1) * d], P("u"), P("v"), att_mask, A["ctx"], dctx, A["lse"], b, t2,
-                                   None, None, None, self.heads, d // self.heads, ws=self._dw_cur.att_ws[self._dw_par])
+                                   None, None, None, self.heads, d // self.heads, ws=self._dw_cur.att_ws[half_of(li)])
             self._dW(dqkv, A["a"], pre + "qkv_w", pre + "qkv_b")
             if self.ln_bwd_fused:
-                dy = K.dense_lnbwd(dqkv, PK("qkv_w.tr"), 3 * d, A["x_in"], P("norm_mha.g"), g, self._ln_partials("norm_mha"),
+                dy = K.dense_lnbwd(dqkv, PK("qkv_w.tr"), 3 * d, A["x_in"], P("norm_mha.g"), g, self._ln_partials("norm_mha", li),
                                    nxt=(0.5, pd, seed, self._salt(li, 1), None))
             else:
                 da = K.dense_plain(dqkv, PK("qkv_w.tr"), d, 3 * d)
                 _, dy = K.layernorm_bwd_next(A["x_in"], P("norm_mha.g"), da, g, G("norm_mha.g"), G("norm_mha.b"),
-                                             (0.5, pd, seed, self._salt(li, 1), None), partials=self._ln_partials("norm_mha"))
+                                             (0.5, pd, seed, self._salt(li, 1), None), partials=self._ln_partials("norm_mha", li))
             if self._chain_final() and li > 0:
                 # block li - 1's norm_final: its partials go to THAT block's half of the arena (block li + 1's sums, the last user of
                 # that half, were launched on this stream long ago)
                 prev = "l%d." % (li - 1)
-                self._dw_par ^= 1
-                part_prev = self._ln_partials("norm_final")
-                self._dw_par ^= 1
+                part_prev = self._ln_partials("norm_final", li - 1)
                 chained_dy = ffn_bwd(dy, T["ffm"], "ffm", "norm_ff_macaron", None,
                                      chain=(tape[li - 1]["final_in"], fp.p(prev + "norm_final.g"), part_prev,
                                             (0.5, pd, seed, self._salt(li - 1, 7), None)))
             else:
                 ffn_bwd(dy, T["ffm"], "ffm", "norm_ff_macaron", None)
-            self._layer_done(li)
+            self.grads.block_done(li, self._dw_cur)
 
     def _decoder_forward_backward(self, mem_bf, enc_mask2d, b, t2, ys_in_pad, ys_out_pad, ys_sub_masks, ys_masks, gscale,
                                   seed, tb=None):
@@ -1227,7 +1183,7 @@ class ConformerCTCTrainStep:
         # Does the ENCODER's backward run from its launch table in this step?  Its first direct group then already holds the product
         # the decoder's walk would queue (_decoder_walk_fused: the memory-side weight gradient) - also when the decoder itself is
         # walked from Python because this batch's label length is not the recorded one, which is the common case on real data.
-        self._enc_replay_now = tb is not None and tb.state == REPLAY
+        self.grads.decoder_begin(md, enc_replayed=tb is not None and tb.state == REPLAY)
         if tb is not None and not self.len_norm and tb.state in (RECORD, REPLAY):
             dtb = tb.dec
             if tb.state == RECORD:
@@ -1251,10 +1207,9 @@ class ConformerCTCTrainStep:
         tgt, tmask = dtb["tgt"].copy_(ys_out_pad.reshape(-1)), dtb["tmask"].copy_(ys_masks.reshape(-1))
         if tb.state == RECORD:
             with tb.table.recording(seed):
-                dtb["out"] = self._decoder_walk(mem_bf, enc_mask2d, b_, t2, L1, toks, sub, pe, tgt, tmask, gscale, seed, tb.table,
-                                                dtb["ls"])
-            dtb["bucket_deferred"] = self._dec_bucket_pending  # (the replayed steps launch the bucket where the walked one did)
-            stats, d_mem = dtb["out"]
+                stats, d_mem, dtb["bucket_deferred"] = self._decoder_walk(mem_bf, enc_mask2d, b_, t2, L1, toks, sub, pe, tgt, tmask,
+                                                                         gscale, seed, tb.table, dtb["ls"])
+            dtb["out"] = stats, d_mem
         else:
             table, stream, L, Ld = tb.table, _host.current_stream_ptr(), self.L, self.Ld
             table.forward(L + Ld, seed, stream)
@@ -1268,16 +1223,14 @@ class ConformerCTCTrainStep:
             for li in reversed(range(Ld)):
                 table.backward(L + li, seed, stream)
             table.backward(L + Ld, seed, stream)
-            self._dec_bucket_pending = bool(dtb.get("bucket_deferred"))
-            if self.dec_names and not self._dec_bucket_pending:
-                self.reducer.launch(*self.fp.span(self.dec_names))
+            self.grads.decoder_done(replayed=True, deferred=dtb["bucket_deferred"])
             stats, d_mem = dtb["out"]
         self.last_acc = stats[1] / stats[2]
         return stats[0] / b_, d_mem
 
     def _decoder_walk(self, mem_bf, enc_mask2d, b, t2, L1, toks, sub, pe, tgt, tmask, gscale, seed, rec, ls):
         """The decoder call by call; `rec`: the block table being filled (segments as _decoder_forward_backward lists them).
-        Returns (loss_att, d_memory) - or (stats, d_memory) to the recording caller, which forms the loss from the kept `stats`."""
+        Returns (loss_att, d_memory) - or (stats, d_memory, bucket deferred?) to the recording caller, which forms the loss itself."""
         fp, d, dec = self.fp, self.d, self.dec
         ops, K = self.O, self.K  # bf16 throughput kernels or their float32 validation twins
         tt = _host.torch()        # (allocations of a recorded step stay referenced by the table)
@@ -1293,7 +1246,6 @@ class ConformerCTCTrainStep:
         xscale = math.sqrt(d)
         seg = (lambda backward, blk: rec.segment(backward, blk)) if rec is not None else (lambda backward, blk: None)
         L, Ld = self.L, self.Ld
-        self._dec_rows = md  # (what _dW compares a product's contraction length with)
         if self.fused and self.dec_fused and self.decoder_fused_launches:
             return self._decoder_walk_fused(mem_bf, emask, b, t2, L1, toks, sub, pe, tgt, tmask, gscale, seed, rec, ls, seg)
         seg(False, L + Ld)
@@ -1378,16 +1330,11 @@ class ConformerCTCTrainStep:
             K.layernorm_bwd(T["x0"], P("norm1.g"), DX(dqkv, "sa_qkv_w"), g, G("norm1.g"), G("norm1.b"), eps=eps)
         seg(True, L + Ld)
         K.embed_bwd(toks, g, fp.g("dec.embed"), xscale, pp, seed, salt(-1, 0))
-        if self._dq_dec is not None:  # the decoder layers' weight gradients: one grid
-            self._dq_dec.launch()
-            self._dq_dec.clear()
+        deferred = self.grads.decoder_done()  # the decoder layers' weight gradients: one grid, then (unless deferred) the bucket
         if rec is not None:
             rec.segment(None, 0)
             rec.keep.append(tape)
-        if self.dec_names:
-            self.reducer.launch(*fp.span(self.dec_names))
-        if rec is not None:
-            return stats, d_mem
+            return stats, d_mem, deferred
         self.last_acc = stats[1] / stats[2]
         return stats[0] / (stats[2] if self.len_norm else b), d_mem
 
@@ -1411,7 +1358,6 @@ class ConformerCTCTrainStep:
         dk = d // self.heads
         scale = 1.0 / dk
         md, m = b * L1, b * t2
-        self._dec_rows = md
         hid = self.dec_hidden
         RELU = _lib.ACT_RELU
         salt = lambda li, site: self._salt(100 + li, site)  # noqa: E731
@@ -1476,7 +1422,7 @@ class ConformerCTCTrainStep:
         # dkv_all lives with the batch shape's plan, at ONE address for walked, recorded and replayed steps alike: the encoder's
         # first direct group reads it (below), and that group may be a recorded launch of another step's
         plan = self._dw_cur
-        merge = plan is not None and self._dw_direct
+        merge = plan is not None and self.grads.direct
         if merge:
             dkv_all = plan.dkv_all
             if dkv_all is None or tuple(dkv_all.shape) != (m, Ld * 2 * d):
@@ -1529,28 +1475,17 @@ class ConformerCTCTrainStep:
         # straggler beside the decoder's 1 240-row products, _dW)
         ops.gemm(dkv_all, self.wt["dec.ca_kv_all"], out_dtype=f32, out=d_mem)
         if merge:
-            # (a replayed encoder backward has the item in its recorded group - same operands, same addresses; queueing it here as
-            # well would leave it in a group nobody launches, with operands that die with this step)
-            if not self._enc_replay_now:
-                if self._dq is None:
-                    self._dq = K.DirectGroup()
-                self._dq.add(dkv_all, mem_bf, self._kv_all["gw"], self._kv_all["gb"])
-            self._dec_bucket_pending = True
+            self.grads.queue_decoder_long(dkv_all, mem_bf, self._kv_all["gw"], self._kv_all["gb"])
         else:
             K.gemm_tn(dkv_all, mem_bf, self._kv_all["gw"], colsum=self._kv_all["gb"])
         # (tmask: the padded label positions - their rows of g are exactly zero, the label mask keeps them out of every valid position)
         K.embed_bwd(toks, g, fp.g("dec.embed"), xscale, pp, seed, salt(-1, 0), row_keep=tmask if self.decoder_embed_row_mask else None)
         dlp.sums.reduce("decoder LayerNorm sums")
-        if self._dq_dec is not None:  # the decoder layers' weight gradients: one grid
-            self._dq_dec.launch()
-            self._dq_dec.clear()
+        deferred = self.grads.decoder_done()  # (deferred: the bucket leaves behind the encoder's first direct group)
         if rec is not None:
             rec.segment(None, 0)
             rec.keep.append(tape)
-        if self.dec_names and not self._dec_bucket_pending:  # (pending: behind the encoder's first direct group, _flush_direct)
-            self.reducer.launch(*fp.span(self.dec_names))
-        if rec is not None:
-            return stats, d_mem
+            return stats, d_mem, deferred
         self.last_acc = stats[1] / stats[2]
         return stats[0] / (stats[2] if self.len_norm else b), d_mem
 
@@ -1572,57 +1507,7 @@ class ConformerCTCTrainStep:
         self._dW(du, T["a"], pre + key + "_w1", pre + key + "_b1")
         da = self._dX(du, pre + key + "_w1")
         K.layernorm_bwd(T["x_in"], fp.p(pre + ln + ".g"), da, g, fp.g(pre + ln + ".g"), fp.g(pre + ln + ".b"),
-                        partials=self._ln_partials(ln))
-
-    # ---- data-parallel gradient reduction ----------------------------------------------------------------------------
-    def _layer_done(self, li):
-        """Backward of block li is complete: its slice of the flat gradient can go on the wire while earlier blocks
-        are still being differentiated."""
-        plan = self._dw_cur
-        if plan is not None:  # the split sums of this block's weight gradients, one launch
-            if self._dw_direct:
-                # the block's partial sums (LayerNorm, depthwise convolution, attention biases) now; its weight-gradient products
-                # leave with the group, and the group's gradient buckets behind them
-                plan.layers[li].reduce("reduce_splits_batch")
-                self._dq_blocks.append(li)
-                if len(self._dq_blocks) >= self.dw_group_blocks or li == 0:
-                    self._flush_direct()
-                return
-            if self._tn_queue:
-                self.K.gemm_tn_partial_group(self._tn_queue, with_colsum=True)  # the block's eight products: one grid
-                self._tn_queue.clear()
-            plan.layers[li].reduce("reduce_splits_batch")
-        self.reducer.launch(*self.fp.span(self.layer_names[li]))
-
-    def _flush_direct(self):
-        """The group's direct weight-gradient products as one grid, then its gradient buckets."""
-        if self._dq is not None:
-            self._dq.launch()
-        self._launch_group_buckets()
-        if self._dq is not None:
-            self._dq.clear()
-
-    def _launch_group_buckets(self):
-        """The finished group's gradient buckets go on the wire, then the deferred decoder bucket (walked and replayed alike)."""
-        for b in self._dq_blocks:
-            self.reducer.launch(*self.fp.span(self.layer_names[b]))
-        self._launch_deferred_dec_bucket()
-        self._dq_blocks.clear()
-
-    def _launch_deferred_dec_bucket(self):
-        """The decoder's gradient bucket when some of its weight gradients ride in the encoder's first direct group (_dW)."""
-        if self._dec_bucket_pending:
-            self._dec_bucket_pending = False
-            if self.dec_names:
-                self.reducer.launch(*self.fp.span(self.dec_names))
-
-    def _layer_begin(self, li):
-        """Backward of block li starts: its partial sums go to arena half li & 1, which block li + 2 used."""
-        self._dw_par = li & 1
-
-    def _embed_done(self):
-        self.reducer.launch(*self.fp.span(["after_norm.g", "ctc_b"]))
-        self.reducer.launch(*self.fp.span(self.embed_names + ["pos_w"]))
+                        partials=self._ln_partials(ln, li))
 
     # ---- one optimizer step ------------------------------------------------------------------------------------------
     @torch.no_grad()

@@ -6,6 +6,7 @@ import numpy as np
 import torch
 
 from .. import _host, _lib
+from .grad_schedule import half_of
 
 
 # The device side of one batched launch (ma_transpose_batch_bf16, ma_pack_batch_bf16, ma_reduce_splits_batch_f32): the packed item
@@ -127,13 +128,13 @@ def block_sums_plan(cache, m, t2, fp, dev, L, d, heads, ks, fused, ln_bwd_fused,
     total += (att_bytes + 255) // 256 * 256
     off["dpos_all"] = (total, t2 * L * d * 4, 0)
     total += (t2 * L * d * 4 + 255) // 256 * 256
-    # Two copies of the arena, used by alternate blocks (_layer_begin): block li's partials and block li - 1's never share bytes.
+    # Two copies of the arena, used by alternate blocks (grad_schedule.half_of): block li's partials and block li - 1's never share bytes.
     # (Needed when the sums ran on a second stream; kept on the one stream so that every launch keeps its addresses.)
     half = (total + 255) // 256 * 256
     arena = cache.arena_for(2 * half)
     layers = []
     for li in range(L):
-        items, base = [], arena.data_ptr() + (li & 1) * half
+        items, base = [], arena.data_ptr() + half_of(li) * half
         add = lambda *a, **kw: items.append(_reduce_item(*a, **kw))  # noqa: E731
         for sfx in () if direct else DW_SUFFIXES:
             g = fp.g("l%d.%s" % (li, sfx))

@@ -160,61 +160,6 @@ def test_a_seed_mismatch_while_recording_marks_the_table_instead_of_raising():
         tab.segment(None, 0)
 
 
-@pytest.mark.parametrize("dec_pending", [False, True])
-@pytest.mark.parametrize("blocks,group", [(12, 6), (12, 5), (2, 6), (7, 3), (1, 1)])
-def test_replayed_backward_launches_the_gradient_buckets_where_the_walked_one_does(monkeypatch, blocks, group, dec_pending):
-    """N > 1: a finished group's gradient buckets go on the wire (reducer.launch) behind its direct weight-gradient products.  The
-    replayed backward pass (one C call per block) must issue the same spans at the same points as _layer_done / _flush_direct do
-    when the blocks are walked - checked here on the host logic alone (no launches: the library and the table are stand-ins).
-    dec_pending (round 6): the decoder's long-contraction weight gradients ride in the encoder's FIRST direct group, so the
-    decoder's bucket must leave behind that group - once, in the walked and in the replayed pass alike."""
-    import ctypes
-    from types import SimpleNamespace
-
-    from mindaudio_amd import _host
-    from mindaudio_amd.train import engine as E
-    from mindaudio_amd.train.block_table import REPLAY
-    from mindaudio_amd.train.plans import ItemTable
-
-    def make():
-        eng = object.__new__(E.ConformerCTCTrainStep)
-        log = []
-        eng.L, eng.d, eng.hidden, eng.K, eng.p_drop = blocks, 256, 2048, None, 0.1
-        eng.dw_group_blocks, eng._dw_direct, eng._dq, eng._dq_blocks = group, True, None, []
-        eng.layer_names = [["l%d.first" % i, "l%d.last" % i] for i in range(blocks)]
-        eng.fp = SimpleNamespace(span=lambda names: (names[0], names[-1]))
-        eng.reducer = SimpleNamespace(launch=lambda lo, hi: log.append(("bucket", lo, hi)))
-        eng._dw_cur = SimpleNamespace(layers=[ItemTable([(_lib.ReduceItem(), 1)], "cpu")] * blocks)
-        eng._dec_bucket_pending, eng.dec_names = dec_pending, ["dec.first", "dec.last"]
-        return eng, log
-
-    prev = _host.swap_pinned(ctypes.c_void_p(0))
-    try:
-        # walked: what _layer_done does after each block's launches
-        walked, wlog = make()
-        stub = SimpleNamespace(ma_reduce_splits_batch_f32=lambda *a: wlog.append(("block", a[2])) or 0)
-        monkeypatch.setattr(E._lib, "load", lambda: stub)
-        for li in reversed(range(blocks)):
-            wlog.append(("launches", li))
-            walked._layer_done(li)
-        # replayed: the table stands in for the block's launches
-        replayed, rlog = make()
-        table = SimpleNamespace(backward=lambda li, seed, stream: rlog.append(("launches", li)))
-        ctx = dict(seed=1, b=1, t2=1, mask_rows=None, att_mask=None, pos_all=None, table=SimpleNamespace(state=REPLAY, table=table))
-        replayed._blocks_backward_fused(None, None, None, ctx)
-    finally:
-        _host.swap_pinned(prev)
-    assert [e for e in wlog if e[0] != "block"] == rlog
-    assert sum(1 for e in rlog if e[0] == "bucket") == blocks + int(dec_pending) and walked._dq_blocks == replayed._dq_blocks == []
-    if dec_pending:
-        dec = [i for i, e in enumerate(rlog) if e == ("bucket", "dec.first", "dec.last")]
-        first_group = min(group, blocks)
-        launches = [i for i, e in enumerate(rlog) if e[0] == "launches"]
-        # exactly once, behind the first group's last block and before the next block's launches
-        assert len(dec) == 1 and dec[0] > launches[first_group - 1] and (len(launches) == first_group or dec[0] < launches[first_group])
-        assert not walked._dec_bucket_pending and not replayed._dec_bucket_pending
-
-
 def test_replay_dispatches_typed_calls_and_reports_the_failing_entry():
     """No GPU needed: entries whose arguments the entry points reject (NULL buffers) make the replay stop at that entry with the
     entry point's own status - which shows that the generated typed call reached the right function with the recorded words."""

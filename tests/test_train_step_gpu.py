@@ -668,7 +668,59 @@ def test_hybrid_table_with_label_lengths_that_change_from_batch_to_batch():
         if tables:
             tb = eng._dw_plan.table
             assert tb.state == "replay" and tb.dec["L1"] == 10  # (recorded at the second sighting: width 10)
-            assert eng._dq is None or eng._dq.n == 0  # nothing queued that no launch will take
+            assert eng.grads.idle()  # nothing queued that no launch will take
+        out.append((losses, eng.fp.master.clone()))
+    assert out[1][0] == out[0][0]
+    assert torch.equal(out[1][1], out[0][1])
+
+
+@pytest.mark.parametrize("tables", [False, True])
+@pytest.mark.parametrize("hybrid", [False, True])
+def test_a_step_that_raises_in_the_middle_of_its_backward_pass_leaves_no_trace(monkeypatch, hybrid, tables):
+    """A host exception in the backward pass of block 0 (a Python error raised by the convolution module's wrapper before it calls the
+    library - no kernel is made to fail): by then block 1's weight-gradient products, the hybrid step's memory-side product and its
+    deferred decoder bucket wait for a group that never leaves.  The same step run again and one more step give, bit for bit, the
+    losses and masters of an engine that never failed - with the launch tables off, and with them on and the exception in the
+    RECORDING step (the step after it is replayed from the table recorded by the second attempt)."""
+    from mindaudio_amd.train import kernels as K
+    from mindaudio_amd.train.engine import ConformerCTCTrainStep
+
+    def cols_of(k):  # (another batch of the same shape every step)
+        b4 = batch(vocab=96, seed=12 + k, shorter=(0, 30 - k, 61 + 2 * k), ylens=(9, 6 - k % 2, 4 + k % 3))
+        cols = _hybrid_cols(96, b4) if hybrid else (b4[0], b4[1], None, None, None, None, b4[2], None, None, b4[3], None)
+        return tuple(c.cuda() if c is not None else None for c in cols)
+
+    real, calls, fail_at = K.convmid_bwd, [0], [0]
+
+    def convmid_bwd(*a, **kw):
+        calls[0] += 1
+        if calls[0] == fail_at[0]:
+            raise RuntimeError("injected")
+        return real(*a, **kw)
+    monkeypatch.setattr(K, "convmid_bwd", convmid_bwd)
+    out = []
+    for fail in (False, True):
+        if hybrid:
+            model = _hybrid_setup(blocks=2, dblocks=2)[3]
+            model.decoder.dropout_rate, model.decoder.positional_dropout_rate = 0.1, 0.1
+        else:
+            model = build(seed=9)[2]
+        eng = ConformerCTCTrainStep(model, base_lr=1e-3, warmup_steps=2, dropout_rate=0.1, positional_dropout_rate=0.1)
+        assert eng.block_tables and eng.L == 2
+        eng.block_tables = tables
+        # blocks are differentiated L-1 .. 0, one call per block: the 4th call is block 0 of the second step (the recording one)
+        calls[0], fail_at[0] = 0, 4 if fail else -1
+        losses = []
+        for k in range(3):
+            if fail and k == 1:
+                with pytest.raises(RuntimeError, match="injected"):
+                    eng.step(*cols_of(k))
+                assert calls[0] == 4 and (getattr(eng._dw_plan.table, "state", None) == "record") == tables
+            losses.append(float(eng.step(*cols_of(k))[0]))
+        torch.cuda.synchronize()
+        assert calls[0] == (4 if tables else 6) + 2 * int(fail)  # (a replayed step does not come through the wrapper)
+        if tables:
+            assert eng._dw_plan.table.state == "replay"
         out.append((losses, eng.fp.master.clone()))
     assert out[1][0] == out[0][0]
     assert torch.equal(out[1][1], out[0][1])
@@ -717,7 +769,7 @@ def test_no_second_stream_option_and_full_direct_groups_flush():
 
 def test_split_k_weight_gradients_equal_the_direct_groups():
     """dw_group_blocks=0 (or a hidden size that is no multiple of 256): a block's eight weight-gradient products leave as ONE split-K
-    grouped launch when its backward pass is done (engine._tn_queue -> _layer_done) and the block's batched sum adds the partials up;
+    grouped launch when its backward pass is done (grad_schedule: queue_splitk -> block_done) and the block's batched sum adds the partials up;
     the default issues them with the full contraction per tile in the direct groups.  Dropout ON: the forward passes are the same
     launches, the backward passes differ only in the float32 summation order of the weight-gradient contraction - well inside the
     bounds this file applies to the larger fused / per-cell difference.  The split-K arm is run-to-run bit-reproducible."""
@@ -733,7 +785,7 @@ def test_split_k_weight_gradients_equal_the_direct_groups():
         else:
             assert eng._dw_direct
         loss = eng.forward_backward(xs.cuda(), ys.cuda(), sub.cuda(), ys_lens.cuda(), grad_scale=8.0)
-        assert not eng._tn_queue  # every queued product has left with its block
+        assert eng.grads.idle()  # every queued product has left with its block
         res.append((float(loss), eng.fp.grad.clone(), eng))
     (l0, g0, e0), (l1, g1, _), (l2, g2, _) = res
     assert abs(l0 - l1) <= 2e-3 * abs(l0), (l0, l1)
