@@ -1543,6 +1543,46 @@ int ma_tasnet_decode_f32(const float* score, const float* mixture_w, int64_t M, 
 int ma_si_snr_pairwise(const float* source, const float* estimate, const int64_t* lengths, int64_t B, int32_t C, int64_t T, double* out,
                        ma_stream_t stream);
 
+/* ---- Bidirectional LSTM layer, inference (mindaudio/models/deepspeech2.py:119-187: nn.LSTM(bidirectional=True, has_bias=True), the
+ * two directions summed) --------------------------------------------------------------------------------------------------------------
+ * Cell, PyTorch gate order i, f, g, o:  gates = x W_ih^T + b_ih + h W_hh^T + b_hh,  c' = sigmoid(f) c + sigmoid(i) tanh(g),
+ * h' = sigmoid(o) tanh(c'),  h_0 = c_0 = 0.  The reverse direction walks t = T - 1 .. 0 and writes at index t; there are no lengths:
+ * both directions run over all T frames.  out[t] = h_fwd[t] + h_bwd[t].
+ * Rounding points: x, W_ih, W_hh and the h that is fed back are bf16 MFMA operands (round to nearest even); projections, gate sums, c
+ * and the output are float32, accumulation is float32; out_bf16 is the rounding of out_f32.  No atomics: the same bits run to run.
+ *
+ * ma_lstm_pack_f32: one layer's weights, both directions stacked: w_ih (2, 4H, K), w_hh (2, 4H, H), b_ih / b_hh (2, 4H) float32 ->
+ *   wih_bf16 (2, 4H, Kpad) bf16 with zero columns K .. Kpad - 1, whh_packed (2 * 4H * H bf16, in the step kernel's fragment order),
+ *   bias (2, 4H) float32 = b_ih + b_hh.  Outputs 16-byte aligned.
+ * ma_lstm_bidir_bf16: x (T, B, Kpad) bf16 -> out_f32 (T, B, H) float32 and out_bf16 (T, B, H) bf16 (NULL: left out).
+ *   Per chunk of time_chunk steps: one ma_gemm_bf16 per direction (the input projection, float32, bias folded in), then ONE LAUNCH PER
+ *   TIME STEP from a host loop inside this call - each serves both directions and does the h W_hh^T product on MFMA, the gate
+ *   arithmetic, the c update and the stores; stream order is the only synchronisation between steps (no persistent kernel, no
+ *   inter-workgroup waiting).  dir_mask: 1 forward only, 2 reverse only (the other half counts as zero), 3 both.
+ *   c_final (2, B, H) float32, optional: the cell state after the last step of each direction.
+ *   workspace >= ma_lstm_workspace_bytes(T, B, H, time_chunk), 16-byte aligned: MA_ERR_WORKSPACE otherwise.
+ * Shapes: T >= 1, B >= 1 (rows beyond B are never read), H % 64 == 0 (64 .. 4096), Kpad % 64 == 0: MA_ERR_UNSUPPORTED otherwise;
+ * MA_ERR_INVALID_ARG for a null or misaligned pointer, a size < 1 or a dir_mask outside 1 .. 3; a failed launch returns MA_ERR_LAUNCH
+ * and ends the loop. */
+int64_t ma_lstm_workspace_bytes(int64_t T, int64_t B, int32_t H, int64_t time_chunk);
+int ma_lstm_pack_f32(const float* w_ih, const float* w_hh, const float* b_ih, const float* b_hh, int32_t K, int32_t Kpad, int32_t H,
+                     void* wih_bf16, void* whh_packed, float* bias, ma_stream_t stream);
+int ma_lstm_bidir_bf16(const void* x, int64_t T, int64_t B, int32_t Kpad, int32_t H, const void* wih_bf16, const void* whh_packed,
+                       const float* bias, int32_t dir_mask, int64_t time_chunk, float* out_f32, void* out_bf16, float* c_final,
+                       void* workspace, int64_t workspace_bytes, ma_stream_t stream);
+
+/* ---- DeepSpeech2 (mindaudio/models/deepspeech2.py) outside its LSTM layers and GEMMs ---------------------------------------------------
+ * ma_ds2_conv1_bf16: Conv2d(1 -> 32, (41, 11), stride (2, 2), pad (20, 5), no bias) + BatchNorm2d in affine form + tanh.
+ *   x (B, F, T) float32; wt (451, 32) float32 = the weight transposed to [frequency tap * 11 + time tap][channel]; scale / shift (32).
+ *   out: the (T1 + 10, B, Fpad, 32) bf16 activation of the second convolution (time-major, channel-last), F1 = (F - 1) / 2 + 1,
+ *   T1 = (T - 1) / 2 + 1; only frames 5 .. 5 + T1 - 1 and frequency rows 10 .. 10 + F1 - 1 are written, the caller keeps the rest zero.
+ *   float32 accumulation in tap order.  F <= 256, B <= 65535, Fpad >= F1 + 20: MA_ERR_UNSUPPORTED otherwise.
+ * ma_ds2_softmax_f32: probs (B, T, C) = softmax over the C classes of logits (T, B, row stride ld): PredictWithSoftmax
+ *   (examples/deepspeech2/eval.py:17-33). */
+int ma_ds2_conv1_bf16(const float* x, int64_t B, int32_t F, int64_t T, const float* wt, const float* scale, const float* shift,
+                      int32_t Fpad, void* out, ma_stream_t stream);
+int ma_ds2_softmax_f32(const float* logits, int64_t ld, int64_t T, int64_t B, int32_t C, float* probs, ma_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

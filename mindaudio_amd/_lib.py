@@ -410,6 +410,12 @@ PROTOTYPES = {
     "ma_gln_apply_bf16": (ctypes.c_int, [vp, i64, i64, i32, vp, vp, vp]),
     "ma_tasnet_decode_f32": (ctypes.c_int, [vp, vp, i64, i64, i32, i32, vp, i32, i32, vp, vp]),
     "ma_si_snr_pairwise": (ctypes.c_int, [vp, vp, vp, i64, i32, i64, vp, vp]),
+    # ---- LSTM layer, DeepSpeech2 ----
+    "ma_lstm_workspace_bytes": (i64, [i64, i64, i32, i64]),
+    "ma_lstm_pack_f32": (ctypes.c_int, [vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp]),
+    "ma_lstm_bidir_bf16": (ctypes.c_int, [vp, i64, i64, i32, i32, vp, vp, vp, i32, i64, vp, vp, vp, vp, i64, vp]),
+    "ma_ds2_conv1_bf16": (ctypes.c_int, [vp, i64, i32, i64, vp, vp, vp, i32, vp, vp]),
+    "ma_ds2_softmax_f32": (ctypes.c_int, [vp, i64, i64, i64, i32, vp, vp]),
 }
 
 FRAME_POWER_TILE, FRAME_POWER_MAX_RATIO, CHANNEL_MEAN_MAX = 16, 32, 8  # MA_FRAME_POWER_TILE, MA_FRAME_POWER_MAX_RATIO, MA_CHANNEL_MEAN_MAX

@@ -1,0 +1,433 @@
+// Bidirectional LSTM layer, inference (mindaudio/models/deepspeech2.py BatchRNN: nn.LSTM(bidirectional=True, has_bias=True), the two
+// directions SUMMED).  Contract: include/mindaudio_amd.h.
+//
+// One layer = the input projection of a time chunk (ma_gemm_bf16, float32 out, b_ih + b_hh as its bias) followed by ONE LAUNCH PER
+// TIME STEP of lstm_step_kernel, issued from the host loop of ma_lstm_bidir_bf16.  The stream order between those launches is the only
+// synchronisation: no workgroup ever waits for another one (no grid barrier, no flags, no cooperative launch, no atomics).
+//
+// Step kernel.  gates (B, 4H) = h_{s-1} (B, H) . W_hh^T, PyTorch gate order i, f, g, o.  A tile is 16 batch rows x 16 hidden units
+// with ALL FOUR gate rows of those units: four 16 x 16 accumulators of v_mfma_f32_16x16x32_bf16, A operand = h (row = batch), B operand =
+// W_hh (column = hidden unit).  The C/D map (column = lane & 15, row = 4 (lane >> 4) + register) puts the four gates of one
+// (batch row, hidden unit) into the same lane and register, so the gate arithmetic needs no lane movement and no memory: add the
+// projection, two sigmoids and two tanhs, update c (float32, in place, one owner per element), store h.
+//   grid = (H / 16 hidden slices, directions, ceil(B / 64)), 4 waves per workgroup, wave w runs the cell of batch rows 64 z + 16 w ..+15.
+// W_hh is packed once (ma_lstm_pack_f32) in fragment order: for (direction, slice, k-step of 32, gate) the 64 lanes' 8 bf16 are 1 KiB
+// contiguous, so a wave reads the four gate fragments of a k-step as one 4 KiB run, straight into registers; h is read from its
+// (B, H) bf16 image, 16 bytes per lane.  Two forms:
+//   lstm_step_ksplit_kernel (H / 32 a multiple of 4): K is split over the four waves, each runs a quarter of the k-steps for all four
+//     batch tiles, so the workgroup reads its 128 KB slice of W_hh once; the partial sums meet in LDS (48 KB, one workgroup barrier).
+//   lstm_step_kernel (any H % 64 == 0): each wave runs all of K for its own tile; no LDS, no barrier.
+// Both issue the next operand block's loads before the current block's MFMAs and load the cell's inputs (projection, c) before the
+// k loop: a step's grid is one workgroup per CU at B = 128, i.e. one wave per SIMD, so latency is hidden inside the wave or not at all.
+//
+// Rounding points: x, W_ih, W_hh and the fed-back h are bf16 MFMA operands (round to nearest even); the projection, the gate sums,
+// c, h before it is fed back, and the layer output are float32; accumulation is float32.
+//
+// Direction sum: out[t] = h_fwd[t] + h_bwd[t].  Step s serves t = s (forward) and t = T - 1 - s (reverse).  The direction that reaches
+// a t first stores its h into out_f32[t]; the one that reaches it later (a later launch) adds its own and stores the float32 sum and
+// its bf16 rounding (the next GEMM's operand).  For odd T both meet at t = (T - 1) / 2 in ONE launch: the forward half goes to out_f32,
+// the reverse half to a (B, H) side buffer and one pointwise launch joins them.  a + b == b + a in float32, so the order never shows.
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include <stdint.h>
+
+#include "../../include/mindaudio_amd.h"
+
+#include "device_common.h"
+#include "launch.h"
+
+namespace ma {
+
+constexpr int kLstmThreads = 256;
+constexpr int kLstmSlice = 16;     // hidden units of a workgroup (x 4 gate rows)
+constexpr int kLstmRowsPerWg = 64;  // batch rows of a workgroup: 16 per wave
+
+enum : int { kLstmFirst = 0, kLstmSecond = 1, kLstmAlone = 2, kLstmTie = 3 };
+
+struct LstmStep {
+  const float* proj[2];  // this step's (B, 4H) projection rows per direction
+  const uint16_t* whh;   // packed, both directions
+  const uint16_t* h_in;  // (2, B, H) bf16: h_{s-1}
+  uint16_t* h_out;       // (2, B, H) bf16: h_s
+  float* c;              // (2, B, H)
+  float* out_f32[2];     // row block t of (T, B, H) per direction
+  uint16_t* out_bf16[2];
+  float* tie;            // (B, H)
+  int32_t mode[2];
+  int32_t dir0;          // direction of blockIdx.y == 0
+  int32_t B, H;
+};
+
+__device__ __forceinline__ float sigmoid_acc(float v) { return 1.0f / (1.0f + expf(-v)); }
+
+// What the cell of one 16 x 16 tile reads besides the product, in the C/D layout (batch row b0 + 4 (lane >> 4) + r, hidden unit
+// 16 sl + (lane & 15)): the four projections, c and - for the direction that reaches a frame second - the other direction's h.
+// None of it depends on the product, so it is loaded BEFORE the k loop and its latency hides behind it.  Rows beyond B read nothing.
+struct LstmCellIn {
+  float gate[4][4];  // [gate][r]
+  float c[4], prev[4];
+};
+__device__ __forceinline__ LstmCellIn lstm_cell_load(const LstmStep& p, int dir, int sl, int b0, int lane) {
+  const int H = p.H;
+  const int64_t dir_off = (int64_t)dir * p.B * H;
+  const int j = sl * kLstmSlice + (lane & 15);
+  LstmCellIn in;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const int b = b0 + 4 * (lane >> 4) + r;
+    const bool ok = b < p.B;
+    const float* pr = p.proj[dir] + (int64_t)(ok ? b : 0) * 4 * H + j;
+    const int64_t e = (int64_t)(ok ? b : 0) * H + j;
+#pragma unroll
+    for (int g = 0; g < 4; ++g) in.gate[g][r] = ok ? pr[g * H] : 0.0f;
+    in.c[r] = ok ? p.c[dir_off + e] : 0.0f;
+    in.prev[r] = (ok && p.mode[dir] == kLstmSecond) ? p.out_f32[dir][e] : 0.0f;
+  }
+  return in;
+}
+
+// The cell: gate sums, two sigmoids, two tanhs, c, h and the stores.  Rows beyond B store nothing.
+__device__ __forceinline__ void lstm_cell_store(const LstmStep& p, int dir, int sl, int b0, int lane, const f32x4 (&acc)[4],
+                                                const LstmCellIn& in) {
+  const int H = p.H;
+  const int64_t dir_off = (int64_t)dir * p.B * H;
+  const int j = sl * kLstmSlice + (lane & 15);
+  const int mode = p.mode[dir];
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const int b = b0 + 4 * (lane >> 4) + r;
+    if (b >= p.B) continue;
+    const float gi = acc[0][r] + in.gate[0][r];
+    const float gf = acc[1][r] + in.gate[1][r];
+    const float gg = acc[2][r] + in.gate[2][r];
+    const float go = acc[3][r] + in.gate[3][r];
+    const int64_t e = (int64_t)b * H + j;
+    const float cn = sigmoid_acc(gf) * in.c[r] + sigmoid_acc(gi) * tanhf(gg);
+    const float h = sigmoid_acc(go) * tanhf(cn);
+    p.c[dir_off + e] = cn;
+    p.h_out[dir_off + e] = f2bf(h);
+    if (mode == kLstmFirst) {
+      p.out_f32[dir][e] = h;
+    } else if (mode == kLstmTie) {
+      p.tie[e] = h;
+    } else {
+      const float v = mode == kLstmSecond ? in.prev[r] + h : h;
+      p.out_f32[dir][e] = v;
+      if (p.out_bf16[dir]) p.out_bf16[dir][e] = f2bf(v);
+    }
+  }
+}
+
+// KB k-steps of operands: the h fragment and the four gate fragments of W_hh per k-step
+template <int KB>
+struct LstmOperands {
+  bf16x8 a[KB];
+  bf16x8 w[KB][4];
+};
+
+// Each wave runs all of K for its own batch tile (the form for an H / 32 that is no multiple of 4; launched with KB = 2).  KB =
+// k-steps per operand block.  Two blocks are in registers: the loads of block i + 1 (5 KB of 16 bytes per lane) are issued before the
+// MFMAs of block i, so that the L2 latency of the weight stream hides behind the previous block's MFMAs.
+template <int KB>
+__global__ __launch_bounds__(kLstmThreads) void lstm_step_kernel(const LstmStep p) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int b0 = ((int)blockIdx.z * 4 + wave) * 16;
+  if (b0 >= p.B) return;  // (no barrier anywhere in this kernel)
+  const int dir = p.dir0 + (int)blockIdx.y;
+  const int H = p.H, nk = H / 32, ns = H / kLstmSlice;
+  const int sl = blockIdx.x;
+  const int64_t dir_off = (int64_t)dir * p.B * H;
+
+  // rows beyond B are not read: their lanes take row 0's operand instead, and their results are never stored (an MFMA row depends
+  // on its own A row only)
+  const int arow = b0 + (lane & 15);
+  const uint16_t* hp = p.h_in + dir_off + (int64_t)(arow < p.B ? arow : 0) * H + 8 * (lane >> 4);
+  const uint16_t* wp = p.whh + ((((int64_t)dir * ns + sl) * nk * 4) * 64 + lane) * 8;
+
+  f32x4 acc[4];
+#pragma unroll
+  for (int g = 0; g < 4; ++g) acc[g] = f32x4{0.f, 0.f, 0.f, 0.f};
+  auto load = [&](LstmOperands<KB>& o, int kk0) __attribute__((always_inline)) {
+#pragma unroll
+    for (int u = 0; u < KB; ++u) {
+      o.a[u] = *reinterpret_cast<const bf16x8*>(hp + (kk0 + u) * 32);
+#pragma unroll
+      for (int g = 0; g < 4; ++g) o.w[u][g] = *reinterpret_cast<const bf16x8*>(wp + ((int64_t)(kk0 + u) * 4 + g) * 512);
+    }
+  };
+  auto mma = [&](const LstmOperands<KB>& o) __attribute__((always_inline)) {
+#pragma unroll
+    for (int u = 0; u < KB; ++u)
+#pragma unroll
+      for (int g = 0; g < 4; ++g) acc[g] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(o.a[u], o.w[u][g], acc[g], 0, 0, 0);
+  };
+  LstmOperands<KB> cur, nxt;
+  load(cur, 0);
+  const LstmCellIn in = lstm_cell_load(p, dir, sl, b0, lane);
+  for (int kk = KB; kk < nk; kk += KB) {  // (nk % KB == 0: the launcher's choice of KB)
+    load(nxt, kk);
+    mma(cur);
+    cur = nxt;
+  }
+  mma(cur);
+  lstm_cell_store(p, dir, sl, b0, lane, acc, in);
+}
+
+constexpr int kLstmPartialFloats = 4 * 3 * 16 * 64;  // [source wave][other tile][gate * 4 + register][lane]: 48 KB
+
+// The same step with K SPLIT OVER THE FOUR WAVES (H / 32 a multiple of 4): wave w runs the k-steps [w nk / 4, (w + 1) nk / 4) for all
+// four batch tiles of the workgroup, so the workgroup reads its 128 KB slice of W_hh once instead of once per wave.  The partial
+// accumulators of the three tiles a wave does not own go through LDS; after the workgroup's one barrier wave w adds the four
+// partials of tile w in wave order and runs the cell.  Tiles beyond B compute on row 0's operand and store nothing.  KB = k-steps
+// per operand block, two blocks in registers as above.
+template <int KB>
+__global__ __launch_bounds__(kLstmThreads) void lstm_step_ksplit_kernel(const LstmStep p) {
+  __shared__ float part[kLstmPartialFloats];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int z0 = (int)blockIdx.z * kLstmRowsPerWg;
+  const int dir = p.dir0 + (int)blockIdx.y;
+  const int H = p.H, nk = H / 32, ns = H / kLstmSlice, nkw = nk / 4;
+  const int sl = blockIdx.x;
+  const int64_t dir_off = (int64_t)dir * p.B * H;
+  const uint16_t* hp[4];
+#pragma unroll
+  for (int t = 0; t < 4; ++t) {
+    const int row = z0 + 16 * t + (lane & 15);
+    hp[t] = p.h_in + dir_off + (int64_t)(row < p.B ? row : 0) * H + 8 * (lane >> 4) + wave * nkw * 32;
+  }
+  const uint16_t* wp = p.whh + (((((int64_t)dir * ns + sl) * nk + wave * nkw) * 4) * 64 + lane) * 8;
+
+  f32x4 acc[4][4];  // [tile][gate]
+#pragma unroll
+  for (int t = 0; t < 4; ++t)
+#pragma unroll
+    for (int g = 0; g < 4; ++g) acc[t][g] = f32x4{0.f, 0.f, 0.f, 0.f};
+  struct Operands {
+    bf16x8 a[KB][4];
+    bf16x8 w[KB][4];
+  };
+  auto load = [&](Operands& o, int kk0) __attribute__((always_inline)) {
+#pragma unroll
+    for (int u = 0; u < KB; ++u) {
+#pragma unroll
+      for (int g = 0; g < 4; ++g) o.w[u][g] = *reinterpret_cast<const bf16x8*>(wp + ((int64_t)(kk0 + u) * 4 + g) * 512);
+#pragma unroll
+      for (int t = 0; t < 4; ++t) o.a[u][t] = *reinterpret_cast<const bf16x8*>(hp[t] + (kk0 + u) * 32);
+    }
+  };
+  auto mma = [&](const Operands& o) __attribute__((always_inline)) {
+#pragma unroll
+    for (int u = 0; u < KB; ++u)
+#pragma unroll
+      for (int t = 0; t < 4; ++t)
+#pragma unroll
+        for (int g = 0; g < 4; ++g) acc[t][g] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(o.a[u][t], o.w[u][g], acc[t][g], 0, 0, 0);
+  };
+  Operands cur, nxt;
+  load(cur, 0);
+  const LstmCellIn in = lstm_cell_load(p, dir, sl, z0 + 16 * wave, lane);
+  for (int kk = KB; kk < nkw; kk += KB) {  // (nkw % KB == 0: the launcher's choice of KB)
+    load(nxt, kk);
+    mma(cur);
+    cur = nxt;
+  }
+  mma(cur);
+
+  // tile t's partial from wave s != t sits in slot (t - s - 1) & 3 (0 .. 2) of wave s's block
+  f32x4 own[4];
+#pragma unroll
+  for (int t = 0; t < 4; ++t) {
+    if (t == wave) {
+#pragma unroll
+      for (int g = 0; g < 4; ++g) own[g] = acc[t][g];
+    } else {
+      float* dst = part + ((wave * 3 + ((t - wave - 1) & 3)) * 16) * 64 + lane;
+#pragma unroll
+      for (int g = 0; g < 4; ++g)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) dst[(g * 4 + r) * 64] = acc[t][g][r];
+    }
+  }
+  __syncthreads();  // (within the workgroup; every wave arrives: nothing returns before this line)
+  f32x4 tot[4];
+#pragma unroll
+  for (int g = 0; g < 4; ++g) tot[g] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int s = 0; s < 4; ++s) {  // wave order = K order
+    if (s == wave) {
+#pragma unroll
+      for (int g = 0; g < 4; ++g) tot[g] += own[g];
+    } else {
+      const float* src = part + ((s * 3 + ((wave - s - 1) & 3)) * 16) * 64 + lane;
+#pragma unroll
+      for (int g = 0; g < 4; ++g)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) tot[g][r] += src[(g * 4 + r) * 64];
+    }
+  }
+  lstm_cell_store(p, dir, sl, z0 + 16 * wave, lane, tot, in);
+}
+
+// the middle frame of an odd T: out = out (forward half) + tie (reverse half)
+__global__ __launch_bounds__(256) void lstm_tie_kernel(float* __restrict__ out, uint16_t* __restrict__ out_bf, const float* __restrict__ tie,
+                                                       int64_t n) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const float v = out[i] + tie[i];
+  out[i] = v;
+  if (out_bf) out_bf[i] = f2bf(v);
+}
+
+// W_ih (2, 4H, K) f32 -> (2, 4H, Kpad) bf16 with zero columns K .. Kpad - 1; bias = b_ih + b_hh
+__global__ __launch_bounds__(256) void lstm_pack_ih_kernel(const float* __restrict__ w, const float* __restrict__ b_ih,
+                                                           const float* __restrict__ b_hh, int K, int Kpad, int64_t rows,
+                                                           uint16_t* __restrict__ out, float* __restrict__ bias) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i < rows) bias[i] = b_ih[i] + b_hh[i];
+  if (i >= rows * Kpad) return;
+  const int64_t r = i / Kpad;
+  const int k = (int)(i - r * Kpad);
+  out[i] = k < K ? f2bf(w[r * K + k]) : (uint16_t)0;
+}
+
+// W_hh (2, 4H, H) f32 -> fragment order: [direction][slice][k-step][gate][lane][8]
+__global__ __launch_bounds__(256) void lstm_pack_hh_kernel(const float* __restrict__ w, int H, int64_t groups, uint16_t* __restrict__ out) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;  // one 8-element fragment
+  if (i >= groups) return;
+  const int nk = H / 32, ns = H / kLstmSlice;
+  const int lane = (int)(i & 63);
+  int64_t q = i >> 6;
+  const int g = (int)(q & 3);
+  q >>= 2;
+  const int kk = (int)(q % nk);
+  q /= nk;
+  const int sl = (int)(q % ns);
+  const int dir = (int)(q / ns);
+  const float* src = w + ((int64_t)dir * 4 * H + (int64_t)g * H + sl * kLstmSlice + (lane & 15)) * H + kk * 32 + 8 * (lane >> 4);
+  u32x4 v;
+  v[0] = pack2_bf16(src[0], src[1]);
+  v[1] = pack2_bf16(src[2], src[3]);
+  v[2] = pack2_bf16(src[4], src[5]);
+  v[3] = pack2_bf16(src[6], src[7]);
+  *reinterpret_cast<u32x4*>(out + i * 8) = v;
+}
+
+static int64_t align256(int64_t v) { return (v + 255) & ~(int64_t)255; }
+
+struct LstmWs {
+  int64_t h, c, tie, proj, total;  // byte offsets; proj holds 2 x (chunk * B, 4H) float32
+};
+static LstmWs lstm_ws(int64_t B, int64_t H, int64_t chunk) {
+  LstmWs w;
+  w.h = 0;
+  w.c = w.h + align256(2 * 2 * B * H * 2);
+  w.tie = w.c + align256(2 * B * H * 4);
+  w.proj = w.tie + align256(B * H * 4);
+  w.total = w.proj + 2 * align256(chunk * B * 4 * H * 4);
+  return w;
+}
+
+static bool lstm_shape_ok(int64_t T, int64_t B, int64_t Kpad, int64_t H) {
+  return T >= 1 && B >= 1 && H >= 64 && H % 64 == 0 && H <= 4096 && Kpad >= 64 && Kpad % 64 == 0 && B <= 65535 * (int64_t)kLstmRowsPerWg &&
+         B * 4 * H <= 0x7fffffff;
+}
+
+}  // namespace ma
+
+using namespace ma;
+
+extern "C" {
+
+int64_t ma_lstm_workspace_bytes(int64_t T, int64_t B, int32_t H, int64_t time_chunk) {
+  if (T < 1 || B < 1 || H < 1 || time_chunk < 1) return MA_ERR_INVALID_ARG;
+  if (!lstm_shape_ok(T, B, 64, H)) return MA_ERR_UNSUPPORTED;
+  return lstm_ws(B, H, time_chunk < T ? time_chunk : T).total;
+}
+
+int ma_lstm_pack_f32(const float* w_ih, const float* w_hh, const float* b_ih, const float* b_hh, int32_t K, int32_t Kpad, int32_t H,
+                     void* wih_bf16, void* whh_packed, float* bias, ma_stream_t stream) {
+  if (!w_ih || !w_hh || !b_ih || !b_hh || !wih_bf16 || !whh_packed || !bias || K < 1 || Kpad < K || H < 1) return MA_ERR_INVALID_ARG;
+  if (!lstm_shape_ok(1, 1, Kpad, H)) return MA_ERR_UNSUPPORTED;
+  if ((reinterpret_cast<uintptr_t>(wih_bf16) | reinterpret_cast<uintptr_t>(whh_packed) | reinterpret_cast<uintptr_t>(bias)) & 15)
+    return MA_ERR_INVALID_ARG;
+  const int64_t rows = 2 * 4 * (int64_t)H, n_ih = rows * Kpad, groups = rows * H / 8;
+  MA_LAUNCH(lstm_pack_ih_kernel, dim3((unsigned)((n_ih + 255) / 256)), dim3(256), 0, (hipStream_t)stream, w_ih, b_ih, b_hh, K, Kpad, rows,
+            reinterpret_cast<uint16_t*>(wih_bf16), bias);
+  MA_LAUNCH(lstm_pack_hh_kernel, dim3((unsigned)((groups + 255) / 256)), dim3(256), 0, (hipStream_t)stream, w_hh, H, groups,
+            reinterpret_cast<uint16_t*>(whh_packed));
+  return MA_OK;
+}
+
+int ma_lstm_bidir_bf16(const void* x, int64_t T, int64_t B, int32_t Kpad, int32_t H, const void* wih_bf16, const void* whh_packed,
+                       const float* bias, int32_t dir_mask, int64_t time_chunk, float* out_f32, void* out_bf16, float* c_final,
+                       void* workspace, int64_t workspace_bytes, ma_stream_t stream) {
+  if (!x || !wih_bf16 || !whh_packed || !bias || !out_f32 || !workspace || T < 1 || B < 1 || Kpad < 1 || H < 1 || time_chunk < 1 ||
+      dir_mask < 1 || dir_mask > 3)
+    return MA_ERR_INVALID_ARG;
+  if (!lstm_shape_ok(T, B, Kpad, H)) return MA_ERR_UNSUPPORTED;
+  if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(wih_bf16) | reinterpret_cast<uintptr_t>(whh_packed) |
+       reinterpret_cast<uintptr_t>(bias) | reinterpret_cast<uintptr_t>(workspace)) & 15)
+    return MA_ERR_INVALID_ARG;
+  const int64_t chunk = time_chunk < T ? time_chunk : T;
+  const LstmWs ws = lstm_ws(B, H, chunk);
+  if (workspace_bytes < ws.total) return MA_ERR_WORKSPACE;
+  hipStream_t st = (hipStream_t)stream;
+  char* base = reinterpret_cast<char*>(workspace);
+  uint16_t* hbuf = reinterpret_cast<uint16_t*>(base + ws.h);
+  float* c = reinterpret_cast<float*>(base + ws.c);
+  float* projbuf[2] = {reinterpret_cast<float*>(base + ws.proj),
+                       reinterpret_cast<float*>(base + ws.proj + (ws.total - ws.proj) / 2)};
+  const int64_t bh = B * H, g4 = 4 * (int64_t)H;
+  if (ensure_init() != MA_OK) return MA_ERR_LAUNCH;
+  // h_0 = c_0 = 0 (only the first of the two h images is read by step 0)
+  if (hipMemsetAsync(hbuf, 0, (size_t)(2 * bh * 2), st) != hipSuccess) return MA_ERR_LAUNCH;
+  if (hipMemsetAsync(c, 0, (size_t)(2 * bh * 4), st) != hipSuccess) return MA_ERR_LAUNCH;
+
+  const uint16_t* xb = reinterpret_cast<const uint16_t*>(x);
+  const uint16_t* wih = reinterpret_cast<const uint16_t*>(wih_bf16);
+  uint16_t* obf = reinterpret_cast<uint16_t*>(out_bf16);
+  const bool both = dir_mask == 3;
+  const dim3 grid((unsigned)(H / kLstmSlice), both ? 2u : 1u, (unsigned)((B + kLstmRowsPerWg - 1) / kLstmRowsPerWg));
+
+  ma_gemm_epilogue_t epi = ma_gemm_epilogue_t{};
+  epi.alpha = 1.0f;
+  for (int64_t s0 = 0; s0 < T; s0 += chunk) {
+    const int64_t n = T - s0 < chunk ? T - s0 : chunk;
+    const int64_t t0[2] = {s0, T - s0 - n};  // first frame of this chunk per direction (the reverse one walks it backwards)
+    for (int d = 0; d < 2; ++d) {
+      if (!(dir_mask & (1 << d))) continue;
+      epi.bias = bias + d * g4;
+      const int rc = ma_gemm_bf16(xb + t0[d] * B * Kpad, Kpad, wih + d * g4 * Kpad, Kpad, projbuf[d], g4, n * B, g4, Kpad, &epi, stream);
+      if (rc != MA_OK) return rc;
+    }
+    for (int64_t s = s0; s < s0 + n; ++s) {
+      LstmStep p;
+      const int64_t t[2] = {s, T - 1 - s};
+      p.whh = reinterpret_cast<const uint16_t*>(whh_packed);
+      p.h_in = hbuf + (s & 1) * 2 * bh;
+      p.h_out = hbuf + ((s + 1) & 1) * 2 * bh;
+      p.c = c;
+      p.tie = reinterpret_cast<float*>(base + ws.tie);
+      p.dir0 = dir_mask == 2 ? 1 : 0;
+      p.B = (int32_t)B;
+      p.H = H;
+      for (int d = 0; d < 2; ++d) {
+        p.proj[d] = projbuf[d] + (t[d] - t0[d]) * B * g4;
+        p.out_f32[d] = out_f32 + t[d] * bh;
+        p.out_bf16[d] = obf ? obf + t[d] * bh : nullptr;
+        const int64_t other = T - 1 - s;  // the step at which the other direction serves this frame
+        p.mode[d] = !both ? kLstmAlone : s < other ? kLstmFirst : s > other ? kLstmSecond : d == 0 ? kLstmFirst : kLstmTie;
+      }
+      if ((H / 32) % 16 == 0) MA_LAUNCH(lstm_step_ksplit_kernel<4>, grid, dim3(kLstmThreads), 0, st, p);
+      else if ((H / 32) % 8 == 0) MA_LAUNCH(lstm_step_ksplit_kernel<2>, grid, dim3(kLstmThreads), 0, st, p);
+      else if ((H / 32) % 4 == 0) MA_LAUNCH(lstm_step_ksplit_kernel<1>, grid, dim3(kLstmThreads), 0, st, p);
+      else MA_LAUNCH(lstm_step_kernel<2>, grid, dim3(kLstmThreads), 0, st, p);
+      if (both && s == T - 1 - s)
+        MA_LAUNCH(lstm_tie_kernel, dim3((unsigned)((bh + 255) / 256)), dim3(256), 0, st, p.out_f32[0], p.out_bf16[0], p.tie, bh);
+    }
+  }
+  if (c_final && hipMemcpyAsync(c_final, c, (size_t)(2 * bh * 4), hipMemcpyDeviceToDevice, st) != hipSuccess) return MA_ERR_LAUNCH;
+  return MA_OK;
+}
+
+}  // extern "C"

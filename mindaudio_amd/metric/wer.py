@@ -3,14 +3,19 @@
 Pure host logic (scoring of decoded token lists)."""
 
 
-def wer(ref, hyp):
-    if not ref:
-        raise ValueError("The reference utterance must not be empty.")
-    # rolling one-row Levenshtein table: prev[j] = distance(ref[:i-1], hyp[:j])
+def edit_distance(ref, hyp):
+    """Levenshtein distance between two sequences (strings or token lists)."""
+    # rolling one-row table: prev[j] = distance(ref[:i-1], hyp[:j])
     prev = list(range(len(hyp) + 1))
     for i, r in enumerate(ref, 1):
         cur = [i] + [0] * len(hyp)
         for j, h in enumerate(hyp, 1):
             cur[j] = prev[j - 1] if r == h else 1 + min(prev[j - 1], cur[j - 1], prev[j])
         prev = cur
-    return prev[-1] / len(ref)
+    return prev[-1]
+
+
+def wer(ref, hyp):
+    if not ref:
+        raise ValueError("The reference utterance must not be empty.")
+    return edit_distance(ref, hyp) / len(ref)

@@ -1,4 +1,5 @@
 from .conformer import ConformerEncoder  # noqa: F401
 from .conv_tasnet import ConvTasNet  # noqa: F401
+from .deepspeech2 import DeepSpeechModel  # noqa: F401
 from .ecapatdnn import EcapaTDNN  # noqa: F401
 from .ecapatdnn import Classifier  # noqa: F401

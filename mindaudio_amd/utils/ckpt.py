@@ -301,6 +301,32 @@ def _is_conv_tasnet(module):
     return type(module).__name__ == "ConvTasNet"
 
 
+def convert_deepspeech2_names(ref_params):
+    """Reference DeepSpeechModel (mindaudio/models/deepspeech2.py) parameter names -> mindaudio_amd.models.DeepSpeechModel's state
+    dict.  The module keeps the reference's cell names and layouts (conv.conv1.weight, conv.bn1.gamma / beta / moving_mean /
+    moving_variance, conv.conv2.weight, conv.bn2.*, RNN.lstms.<k>.weight_ih_l0 / weight_hh_l0 / bias_ih_l0 / bias_hh_l0 and their
+    `_reverse` twins, fc.module.weight), so only wrapper prefixes and optimizer state are removed.  MaskConv registers its cells a second
+    time in `conv.module_list.<i>`: those duplicates are ignored.
+    Not verified against a file MindSpore wrote (none can be produced here): the names, and the per-direction split of nn.LSTM's
+    weights, are inferred from the cell definitions."""
+    out = {}
+    for name, arr in ref_params.items():
+        n = _strip(name)
+        if _SKIP.match(n) or ".module_list." in n:
+            continue
+        out[n] = arr
+    return out
+
+
+def deepspeech2_to_reference_names(state, prefix=""):
+    """Inverse of `convert_deepspeech2_names`: the names and layouts are already the reference's."""
+    return {prefix + k: (v.detach().float().cpu().numpy() if hasattr(v, "detach") else np.asarray(v)) for k, v in state.items()}
+
+
+def _is_deepspeech2(module):
+    return type(module).__name__ == "DeepSpeechModel"
+
+
 def read_epoch_num(path):
     """`int(param_dict.get("epoch_num", 0))` of examples/conformer/train.py:121 - the number of finished epochs the reference's
     ModelCheckpoint appends to every file (`append_info=[{"epoch_num": ...}]`, train.py:157-163)."""
@@ -316,6 +342,8 @@ def load_mindspore_checkpoint(module, path, strict=True):
     raw = read_mindspore_ckpt(path)
     if _is_conv_tasnet(module):
         params = convert_conv_tasnet_names(raw)
+    elif _is_deepspeech2(module):
+        params = convert_deepspeech2_names(raw)
     else:
         params = convert_ecapa_names(raw) if _is_ecapa(module) else convert_names(raw)
     own = module.state_dict()
