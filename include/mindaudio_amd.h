@@ -1583,6 +1583,52 @@ int ma_ds2_conv1_bf16(const float* x, int64_t B, int32_t F, int64_t T, const flo
                       int32_t Fpad, void* out, ma_stream_t stream);
 int ma_ds2_softmax_f32(const float* logits, int64_t ld, int64_t T, int64_t B, int32_t C, float* probs, ma_stream_t stream);
 
+/* ---- Layer-pipelined unidirectional LSTM stack, inference (mindaudio/models/tasnet.py:106-108: nn.LSTM(N, hidden_size, num_layers,
+ * bidirectional=False)) -----------------------------------------------------------------------------------------------------------------
+ * The cell and its gate order are those of the block above; h_0 = c_0 = 0 in every layer; layer l >= 1 reads layer l - 1's h.
+ * Rounding points: x, W_ih, W_hh and every h that feeds a product (a layer's own h_{t-1} and the lower layer's h_t) are bf16 MFMA
+ * operands (round to nearest even); gate sums, c, the output and h_final are float32, accumulation is float32 in a fixed order;
+ * out_bf16 is the rounding of out_f32.  No atomics: the same bits run to run.
+ *
+ * ma_lstm_stack_pack_f32: ONE layer's weights: w_ih (4H, K), w_hh (4H, H), b_ih / b_hh (4H) float32 -> packed: 4H * (Kpad + H) bf16
+ *   holding [W_ih | W_hh] along K in the step kernel's fragment order [slice of 16 units][k-step of 32][gate][lane][8], the columns
+ *   K .. Kpad - 1 zero; bias (4H) float32 = b_ih + b_hh.  Layer 0 has K = the input width; a layer above it has K = Kpad = H.
+ *   Outputs 16-byte aligned.
+ * ma_lstm_stack_bf16: x (T, B, Kpad) bf16 -> out_f32 (T, B, H) float32 and out_bf16 (T, B, H) bf16 (NULL: left out) of the LAST layer.
+ *   packed / bias: HOST arrays of n_layers device pointers.  A host loop inside this call walks the diagonals d = t + l =
+ *   0 .. T + n_layers - 2, ONE LAUNCH PER DIAGONAL that serves every layer active on it (layer l runs t = d - l):
+ *   gates = [x_t | h_{t-1}] . [W_ih | W_hh]^T + bias in one K loop on MFMA, then the cell.  Stream order is the only synchronisation
+ *   between launches (no persistent kernel, no inter-workgroup waiting).  Per layer the workspace holds two bf16 images of h, written
+ *   at parity d & 1 and read at parity (d - 1) & 1, and one float32 c.
+ *   h_final / c_final (n_layers, B, H) float32, optional: h and c after the last step of each layer.
+ *   workspace >= ma_lstm_stack_workspace_bytes(T, B, H, n_layers), 16-byte aligned: MA_ERR_WORKSPACE otherwise.
+ * Shapes: T >= 1, B >= 1 (rows beyond B are never read), H % 64 == 0 (64 .. 4096), Kpad % 64 == 0, n_layers 1 .. 8: MA_ERR_UNSUPPORTED
+ * otherwise; MA_ERR_INVALID_ARG for a null or misaligned pointer or a size < 1; a failed launch returns MA_ERR_LAUNCH and ends the
+ * loop. */
+int64_t ma_lstm_stack_workspace_bytes(int64_t T, int64_t B, int32_t H, int32_t n_layers);
+int ma_lstm_stack_pack_f32(const float* w_ih, const float* w_hh, const float* b_ih, const float* b_hh, int32_t K, int32_t Kpad, int32_t H,
+                           void* packed, float* bias, ma_stream_t stream);
+int ma_lstm_stack_bf16(const void* x, int64_t T, int64_t B, int32_t Kpad, int32_t H, int32_t n_layers, const void* const* packed,
+                       const float* const* bias, float* out_f32, void* out_bf16, float* h_final, float* c_final, void* workspace,
+                       int64_t workspace_bytes, ma_stream_t stream);
+
+/* ---- TasNet (mindaudio/models/tasnet.py) outside its LSTM stack and fc GEMM, float32 ---------------------------------------------------
+ * ma_tasnet_gated_encode_f32: mixture (B, K, L) float32.  Per segment row (b, k): norm_coef[b, k] = sqrt(sum x^2); xn = x / (norm_coef +
+ *   1e-8); mixture_w[b, k, n] = relu(sum_j xn[j] Ut[j, n] + bU[n]) * sigmoid(sum_j xn[j] Vt[j, n] + bV[n]) with Ut, Vt (L, N) the
+ *   transposed Conv1d(L, N, 1) weights; then LayerNorm over N (mean and biased variance of the row, (v - mean) / sqrt(var + ln_eps) *
+ *   gamma + beta) stored as bf16 into xin (K, B, Kpad), row k * B + b, columns 0 .. N - 1: the LSTM stack's time-major input.  The
+ *   columns N .. Kpad - 1 are never written (the caller zeroes them once).  L <= 64, N <= 1024: MA_ERR_UNSUPPORTED otherwise.
+ * ma_tasnet_mask_decode_f32: score (K * B, nspk * N) float32, row k * B + b, row stride ld_score, column s * N + n (the fc output).
+ *   mask = softmax over the nspk speakers per (row, n); source_w = mixture_w[b, k, n] * mask;
+ *   out[b, s, k, l] = (sum_n source_w[s, n] basis[l, n] + bias[l]) * norm_coef[b, k] (the reference multiplies the bias too), out
+ *   (B, nspk, K, L).  nspk 1 .. 4, L <= 64, N <= 1024: MA_ERR_UNSUPPORTED otherwise.
+ * Both: MA_ERR_INVALID_ARG for a null pointer, a dimension < 1 or a misaligned base (16 bytes); fixed summation order. */
+int ma_tasnet_gated_encode_f32(const float* mixture, int64_t B, int64_t K, int32_t L, int32_t N, const float* Ut, const float* bU,
+                               const float* Vt, const float* bV, const float* gamma, const float* beta, float ln_eps, float* mixture_w,
+                               float* norm_coef, void* xin, int32_t Kpad, ma_stream_t stream);
+int ma_tasnet_mask_decode_f32(const float* score, int64_t ld_score, const float* mixture_w, const float* norm_coef, int64_t B, int64_t K,
+                              int32_t nspk, int32_t N, const float* basis, const float* bias, int32_t L, float* out, ma_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

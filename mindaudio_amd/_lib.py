@@ -416,6 +416,13 @@ PROTOTYPES = {
     "ma_lstm_bidir_bf16": (ctypes.c_int, [vp, i64, i64, i32, i32, vp, vp, vp, i32, i64, vp, vp, vp, vp, i64, vp]),
     "ma_ds2_conv1_bf16": (ctypes.c_int, [vp, i64, i32, i64, vp, vp, vp, i32, vp, vp]),
     "ma_ds2_softmax_f32": (ctypes.c_int, [vp, i64, i64, i64, i32, vp, vp]),
+    # ---- layer-pipelined LSTM stack, TasNet ----
+    "ma_lstm_stack_workspace_bytes": (i64, [i64, i64, i32, i32]),
+    "ma_lstm_stack_pack_f32": (ctypes.c_int, [vp, vp, vp, vp, i32, i32, i32, vp, vp, vp]),
+    "ma_lstm_stack_bf16": (ctypes.c_int, [vp, i64, i64, i32, i32, i32, ctypes.POINTER(vp), ctypes.POINTER(vp), vp, vp, vp, vp, vp, i64,
+                                          vp]),
+    "ma_tasnet_gated_encode_f32": (ctypes.c_int, [vp, i64, i64, i32, i32, vp, vp, vp, vp, vp, vp, f32, vp, vp, vp, i32, vp]),
+    "ma_tasnet_mask_decode_f32": (ctypes.c_int, [vp, i64, vp, vp, i64, i64, i32, i32, vp, vp, i32, vp, vp]),
 }
 
 FRAME_POWER_TILE, FRAME_POWER_MAX_RATIO, CHANNEL_MEAN_MAX = 16, 32, 8  # MA_FRAME_POWER_TILE, MA_FRAME_POWER_MAX_RATIO, MA_CHANNEL_MEAN_MAX

@@ -3,9 +3,9 @@ the same device functions as the fused head (ops.aam_softmax_loss, which a train
 import math
 
 from .. import ops
-from .separation_loss import Convtasnet_Loss
+from .separation_loss import Convtasnet_Loss, Separation_Loss
 
-__all__ = ["AdditiveAngularMargin", "Convtasnet_Loss"]
+__all__ = ["AdditiveAngularMargin", "Convtasnet_Loss", "Separation_Loss"]
 
 
 class AdditiveAngularMargin:

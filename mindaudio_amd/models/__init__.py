@@ -3,3 +3,4 @@ from .conv_tasnet import ConvTasNet  # noqa: F401
 from .deepspeech2 import DeepSpeechModel  # noqa: F401
 from .ecapatdnn import EcapaTDNN  # noqa: F401
 from .ecapatdnn import Classifier  # noqa: F401
+from .tasnet import TasNet  # noqa: F401

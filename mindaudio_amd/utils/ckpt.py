@@ -18,7 +18,8 @@ wrappers `Dense.dense`, `Conv1d.conv1d`, `Conv2d.conv2d`, `nn.SequentialCell` in
 `nn.Embedding.embedding_table`; `convert_names` maps them onto the names of mindaudio_amd.conformer.asr_model.ASRModel.
 `convert_ecapa_names` / `ecapa_to_reference_names` do the same for EcapaTDNN (mindaudio/models/ecapatdnn.py), which
 `load_mindspore_checkpoint` picks when it is handed that module, and `convert_conv_tasnet_names` /
-`conv_tasnet_to_reference_names` for ConvTasNet (mindaudio/models/conv_tasnet.py).
+`conv_tasnet_to_reference_names` for ConvTasNet (mindaudio/models/conv_tasnet.py), `convert_tasnet_names` /
+`tasnet_to_reference_names` for TasNet (mindaudio/models/tasnet.py).
 """
 import re
 
@@ -26,7 +27,7 @@ import numpy as np
 
 __all__ = ["read_mindspore_ckpt", "write_mindspore_ckpt", "convert_names", "to_reference_names", "read_epoch_num",
            "load_mindspore_checkpoint", "convert_ecapa_names", "ecapa_to_reference_names", "convert_conv_tasnet_names",
-           "conv_tasnet_to_reference_names"]
+           "conv_tasnet_to_reference_names", "convert_tasnet_names", "tasnet_to_reference_names"]
 
 _DTYPES = {"Float32": np.float32, "Float16": np.float16, "Float64": np.float64, "Int32": np.int32, "Int64": np.int64,
            "Int16": np.int16, "Int8": np.int8, "UInt8": np.uint8, "UInt16": np.uint16, "UInt32": np.uint32,
@@ -327,6 +328,48 @@ def _is_deepspeech2(module):
     return type(module).__name__ == "DeepSpeechModel"
 
 
+_TASNET_UNUSED = "separator.new_lstm."  # tasnet.py:111: Dense(500, 512), never called by construct()
+
+
+def convert_tasnet_names(ref_params):
+    """Reference TasNet (mindaudio/models/tasnet.py) parameter names -> mindaudio_amd.models.TasNet's state dict.  The cell
+    attributes already carry this package's names: encoder.conv1d_U|V.weight|bias, separator.layer_norm.gamma|beta,
+    separator.lstm.{weight_ih,weight_hh,bias_ih,bias_hh}_l<k>, separator.fc.weight|bias, decoder.basis_signals.weight|bias.  What
+    differs is the unit axis MindSpore's nn.Conv1d keeps in its weight ((N, L, 1, 1) -> (N, L, 1)), handled as for Conv-TasNet.
+    `separator.new_lstm.*`, the reference's unused Dense(500, 512), is accepted and ignored, like the optimizer state.
+    Not verified against a file MindSpore wrote (none can be produced here): the names, and nn.LSTM's per-layer split of its
+    weights, are inferred from the cell definitions."""
+    out = {}
+    for name, arr in ref_params.items():
+        n = _strip(name)
+        if _SKIP.match(n) or n.startswith(_TASNET_UNUSED):
+            continue
+        if n.endswith(".weight") and np.ndim(arr) == 4 and np.shape(arr)[2] == 1:
+            arr = np.asarray(arr)[:, :, 0, :]
+        out[n] = arr
+    return out
+
+
+def tasnet_to_reference_names(state, prefix="", new_lstm=None):
+    """Inverse of `convert_tasnet_names`: a TasNet state dict of this package -> {reference name: ndarray in MindSpore's layout}
+    (Conv1d weights with the unit axis).  `separator.new_lstm.weight` (512, 500) and `.bias` (512) are written back so that the
+    reference's load_param_into_net finds every parameter of its cell: from `new_lstm` = (weight, bias) when given, zeros otherwise
+    (the layer is never called)."""
+    out = {}
+    for k, v in state.items():
+        a = v.detach().float().cpu().numpy() if hasattr(v, "detach") else np.asarray(v)
+        if k.endswith(".weight") and a.ndim == 3:
+            a = a[:, :, None, :]
+        out[prefix + k] = a
+    w, b = new_lstm if new_lstm is not None else (np.zeros((512, 500), np.float32), np.zeros((512,), np.float32))
+    out[prefix + _TASNET_UNUSED + "weight"], out[prefix + _TASNET_UNUSED + "bias"] = np.asarray(w, np.float32), np.asarray(b, np.float32)
+    return out
+
+
+def _is_tasnet(module):
+    return type(module).__name__ == "TasNet"
+
+
 def read_epoch_num(path):
     """`int(param_dict.get("epoch_num", 0))` of examples/conformer/train.py:121 - the number of finished epochs the reference's
     ModelCheckpoint appends to every file (`append_info=[{"epoch_num": ...}]`, train.py:157-163)."""
@@ -344,6 +387,8 @@ def load_mindspore_checkpoint(module, path, strict=True):
         params = convert_conv_tasnet_names(raw)
     elif _is_deepspeech2(module):
         params = convert_deepspeech2_names(raw)
+    elif _is_tasnet(module):
+        params = convert_tasnet_names(raw)
     else:
         params = convert_ecapa_names(raw) if _is_ecapa(module) else convert_names(raw)
     own = module.state_dict()
