@@ -1629,6 +1629,91 @@ int ma_tasnet_gated_encode_f32(const float* mixture, int64_t B, int64_t K, int32
 int ma_tasnet_mask_decode_f32(const float* score, int64_t ld_score, const float* mixture_w, const float* norm_coef, int64_t B, int64_t K,
                               int32_t nspk, int32_t N, const float* basis, const float* bias, int32_t L, float* out, ma_stream_t stream);
 
+/* ---- WaveGrad vocoder (mindaudio/models/wavegrad/wavegrad_v190.py, examples/wavegrad/reverse.py) -----------------------------------------
+ * Activations are time-major, channel-last float32 (B, T_l, C), compact.  bf16 exists only as an MFMA operand: (B, T_l + 2 * halo, Cpad)
+ * with zero halo rows around every utterance and zero columns C .. Cpad - 1 (Cpad % 64 == 0), the layout of ma_conv1d_taps_bf16.  No
+ * atomics, no cross-workgroup waiting: the same bits from run to run.  All: every argument check comes before any HIP call; 16-byte
+ * aligned bases; nothing allocates or synchronises.
+ *
+ * ma_wavegrad_init_conv_f32: Conv1d(1 -> C0, `taps` odd <= 7, pad same, bias) on audio (B, T) float32, float32 weights wt (taps, C0)
+ *   (transposed), fma chain in tap order starting from the bias -> out (B, T, C0).  Taps outside the utterance read zero.  C0 % 4 == 0.
+ * ma_wavegrad_pack_bf16: the operand producer in front of every MFMA product.  For output row t < T_in * f of utterance b, channel c:
+ *     v = x[b, t / f, c]                                  x (B, T_in, C) float32; f >= 1 is nearest-neighbour repetition
+ *     res[b, t, c] = v * res_mul                           (res != NULL: (B, T_in * f, C) float32)
+ *     v = fma(scale, v, shift) * (1 / sqrt 2)              (film != NULL: a (B * T_in * f, >= 2 C) float32 matrix, row stride ld_film,
+ *                                                           shift = columns 0 .. C - 1, scale = columns C .. 2 C - 1)
+ *     v = v >= 0 ? v : slope * v                           (slope = 1: a plain cast)
+ *     v += enc[b * ld_enc + c]                             (enc != NULL; ld_enc = 0 broadcasts one row over the batch)
+ *     v *= mul;  out = bf16(v), round to nearest even
+ *   out (B, T_in * f + 2 * halo, Cpad) bf16: halo rows and the columns C .. Cpad - 1 are written as zeros on every call; halo >= 0.
+ *   out may be NULL when res is given.  C % 8 == 0, Cpad % 64 == 0, Cpad >= C, ld_film % 4 == 0, ld_enc % 4 == 0: MA_ERR_UNSUPPORTED
+ *   otherwise.
+ * ma_wavegrad_last_conv_update_f32: Conv1d(C -> 1, `taps` odd <= 7, pad same, bias) on x (B, T, C) float32 with w (taps, C) float32,
+ *   fused with the update of reverse.py:116-123:  pred = conv(x);  audio_out = c1 * (audio_in - c2 * pred) (+ sigma * noise when noise
+ *   != NULL).  pred (B, T) is stored when non-NULL; audio_out may be NULL (then audio_in and noise are not read) when pred is given;
+ *   audio_out == audio_in is allowed.  C % 4 == 0, B <= 65535. */
+int ma_wavegrad_init_conv_f32(const float* audio, int64_t B, int64_t T, const float* wt, const float* bias, int32_t taps, int32_t C0,
+                              float* out, ma_stream_t stream);
+int ma_wavegrad_pack_bf16(const float* x, int64_t B, int64_t T_in, int32_t f, int32_t C, int32_t Cpad, int32_t halo, const float* film,
+                          int64_t ld_film, const float* enc, int64_t ld_enc, float slope, float mul, void* out, float* res,
+                          float res_mul, ma_stream_t stream);
+int ma_wavegrad_last_conv_update_f32(const float* x, int64_t B, int64_t T, int32_t C, const float* w, const float* bias, int32_t taps,
+                                     const float* audio_in, const float* noise, float c1, float c2, float sigma, float* audio_out,
+                                     float* pred, ma_stream_t stream);
+
+/* One launch (B launches for the MFMA products: one per utterance) of a network evaluation.  Buffers are byte offsets into ONE
+ * workspace; MA_WAVEGRAD_BUF_NONE = absent, _AUDIO = the call's audio (B, T), _MEL = the call's spectrogram (B, frames, n_mels) float32
+ * (time-major).  T = the rows per utterance of the op's OUTPUT.
+ *   MA_WAVEGRAD_OP_INIT  in (AUDIO) -> out (B, T, N) float32; w = wt (taps, N) float32
+ *   MA_WAVEGRAD_OP_PACK  in x (B, T / f, C) float32, in2 = film matrix (row stride ld_film) or NONE, enc_off >= 0: the step's encoding
+ *                        row + enc_off; -> out (B, T + 2 halo, Cpad) bf16 or NONE, out2 = res or NONE
+ *   MA_WAVEGRAD_OP_CONV  ma_conv1d_taps_bf16 per utterance on in (B, T + 2 halo, Cpad) bf16, w (N, taps, Cpad) bf16, bias, alpha,
+ *                        residual (B, T, N) float32 or NONE -> out (B, T, N) float32, or bf16 when out_bf16 (N % 64 == 0 then)
+ *   MA_WAVEGRAD_OP_DOWN  the kernel = stride = f convolution as ma_gemm_bf16 per utterance on in (B, T * f + 2 halo, Cpad) bf16:
+ *                        A = the utterance's first real row, lda = K = f * Cpad, M = T; w (N, f, Cpad) bf16 -> out (B, T, N) float32
+ *   MA_WAVEGRAD_OP_LAST  ma_wavegrad_last_conv_update_f32 on in (B, T, C) float32, w (taps, C) float32
+ * `once` ops do not depend on the step (first_conv of the spectrogram): ma_wavegrad_reverse runs them once per call. */
+enum { MA_WAVEGRAD_OP_INIT = 0, MA_WAVEGRAD_OP_PACK = 1, MA_WAVEGRAD_OP_CONV = 2, MA_WAVEGRAD_OP_DOWN = 3, MA_WAVEGRAD_OP_LAST = 4 };
+#define MA_WAVEGRAD_BUF_NONE (-1)
+#define MA_WAVEGRAD_BUF_AUDIO (-2)
+#define MA_WAVEGRAD_BUF_MEL (-3)
+typedef struct ma_wavegrad_op {
+  int32_t kind, once;
+  int64_t in, in2, out, out2, residual; /* byte offsets into the workspace (multiples of 16) or MA_WAVEGRAD_BUF_* */
+  const void* w;                        /* device */
+  const float* bias;                    /* device */
+  int64_t T, ld_film;
+  int32_t C, Cpad, N, taps, dilation, f, halo, out_bf16, enc_off, reserved;
+  float slope, mul, res_mul, alpha;
+} ma_wavegrad_op_t;
+
+/* The network for one (B, frames) shape: plain data, filled by the caller once per shape.  T = hop * frames; enc_dim = the floats
+ * of one step's positional-encoding row (the sum over the FiLM levels). */
+typedef struct ma_wavegrad_plan {
+  int32_t n_ops, enc_dim;
+  int64_t B, T, frames, n_mels;
+  const ma_wavegrad_op_t* ops; /* host */
+} ma_wavegrad_plan_t;
+
+/* Bytes of workspace the plan's offsets reach (the largest offset + extent over its ops); a negative MA_ERR_* for a plan that
+ * ma_wavegrad_forward would refuse (an unknown kind, a misaligned or missing buffer, a halo smaller than (taps / 2) * dilation, ...). */
+int64_t ma_wavegrad_workspace_bytes(const ma_wavegrad_plan_t* plan);
+
+/* ma_wavegrad_forward: one network evaluation, a host loop over the plan's ops inside one call.  audio (B, T), mel (B, frames, n_mels),
+ *   enc (B or 1, enc_dim) float32 with row stride ld_enc (0: one row for the whole batch) -> pred (B, T) float32.
+ * ma_wavegrad_reverse: iterations m = first_step .. first_step + n_steps - 1 of the S-step loop of reverse.py:114-123 back to back, n =
+ *   S - 1 - m:  pred = network(audio, enc_table[n]);  audio = c1[n] * (audio - c2[n] * pred) + (n > 0 ? sigma[n] * noise[m - first_step]
+ *   : 0), audio (B, T) updated in place.  c1, c2, sigma: HOST arrays [S]; enc_table (S, enc_dim) and noise (n_steps, B, T; the entry of
+ *   n == 0 is never read and may be missing) on the device.  Between its first and its last launch there is no host synchronisation,
+ *   no read-back and no allocation; the `once` ops run once per call.
+ * Both: MA_ERR_WORKSPACE when workspace_bytes < ma_wavegrad_workspace_bytes(plan); a failed launch returns MA_ERR_LAUNCH and ends
+ * the call. */
+int ma_wavegrad_forward(const ma_wavegrad_plan_t* plan, const float* audio, const float* mel, const float* enc, int64_t ld_enc,
+                        float* pred, void* workspace, int64_t workspace_bytes, ma_stream_t stream);
+int ma_wavegrad_reverse(const ma_wavegrad_plan_t* plan, float* audio, const float* mel, const float* enc_table, const float* c1,
+                        const float* c2, const float* sigma, const float* noise, int32_t S, int32_t first_step, int32_t n_steps,
+                        void* workspace, int64_t workspace_bytes, ma_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -103,6 +103,22 @@ class IirFilter(ctypes.Structure):
                 ("power", ctypes.c_void_p), ("steps", ctypes.c_int32), ("reserved", ctypes.c_int32)]
 
 
+class WaveGradOp(ctypes.Structure):
+    """struct ma_wavegrad_op (include/mindaudio_amd.h)."""
+
+    _fields_ = [("kind", i32), ("once", i32), ("inp", i64), ("in2", i64), ("out", i64), ("out2", i64), ("residual", i64),
+                ("w", ctypes.c_void_p), ("bias", ctypes.c_void_p), ("T", i64), ("ld_film", i64), ("C", i32), ("Cpad", i32), ("N", i32),
+                ("taps", i32), ("dilation", i32), ("f", i32), ("halo", i32), ("out_bf16", i32), ("enc_off", i32), ("reserved", i32),
+                ("slope", f32), ("mul", f32), ("res_mul", f32), ("alpha", f32)]
+
+
+class WaveGradPlan(ctypes.Structure):
+    """struct ma_wavegrad_plan (include/mindaudio_amd.h); ops is a HOST array of WaveGradOp."""
+
+    _fields_ = [("n_ops", i32), ("enc_dim", i32), ("B", i64), ("T", i64), ("frames", i64), ("n_mels", i64),
+                ("ops", ctypes.POINTER(WaveGradOp))]
+
+
 class GemmEpilogue(ctypes.Structure):
     """struct ma_gemm_epilogue (include/mindaudio_amd.h)."""
 
@@ -423,7 +439,17 @@ PROTOTYPES = {
                                           vp]),
     "ma_tasnet_gated_encode_f32": (ctypes.c_int, [vp, i64, i64, i32, i32, vp, vp, vp, vp, vp, vp, f32, vp, vp, vp, i32, vp]),
     "ma_tasnet_mask_decode_f32": (ctypes.c_int, [vp, i64, vp, vp, i64, i64, i32, i32, vp, vp, i32, vp, vp]),
+    # ---- WaveGrad vocoder ----
+    "ma_wavegrad_init_conv_f32": (ctypes.c_int, [vp, i64, i64, vp, vp, i32, i32, vp, vp]),
+    "ma_wavegrad_pack_bf16": (ctypes.c_int, [vp, i64, i64, i32, i32, i32, i32, vp, i64, vp, i64, f32, f32, vp, vp, f32, vp]),
+    "ma_wavegrad_last_conv_update_f32": (ctypes.c_int, [vp, i64, i64, i32, vp, vp, i32, vp, vp, f32, f32, f32, vp, vp, vp]),
+    "ma_wavegrad_workspace_bytes": (i64, [ctypes.POINTER(WaveGradPlan)]),
+    "ma_wavegrad_forward": (ctypes.c_int, [ctypes.POINTER(WaveGradPlan), vp, vp, vp, i64, vp, vp, i64, vp]),
+    "ma_wavegrad_reverse": (ctypes.c_int, [ctypes.POINTER(WaveGradPlan), vp, vp, vp, ctypes.POINTER(f32), ctypes.POINTER(f32),
+                                           ctypes.POINTER(f32), vp, i32, i32, i32, vp, i64, vp]),
 }
+WAVEGRAD_OP_INIT, WAVEGRAD_OP_PACK, WAVEGRAD_OP_CONV, WAVEGRAD_OP_DOWN, WAVEGRAD_OP_LAST = range(5)  # MA_WAVEGRAD_OP_*
+WAVEGRAD_BUF_NONE, WAVEGRAD_BUF_AUDIO, WAVEGRAD_BUF_MEL = -1, -2, -3  # MA_WAVEGRAD_BUF_*
 
 FRAME_POWER_TILE, FRAME_POWER_MAX_RATIO, CHANNEL_MEAN_MAX = 16, 32, 8  # MA_FRAME_POWER_TILE, MA_FRAME_POWER_MAX_RATIO, MA_CHANNEL_MEAN_MAX
 DTYPE_F32, DTYPE_F64, DTYPE_I32, DTYPE_I64 = 0, 1, 2, 3  # MA_DTYPE_*

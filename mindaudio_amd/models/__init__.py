@@ -4,3 +4,4 @@ from .deepspeech2 import DeepSpeechModel  # noqa: F401
 from .ecapatdnn import EcapaTDNN  # noqa: F401
 from .ecapatdnn import Classifier  # noqa: F401
 from .tasnet import TasNet  # noqa: F401
+from .wavegrad import WaveGrad  # noqa: F401

@@ -370,6 +370,40 @@ def _is_tasnet(module):
     return type(module).__name__ == "TasNet"
 
 
+def convert_wavegrad_names(ref_params):
+    """Reference WaveGrad (mindaudio/models/wavegrad/wavegrad_v190.py) parameter names -> mindaudio_amd.models.WaveGrad's state dict.
+    The cell attributes already carry this package's names (DBlock.0, DBlock.<n>.{residual_dense, conv.1|3|5, downscale1,
+    downscale2}, FiLM.<n>.{input_conv, output_conv}, UBlock.<n>.{block1, block2_a, block2_b, block3_a, block3_b}, first_conv,
+    last_conv, each with .weight / .bias); what differs is the unit axis MindSpore's nn.Conv1d keeps in its weight ((out, in, 1, k) ->
+    (out, in, k); (out, in, k) is accepted as it is).  `cur_step`, the optimizer's `moment*` and `global_step` are ignored.
+    Not verified against a file MindSpore wrote (none can be produced here): the names are inferred from the cell definitions."""
+    out = {}
+    for name, arr in ref_params.items():
+        n = _strip(name)
+        if _SKIP.match(n):
+            continue
+        if n.endswith(".weight") and np.ndim(arr) == 4 and np.shape(arr)[2] == 1:
+            arr = np.asarray(arr)[:, :, 0, :]
+        out[n] = arr
+    return out
+
+
+def wavegrad_to_reference_names(state, prefix=""):
+    """Inverse of `convert_wavegrad_names`: a WaveGrad state dict of this package -> {reference name: ndarray in MindSpore's layout}
+    (Conv1d weights with the unit axis)."""
+    out = {}
+    for k, v in state.items():
+        a = v.detach().float().cpu().numpy() if hasattr(v, "detach") else np.asarray(v)
+        if k.endswith(".weight") and a.ndim == 3:
+            a = a[:, :, None, :]
+        out[prefix + k] = a
+    return out
+
+
+def _is_wavegrad(module):
+    return type(module).__name__ == "WaveGrad"
+
+
 def read_epoch_num(path):
     """`int(param_dict.get("epoch_num", 0))` of examples/conformer/train.py:121 - the number of finished epochs the reference's
     ModelCheckpoint appends to every file (`append_info=[{"epoch_num": ...}]`, train.py:157-163)."""
@@ -389,6 +423,8 @@ def load_mindspore_checkpoint(module, path, strict=True):
         params = convert_deepspeech2_names(raw)
     elif _is_tasnet(module):
         params = convert_tasnet_names(raw)
+    elif _is_wavegrad(module):
+        params = convert_wavegrad_names(raw)
     else:
         params = convert_ecapa_names(raw) if _is_ecapa(module) else convert_names(raw)
     own = module.state_dict()
