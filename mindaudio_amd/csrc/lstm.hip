@@ -1,24 +1,18 @@
 // Bidirectional LSTM layer, inference (mindaudio/models/deepspeech2.py BatchRNN: nn.LSTM(bidirectional=True, has_bias=True), the two
-// directions SUMMED).  Contract: include/mindaudio_amd.h.
+// directions SUMMED).  Contract: include/mindaudio_amd.h.  The tile, the cell, the packed weights' fragment order and the K loop are
+// lstm_common.h's; this file holds the schedule, the direction sum and the two ways a workgroup covers its batch rows.
 //
-// One layer = the input projection of a time chunk (ma_gemm_bf16, float32 out, b_ih + b_hh as its bias) followed by ONE LAUNCH PER
-// TIME STEP of lstm_step_kernel, issued from the host loop of ma_lstm_bidir_bf16.  The stream order between those launches is the only
-// synchronisation: no workgroup ever waits for another one (no grid barrier, no flags, no cooperative launch, no atomics).
+// Schedule.  One layer = the input projection of a time chunk (ma_gemm_bf16, float32 out, b_ih + b_hh as its bias) followed by ONE
+// LAUNCH PER TIME STEP of a step kernel, issued from the host loop of ma_lstm_bidir_bf16.  The stream order between those launches is
+// the only synchronisation: no workgroup ever waits for another one (no grid barrier, no flags, no cooperative launch, no atomics).
 //
-// Step kernel.  gates (B, 4H) = h_{s-1} (B, H) . W_hh^T, PyTorch gate order i, f, g, o.  A tile is 16 batch rows x 16 hidden units
-// with ALL FOUR gate rows of those units: four 16 x 16 accumulators of v_mfma_f32_16x16x32_bf16, A operand = h (row = batch), B operand =
-// W_hh (column = hidden unit).  The C/D map (column = lane & 15, row = 4 (lane >> 4) + register) puts the four gates of one
-// (batch row, hidden unit) into the same lane and register, so the gate arithmetic needs no lane movement and no memory: add the
-// projection, two sigmoids and two tanhs, update c (float32, in place, one owner per element), store h.
-//   grid = (H / 16 hidden slices, directions, ceil(B / 64)), 4 waves per workgroup, wave w runs the cell of batch rows 64 z + 16 w ..+15.
-// W_hh is packed once (ma_lstm_pack_f32) in fragment order: for (direction, slice, k-step of 32, gate) the 64 lanes' 8 bf16 are 1 KiB
-// contiguous, so a wave reads the four gate fragments of a k-step as one 4 KiB run, straight into registers; h is read from its
+// Step kernel.  gates (B, 4H) = h_{s-1} (B, H) . W_hh^T + the step's projection rows; c is float32, updated in place, one owner per
+// element.  grid = (H / 16 hidden slices, directions, ceil(B / 64)), 4 waves per workgroup, wave w runs the cell of batch rows
+// 64 z + 16 w .. + 15.  W_hh is packed once (ma_lstm_pack_f32) with the two directions as 2 H / 16 slices; h is read from its
 // (B, H) bf16 image, 16 bytes per lane.  Two forms:
 //   lstm_step_ksplit_kernel (H / 32 a multiple of 4): K is split over the four waves, each runs a quarter of the k-steps for all four
 //     batch tiles, so the workgroup reads its 128 KB slice of W_hh once; the partial sums meet in LDS (48 KB, one workgroup barrier).
 //   lstm_step_kernel (any H % 64 == 0): each wave runs all of K for its own tile; no LDS, no barrier.
-// Both issue the next operand block's loads before the current block's MFMAs and load the cell's inputs (projection, c) before the
-// k loop: a step's grid is one workgroup per CU at B = 128, i.e. one wave per SIMD, so latency is hidden inside the wave or not at all.
 //
 // Rounding points: x, W_ih, W_hh and the fed-back h are bf16 MFMA operands (round to nearest even); the projection, the gate sums,
 // c, h before it is fed back, and the layer output are float32; accumulation is float32.
@@ -33,14 +27,10 @@
 
 #include "../../include/mindaudio_amd.h"
 
-#include "device_common.h"
 #include "launch.h"
+#include "lstm_common.h"
 
 namespace ma {
-
-constexpr int kLstmThreads = 256;
-constexpr int kLstmSlice = 16;     // hidden units of a workgroup (x 4 gate rows)
-constexpr int kLstmRowsPerWg = 64;  // batch rows of a workgroup: 16 per wave
 
 enum : int { kLstmFirst = 0, kLstmSecond = 1, kLstmAlone = 2, kLstmTie = 3 };
 
@@ -58,11 +48,9 @@ struct LstmStep {
   int32_t B, H;
 };
 
-__device__ __forceinline__ float sigmoid_acc(float v) { return 1.0f / (1.0f + expf(-v)); }
-
 // What the cell of one 16 x 16 tile reads besides the product, in the C/D layout (batch row b0 + 4 (lane >> 4) + r, hidden unit
 // 16 sl + (lane & 15)): the four projections, c and - for the direction that reaches a frame second - the other direction's h.
-// None of it depends on the product, so it is loaded BEFORE the k loop and its latency hides behind it.  Rows beyond B read nothing.
+// Rows beyond B read nothing.
 struct LstmCellIn {
   float gate[4][4];  // [gate][r]
   float c[4], prev[4];
@@ -86,7 +74,7 @@ __device__ __forceinline__ LstmCellIn lstm_cell_load(const LstmStep& p, int dir,
   return in;
 }
 
-// The cell: gate sums, two sigmoids, two tanhs, c, h and the stores.  Rows beyond B store nothing.
+// The gate sums, the cell and the stores of a tile.  Rows beyond B store nothing.
 __device__ __forceinline__ void lstm_cell_store(const LstmStep& p, int dir, int sl, int b0, int lane, const f32x4 (&acc)[4],
                                                 const LstmCellIn& in) {
   const int H = p.H;
@@ -97,80 +85,44 @@ __device__ __forceinline__ void lstm_cell_store(const LstmStep& p, int dir, int 
   for (int r = 0; r < 4; ++r) {
     const int b = b0 + 4 * (lane >> 4) + r;
     if (b >= p.B) continue;
-    const float gi = acc[0][r] + in.gate[0][r];
-    const float gf = acc[1][r] + in.gate[1][r];
-    const float gg = acc[2][r] + in.gate[2][r];
-    const float go = acc[3][r] + in.gate[3][r];
     const int64_t e = (int64_t)b * H + j;
-    const float cn = sigmoid_acc(gf) * in.c[r] + sigmoid_acc(gi) * tanhf(gg);
-    const float h = sigmoid_acc(go) * tanhf(cn);
-    p.c[dir_off + e] = cn;
-    p.h_out[dir_off + e] = f2bf(h);
+    const LstmCell o = lstm_cell(acc[0][r] + in.gate[0][r], acc[1][r] + in.gate[1][r], acc[2][r] + in.gate[2][r],
+                                 acc[3][r] + in.gate[3][r], in.c[r]);
+    p.c[dir_off + e] = o.c;
+    p.h_out[dir_off + e] = f2bf(o.h);
     if (mode == kLstmFirst) {
-      p.out_f32[dir][e] = h;
+      p.out_f32[dir][e] = o.h;
     } else if (mode == kLstmTie) {
-      p.tie[e] = h;
+      p.tie[e] = o.h;
     } else {
-      const float v = mode == kLstmSecond ? in.prev[r] + h : h;
+      const float v = mode == kLstmSecond ? in.prev[r] + o.h : o.h;
       p.out_f32[dir][e] = v;
       if (p.out_bf16[dir]) p.out_bf16[dir][e] = f2bf(v);
     }
   }
 }
 
-// KB k-steps of operands: the h fragment and the four gate fragments of W_hh per k-step
-template <int KB>
-struct LstmOperands {
-  bf16x8 a[KB];
-  bf16x8 w[KB][4];
-};
+// this lane's A operand row of the tile at batch row b0 (rows beyond B take row 0's), at the lane's column of k-step 0
+__device__ __forceinline__ const uint16_t* lstm_h_row(const LstmStep& p, int dir, int b0, int lane) {
+  const int row = b0 + (lane & 15);
+  return p.h_in + (int64_t)dir * p.B * p.H + (int64_t)(row < p.B ? row : 0) * p.H + 8 * (lane >> 4);
+}
 
 // Each wave runs all of K for its own batch tile (the form for an H / 32 that is no multiple of 4; launched with KB = 2).  KB =
-// k-steps per operand block.  Two blocks are in registers: the loads of block i + 1 (5 KB of 16 bytes per lane) are issued before the
-// MFMAs of block i, so that the L2 latency of the weight stream hides behind the previous block's MFMAs.
+// k-steps per operand block (5 KB of 16 bytes per lane).
 template <int KB>
 __global__ __launch_bounds__(kLstmThreads) void lstm_step_kernel(const LstmStep p) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int b0 = ((int)blockIdx.z * 4 + wave) * 16;
   if (b0 >= p.B) return;  // (no barrier anywhere in this kernel)
-  const int dir = p.dir0 + (int)blockIdx.y;
-  const int H = p.H, nk = H / 32, ns = H / kLstmSlice;
-  const int sl = blockIdx.x;
-  const int64_t dir_off = (int64_t)dir * p.B * H;
-
-  // rows beyond B are not read: their lanes take row 0's operand instead, and their results are never stored (an MFMA row depends
-  // on its own A row only)
-  const int arow = b0 + (lane & 15);
-  const uint16_t* hp = p.h_in + dir_off + (int64_t)(arow < p.B ? arow : 0) * H + 8 * (lane >> 4);
-  const uint16_t* wp = p.whh + ((((int64_t)dir * ns + sl) * nk * 4) * 64 + lane) * 8;
-
-  f32x4 acc[4];
-#pragma unroll
-  for (int g = 0; g < 4; ++g) acc[g] = f32x4{0.f, 0.f, 0.f, 0.f};
-  auto load = [&](LstmOperands<KB>& o, int kk0) __attribute__((always_inline)) {
-#pragma unroll
-    for (int u = 0; u < KB; ++u) {
-      o.a[u] = *reinterpret_cast<const bf16x8*>(hp + (kk0 + u) * 32);
-#pragma unroll
-      for (int g = 0; g < 4; ++g) o.w[u][g] = *reinterpret_cast<const bf16x8*>(wp + ((int64_t)(kk0 + u) * 4 + g) * 512);
-    }
-  };
-  auto mma = [&](const LstmOperands<KB>& o) __attribute__((always_inline)) {
-#pragma unroll
-    for (int u = 0; u < KB; ++u)
-#pragma unroll
-      for (int g = 0; g < 4; ++g) acc[g] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(o.a[u], o.w[u][g], acc[g], 0, 0, 0);
-  };
-  LstmOperands<KB> cur, nxt;
-  load(cur, 0);
-  const LstmCellIn in = lstm_cell_load(p, dir, sl, b0, lane);
-  for (int kk = KB; kk < nk; kk += KB) {  // (nk % KB == 0: the launcher's choice of KB)
-    load(nxt, kk);
-    mma(cur);
-    cur = nxt;
-  }
-  mma(cur);
-  lstm_cell_store(p, dir, sl, b0, lane, acc, in);
+  const int dir = p.dir0 + (int)blockIdx.y, sl = blockIdx.x;
+  const int nk = p.H / 32, ns = p.H / kLstmSlice;
+  const uint16_t* hp = lstm_h_row(p, dir, b0, lane);
+  f32x4 acc[1][4];
+  LstmCellIn in;
+  lstm_k_loop<KB>(lstm_gate_run(p.whh, nk, (int64_t)dir * ns + sl, 0, lane), [&](int, int kk) { return hp + kk * 32; }, 0, nk, acc,
+                  [&] { in = lstm_cell_load(p, dir, sl, b0, lane); });
+  lstm_cell_store(p, dir, sl, b0, lane, acc[0], in);
 }
 
 constexpr int kLstmPartialFloats = 4 * 3 * 16 * 64;  // [source wave][other tile][gate * 4 + register][lane]: 48 KB
@@ -178,39 +130,32 @@ constexpr int kLstmPartialFloats = 4 * 3 * 16 * 64;  // [source wave][other tile
 // The same step with K SPLIT OVER THE FOUR WAVES (H / 32 a multiple of 4): wave w runs the k-steps [w nk / 4, (w + 1) nk / 4) for all
 // four batch tiles of the workgroup, so the workgroup reads its 128 KB slice of W_hh once instead of once per wave.  The partial
 // accumulators of the three tiles a wave does not own go through LDS; after the workgroup's one barrier wave w adds the four
-// partials of tile w in wave order and runs the cell.  Tiles beyond B compute on row 0's operand and store nothing.  KB = k-steps
-// per operand block, two blocks in registers as above.
+// partials of tile w in wave order and runs the cell.  Tiles beyond B compute on row 0's operand and store nothing.
 template <int KB>
 __global__ __launch_bounds__(kLstmThreads) void lstm_step_ksplit_kernel(const LstmStep p) {
   __shared__ float part[kLstmPartialFloats];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int z0 = (int)blockIdx.z * kLstmRowsPerWg;
-  const int dir = p.dir0 + (int)blockIdx.y;
-  const int H = p.H, nk = H / 32, ns = H / kLstmSlice, nkw = nk / 4;
-  const int sl = blockIdx.x;
-  const int64_t dir_off = (int64_t)dir * p.B * H;
+  const int dir = p.dir0 + (int)blockIdx.y, sl = blockIdx.x;
+  const int nk = p.H / 32, ns = p.H / kLstmSlice, nkw = nk / 4;
   const uint16_t* hp[4];
 #pragma unroll
-  for (int t = 0; t < 4; ++t) {
-    const int row = z0 + 16 * t + (lane & 15);
-    hp[t] = p.h_in + dir_off + (int64_t)(row < p.B ? row : 0) * H + 8 * (lane >> 4) + wave * nkw * 32;
-  }
-  const uint16_t* wp = p.whh + (((((int64_t)dir * ns + sl) * nk + wave * nkw) * 4) * 64 + lane) * 8;
-
+  for (int t = 0; t < 4; ++t) hp[t] = lstm_h_row(p, dir, z0 + 16 * t, lane) + wave * nkw * 32;  // (both operands start at the wave's share)
+  const uint16_t* wp = lstm_gate_run(p.whh, nk, (int64_t)dir * ns + sl, wave * nkw, lane);
   f32x4 acc[4][4];  // [tile][gate]
 #pragma unroll
   for (int t = 0; t < 4; ++t)
 #pragma unroll
     for (int g = 0; g < 4; ++g) acc[t][g] = f32x4{0.f, 0.f, 0.f, 0.f};
-  struct Operands {
-    bf16x8 a[KB][4];
-    bf16x8 w[KB][4];
-  };
+  // lstm_k_loop<KB, 4> written out: the same statements in the same order.  Through the call, with the cell's loads behind a callable,
+  // this kernel's step measured 0.08 us longer at B = 1 (TasNet's layered schedule, 13 280 steps: 66.2 ms against 65.1 ms), so it
+  // keeps the loop in its own body; a change to lstm_k_loop's issue order is made here as well.
+  using Operands = LstmOperands<KB, 4>;
   auto load = [&](Operands& o, int kk0) __attribute__((always_inline)) {
 #pragma unroll
     for (int u = 0; u < KB; ++u) {
 #pragma unroll
-      for (int g = 0; g < 4; ++g) o.w[u][g] = *reinterpret_cast<const bf16x8*>(wp + ((int64_t)(kk0 + u) * 4 + g) * 512);
+      for (int g = 0; g < 4; ++g) o.w[u][g] = *reinterpret_cast<const bf16x8*>(wp + ((int64_t)(kk0 + u) * 4 + g) * kLstmGateElems);
 #pragma unroll
       for (int t = 0; t < 4; ++t) o.a[u][t] = *reinterpret_cast<const bf16x8*>(hp[t] + (kk0 + u) * 32);
     }
@@ -290,29 +235,14 @@ __global__ __launch_bounds__(256) void lstm_pack_ih_kernel(const float* __restri
   out[i] = k < K ? f2bf(w[r * K + k]) : (uint16_t)0;
 }
 
-// W_hh (2, 4H, H) f32 -> fragment order: [direction][slice][k-step][gate][lane][8]
+// W_hh (2, 4H, H) f32 -> fragment order, the directions as 2 H / 16 slices
 __global__ __launch_bounds__(256) void lstm_pack_hh_kernel(const float* __restrict__ w, int H, int64_t groups, uint16_t* __restrict__ out) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;  // one 8-element fragment
   if (i >= groups) return;
-  const int nk = H / 32, ns = H / kLstmSlice;
-  const int lane = (int)(i & 63);
-  int64_t q = i >> 6;
-  const int g = (int)(q & 3);
-  q >>= 2;
-  const int kk = (int)(q % nk);
-  q /= nk;
-  const int sl = (int)(q % ns);
-  const int dir = (int)(q / ns);
-  const float* src = w + ((int64_t)dir * 4 * H + (int64_t)g * H + sl * kLstmSlice + (lane & 15)) * H + kk * 32 + 8 * (lane >> 4);
-  u32x4 v;
-  v[0] = pack2_bf16(src[0], src[1]);
-  v[1] = pack2_bf16(src[2], src[3]);
-  v[2] = pack2_bf16(src[4], src[5]);
-  v[3] = pack2_bf16(src[6], src[7]);
-  *reinterpret_cast<u32x4*>(out + i * 8) = v;
+  const LstmFragment f = lstm_fragment(i, H / 32);
+  const int64_t dir = f.unit / H, j = f.unit % H;
+  lstm_pack_fragment(w + ((dir * 4 + f.gate) * H + j) * H, f.k, H, out + i * 8);
 }
-
-static int64_t align256(int64_t v) { return (v + 255) & ~(int64_t)255; }
 
 struct LstmWs {
   int64_t h, c, tie, proj, total;  // byte offsets; proj holds 2 x (chunk * B, 4H) float32
@@ -325,11 +255,6 @@ static LstmWs lstm_ws(int64_t B, int64_t H, int64_t chunk) {
   w.proj = w.tie + align256(B * H * 4);
   w.total = w.proj + 2 * align256(chunk * B * 4 * H * 4);
   return w;
-}
-
-static bool lstm_shape_ok(int64_t T, int64_t B, int64_t Kpad, int64_t H) {
-  return T >= 1 && B >= 1 && H >= 64 && H % 64 == 0 && H <= 4096 && Kpad >= 64 && Kpad % 64 == 0 && B <= 65535 * (int64_t)kLstmRowsPerWg &&
-         B * 4 * H <= 0x7fffffff;
 }
 
 }  // namespace ma
@@ -348,8 +273,7 @@ int ma_lstm_pack_f32(const float* w_ih, const float* w_hh, const float* b_ih, co
                      void* wih_bf16, void* whh_packed, float* bias, ma_stream_t stream) {
   if (!w_ih || !w_hh || !b_ih || !b_hh || !wih_bf16 || !whh_packed || !bias || K < 1 || Kpad < K || H < 1) return MA_ERR_INVALID_ARG;
   if (!lstm_shape_ok(1, 1, Kpad, H)) return MA_ERR_UNSUPPORTED;
-  if ((reinterpret_cast<uintptr_t>(wih_bf16) | reinterpret_cast<uintptr_t>(whh_packed) | reinterpret_cast<uintptr_t>(bias)) & 15)
-    return MA_ERR_INVALID_ARG;
+  if (!lstm_aligned16(wih_bf16, whh_packed, bias)) return MA_ERR_INVALID_ARG;
   const int64_t rows = 2 * 4 * (int64_t)H, n_ih = rows * Kpad, groups = rows * H / 8;
   MA_LAUNCH(lstm_pack_ih_kernel, dim3((unsigned)((n_ih + 255) / 256)), dim3(256), 0, (hipStream_t)stream, w_ih, b_ih, b_hh, K, Kpad, rows,
             reinterpret_cast<uint16_t*>(wih_bf16), bias);
@@ -365,9 +289,7 @@ int ma_lstm_bidir_bf16(const void* x, int64_t T, int64_t B, int32_t Kpad, int32_
       dir_mask < 1 || dir_mask > 3)
     return MA_ERR_INVALID_ARG;
   if (!lstm_shape_ok(T, B, Kpad, H)) return MA_ERR_UNSUPPORTED;
-  if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(wih_bf16) | reinterpret_cast<uintptr_t>(whh_packed) |
-       reinterpret_cast<uintptr_t>(bias) | reinterpret_cast<uintptr_t>(workspace)) & 15)
-    return MA_ERR_INVALID_ARG;
+  if (!lstm_aligned16(x, wih_bf16, whh_packed, bias, workspace)) return MA_ERR_INVALID_ARG;
   const int64_t chunk = time_chunk < T ? time_chunk : T;
   const LstmWs ws = lstm_ws(B, H, chunk);
   if (workspace_bytes < ws.total) return MA_ERR_WORKSPACE;

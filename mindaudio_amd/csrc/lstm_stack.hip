@@ -1,5 +1,6 @@
 // Layer-pipelined unidirectional LSTM stack, inference (mindaudio/models/tasnet.py Separator: nn.LSTM(N, hidden, num_layers,
-// bidirectional=False)).  Contract: include/mindaudio_amd.h.
+// bidirectional=False)).  Contract: include/mindaudio_amd.h.  The tile, the cell, the packed weights' fragment order and the K loop
+// are lstm_common.h's; this file holds the schedule, the state's parity argument and the two ways a workgroup covers its batch rows.
 //
 // Schedule.  Layer l at time t needs layer l - 1 at time t and itself at t - 1, so every (l, t) with t + l = d can run at once.  The host
 // loop of ma_lstm_stack_bf16 walks the diagonals d = 0 .. T + n_layers - 2 and issues ONE LAUNCH PER DIAGONAL; blockIdx.y spans the
@@ -7,20 +8,14 @@
 // those launches is the only synchronisation: no workgroup ever waits for another one (no grid barrier, no flags, no cooperative
 // launch, no atomics, no graph capture).
 //
-// Cell.  gates (B, 4H) = [x_t | h_{t-1}] . [W_ih | W_hh]^T + (b_ih + b_hh), PyTorch gate order i, f, g, o, in ONE K loop of
-// v_mfma_f32_16x16x32_bf16 over K = Kin + H (Kin = Kpad for layer 0, H above it): there is no projection GEMM and no projection buffer.
-// A tile is 16 batch rows x 16 hidden units with all four gate rows of those units, as in lstm.hip: the C/D map (column = lane & 15,
-// row = 4 (lane >> 4) + register) puts the four gates of one (batch row, hidden unit) into the same lane and register index, so the
-// bias add, two sigmoids, two tanhs, the float32 c update and every store are lane-local.  The bias and c are loaded before the K loop.
-// The weights are packed once per layer (ma_lstm_stack_pack_f32) in fragment order [slice of 16 units][k-step of 32][gate][lane][8]:
-// the four gate fragments of a k-step are one 4 KiB run.  The A operand of layer 0 is x[t], that of layer l >= 1 the bf16 h image of
-// layer l - 1; the recurrent half of K reads the layer's own h image.  Two forms:
+// Cell.  gates (B, 4H) = [x_t | h_{t-1}] . [W_ih | W_hh]^T + (b_ih + b_hh) in ONE K loop over K = Kin + H (Kin = Kpad for layer 0, H
+// above it): there is no projection GEMM and no projection buffer.  The weights are packed once per layer (ma_lstm_stack_pack_f32).
+// The A operand of layer 0 is x[t], that of layer l >= 1 the bf16 h image of layer l - 1; the recurrent half of K reads the layer's
+// own h image.  Two forms:
 //   lstm_stack_ksplit_kernel (B <= 16, one batch tile): the four waves split the k-steps between them (32 at H = Kpad = 512: 8 each,
 //     all in flight at once), leave their partial gate sums in LDS (16 KB) and meet at one workgroup barrier; then wave w sums the four
 //     partials IN WAVE ORDER for register index w (batch rows 4 (lane >> 4) + w) and runs that quarter of the cell.
 //   lstm_stack_tile_kernel (B > 16): grid.z = ceil(B / 64), wave w runs all of K for batch rows 64 z + 16 w .. + 15; no LDS, no barrier.
-// Rows beyond B are never read for their own sake (their lanes take row 0's operand; an MFMA row depends on its own A row only) and
-// never stored.
 //
 // State and the parity argument.  Per layer: TWO (B, H) bf16 images of h and one (B, H) float32 c.
 //   (1) every write of h on diagonal d goes to image d & 1 of the writing layer;
@@ -44,14 +39,11 @@
 
 #include "../../include/mindaudio_amd.h"
 
-#include "device_common.h"
 #include "launch.h"
+#include "lstm_common.h"
 
 namespace ma {
 
-constexpr int kStackThreads = 256;
-constexpr int kStackSlice = 16;      // hidden units of a workgroup (x 4 gate rows)
-constexpr int kStackRowsPerWg = 64;  // batch rows of a tile-kernel workgroup: 16 per wave
 constexpr int kStackMaxLayers = 8;
 
 struct StackStep {
@@ -67,8 +59,6 @@ struct StackStep {
   int64_t T, d;
   int32_t l0, n_layers, B, H, Kpad;
 };
-
-__device__ __forceinline__ float stack_sigmoid(float v) { return 1.0f / (1.0f + expf(-v)); }
 
 // where layer l on diagonal d finds its operands and leaves its state
 struct StackLayer {
@@ -100,85 +90,61 @@ __device__ __forceinline__ StackLayer stack_layer(const StackStep& p) {
   return s;
 }
 
-// The cell of one (batch row b, hidden unit j): gate sums in, c and h out.  Lane-local.
+// The A operand of one batch tile: k-steps below nk_in come from the layer's input, the rest from its own h image.
+struct StackA {
+  const uint16_t *in, *h;  // this lane's row (rows beyond B take row 0's) at the lane's column of k-step 0 of each half;
+  int nk_in;               // `h` is biased by the input half's width, so that both halves are addressed by the k-step index alone
+  __device__ __forceinline__ StackA(const StackStep& p, const StackLayer& s, int b0, int lane) : nk_in(s.nk_in) {
+    const int arow = b0 + (lane & 15) < p.B ? b0 + (lane & 15) : 0;
+    in = s.in + (int64_t)arow * s.ld_in + 8 * (lane >> 4);
+    h = s.h_prev + (int64_t)arow * p.H + 8 * (lane >> 4) - (int64_t)s.nk_in * 32;
+  }
+  __device__ __forceinline__ const uint16_t* operator()(int, int kk) const { return (kk < nk_in ? in : h) + kk * 32; }
+};
+
+// The cell of one (batch row b, hidden unit j) and where its state and outputs go.  Lane-local.
 __device__ __forceinline__ void stack_cell(const StackStep& p, const StackLayer& s, int b, int j, float gi, float gf, float gg, float go,
                                            float c_prev) {
   const int64_t e = (int64_t)b * p.H + j;
-  const float cn = stack_sigmoid(gf) * c_prev + stack_sigmoid(gi) * tanhf(gg);
-  const float h = stack_sigmoid(go) * tanhf(cn);
-  s.c[e] = cn;
-  s.h_next[e] = f2bf(h);
+  const LstmCell n = lstm_cell(gi, gf, gg, go, c_prev);
+  s.c[e] = n.c;
+  s.h_next[e] = f2bf(n.h);
   if (s.l == p.n_layers - 1) {
     const int64_t o = s.t * p.B * (int64_t)p.H + e;
-    p.out_f32[o] = h;
-    if (p.out_bf16) p.out_bf16[o] = f2bf(h);
+    p.out_f32[o] = n.h;
+    if (p.out_bf16) p.out_bf16[o] = f2bf(n.h);
   }
   if (s.t == p.T - 1) {
     const int64_t o = (int64_t)s.l * p.B * p.H + e;
-    if (p.h_final) p.h_final[o] = h;
-    if (p.c_final) p.c_final[o] = cn;
+    if (p.h_final) p.h_final[o] = n.h;
+    if (p.c_final) p.c_final[o] = n.c;
   }
 }
 
 // B <= 16.  KB = k-steps per operand block; the launcher picks it so that every wave's share nk / 4 is a multiple of KB (KB = 1 also
 // serves an nk that is no multiple of 4: the shares are then [w nk / 4, (w + 1) nk / 4), each at least one k-step since nk >= 4).
-// Two blocks are in registers: the loads of block i + 1 are issued before the MFMAs of block i.
 template <int KB>
-__global__ __launch_bounds__(kStackThreads) void lstm_stack_ksplit_kernel(const StackStep p) {
+__global__ __launch_bounds__(kLstmThreads) void lstm_stack_ksplit_kernel(const StackStep p) {
   __shared__ float part[4 * 16 * 64];  // [source wave][gate * 4 + register][lane]
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const StackLayer s = stack_layer(p);
   const int H = p.H, sl = blockIdx.x;
-  const int k0 = wave * s.nk / 4, k1 = (wave + 1) * s.nk / 4;
-  const int arow = (lane & 15) < p.B ? (lane & 15) : 0;
-  const uint16_t* ain = s.in + (int64_t)arow * s.ld_in + 8 * (lane >> 4);
-  // (biased by the input half's width, so that both halves are addressed by the k-step index alone: used for kk >= nk_in only)
-  const uint16_t* ah = s.h_prev + (int64_t)arow * H + 8 * (lane >> 4) - (int64_t)s.nk_in * 32;
-  const uint16_t* wp = s.w + (((int64_t)sl * s.nk * 4) * 64 + lane) * 8;
-
-  struct Operands {
-    bf16x8 a[KB];
-    bf16x8 w[KB][4];
-  };
-  auto load = [&](Operands& o, int kk0) __attribute__((always_inline)) {
-#pragma unroll
-    for (int u = 0; u < KB; ++u) {
-      const int kk = kk0 + u;
-#pragma unroll
-      for (int g = 0; g < 4; ++g) o.w[u][g] = *reinterpret_cast<const bf16x8*>(wp + ((int64_t)kk * 4 + g) * 512);
-      o.a[u] = *reinterpret_cast<const bf16x8*>((kk < s.nk_in ? ain : ah) + kk * 32);
-    }
-  };
-  f32x4 acc[4];
-#pragma unroll
-  for (int g = 0; g < 4; ++g) acc[g] = f32x4{0.f, 0.f, 0.f, 0.f};
-  auto mma = [&](const Operands& o) __attribute__((always_inline)) {
-#pragma unroll
-    for (int u = 0; u < KB; ++u)
-#pragma unroll
-      for (int g = 0; g < 4; ++g) acc[g] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(o.a[u], o.w[u][g], acc[g], 0, 0, 0);
-  };
-  Operands cur, nxt;
-  load(cur, k0);
   // this thread's quarter of the cell: register index `wave` of the C/D map
-  const int b = 4 * (lane >> 4) + wave, j = sl * kStackSlice + (lane & 15);
+  const int b = 4 * (lane >> 4) + wave, j = sl * kLstmSlice + (lane & 15);
   const bool ok = b < p.B;
-  float bias[4];
+  f32x4 acc[1][4];
+  float bias[4], c_prev;
+  lstm_k_loop<KB>(lstm_gate_run(s.w, s.nk, sl, 0, lane), StackA(p, s, 0, lane), wave * s.nk / 4, (wave + 1) * s.nk / 4, acc, [&] {
 #pragma unroll
-  for (int g = 0; g < 4; ++g) bias[g] = s.bias[g * H + j];
-  const float c_prev = ok ? s.c[(int64_t)b * H + j] : 0.0f;
-  for (int kk = k0 + KB; kk < k1; kk += KB) {  // ((k1 - k0) % KB == 0: the launcher's choice of KB)
-    load(nxt, kk);
-    mma(cur);
-    cur = nxt;
-  }
-  mma(cur);
+    for (int g = 0; g < 4; ++g) bias[g] = s.bias[g * H + j];
+    c_prev = ok ? s.c[(int64_t)b * H + j] : 0.0f;
+  });
 
   float* dst = part + (wave * 16) * 64 + lane;
 #pragma unroll
   for (int g = 0; g < 4; ++g)
 #pragma unroll
-    for (int r = 0; r < 4; ++r) dst[(g * 4 + r) * 64] = acc[g][r];
+    for (int r = 0; r < 4; ++r) dst[(g * 4 + r) * 64] = acc[0][g][r];
   __syncthreads();  // (within the workgroup; every wave arrives: nothing returns before this line)
   float gate[4];
 #pragma unroll
@@ -192,100 +158,44 @@ __global__ __launch_bounds__(kStackThreads) void lstm_stack_ksplit_kernel(const 
 }
 
 // B > 16: each wave runs all of K for its own 16 batch rows (nk is even: blocks of 2 k-steps).
-__global__ __launch_bounds__(kStackThreads) void lstm_stack_tile_kernel(const StackStep p) {
-  constexpr int KB = 2;
+__global__ __launch_bounds__(kLstmThreads) void lstm_stack_tile_kernel(const StackStep p) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int b0 = ((int)blockIdx.z * 4 + wave) * 16;
   if (b0 >= p.B) return;  // (no barrier anywhere in this kernel)
   const StackLayer s = stack_layer(p);
   const int H = p.H, sl = blockIdx.x;
-  const int arow = b0 + (lane & 15) < p.B ? b0 + (lane & 15) : 0;
-  const uint16_t* ain = s.in + (int64_t)arow * s.ld_in + 8 * (lane >> 4);
-  // (biased by the input half's width, so that both halves are addressed by the k-step index alone: used for kk >= nk_in only)
-  const uint16_t* ah = s.h_prev + (int64_t)arow * H + 8 * (lane >> 4) - (int64_t)s.nk_in * 32;
-  const uint16_t* wp = s.w + (((int64_t)sl * s.nk * 4) * 64 + lane) * 8;
-
-  struct Operands {
-    bf16x8 a[KB];
-    bf16x8 w[KB][4];
-  };
-  auto load = [&](Operands& o, int kk0) __attribute__((always_inline)) {
-#pragma unroll
-    for (int u = 0; u < KB; ++u) {
-      const int kk = kk0 + u;
-#pragma unroll
-      for (int g = 0; g < 4; ++g) o.w[u][g] = *reinterpret_cast<const bf16x8*>(wp + ((int64_t)kk * 4 + g) * 512);
-      o.a[u] = *reinterpret_cast<const bf16x8*>((kk < s.nk_in ? ain : ah) + kk * 32);
-    }
-  };
-  f32x4 acc[4];
-#pragma unroll
-  for (int g = 0; g < 4; ++g) acc[g] = f32x4{0.f, 0.f, 0.f, 0.f};
-  auto mma = [&](const Operands& o) __attribute__((always_inline)) {
-#pragma unroll
-    for (int u = 0; u < KB; ++u)
-#pragma unroll
-      for (int g = 0; g < 4; ++g) acc[g] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(o.a[u], o.w[u][g], acc[g], 0, 0, 0);
-  };
-  Operands cur, nxt;
-  load(cur, 0);
-  const int j = sl * kStackSlice + (lane & 15);
+  const int j = sl * kLstmSlice + (lane & 15);
+  f32x4 acc[1][4];
   float bias[4], c_prev[4];
+  lstm_k_loop<2>(lstm_gate_run(s.w, s.nk, sl, 0, lane), StackA(p, s, b0, lane), 0, s.nk, acc, [&] {
 #pragma unroll
-  for (int g = 0; g < 4; ++g) bias[g] = s.bias[g * H + j];
+    for (int g = 0; g < 4; ++g) bias[g] = s.bias[g * H + j];
 #pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    const int b = b0 + 4 * (lane >> 4) + r;
-    c_prev[r] = b < p.B ? s.c[(int64_t)b * H + j] : 0.0f;
-  }
-  for (int kk = KB; kk < s.nk; kk += KB) {
-    load(nxt, kk);
-    mma(cur);
-    cur = nxt;
-  }
-  mma(cur);
+    for (int r = 0; r < 4; ++r) {
+      const int b = b0 + 4 * (lane >> 4) + r;
+      c_prev[r] = b < p.B ? s.c[(int64_t)b * H + j] : 0.0f;
+    }
+  });
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
     const int b = b0 + 4 * (lane >> 4) + r;
-    if (b < p.B) stack_cell(p, s, b, j, acc[0][r] + bias[0], acc[1][r] + bias[1], acc[2][r] + bias[2], acc[3][r] + bias[3], c_prev[r]);
+    if (b < p.B)
+      stack_cell(p, s, b, j, acc[0][0][r] + bias[0], acc[0][1][r] + bias[1], acc[0][2][r] + bias[2], acc[0][3][r] + bias[3], c_prev[r]);
   }
 }
 
-// [W_ih | W_hh] of one layer -> fragment order [slice][k-step][gate][lane][8]; columns K .. Kpad - 1 of the W_ih half are zero;
-// bias = b_ih + b_hh
+// [W_ih | W_hh] of one layer -> fragment order; columns K .. Kpad - 1 of the W_ih half are zero; bias = b_ih + b_hh
 __global__ __launch_bounds__(256) void lstm_stack_pack_kernel(const float* __restrict__ w_ih, const float* __restrict__ w_hh,
                                                               const float* __restrict__ b_ih, const float* __restrict__ b_hh, int K, int Kpad,
                                                               int H, int64_t groups, uint16_t* __restrict__ out, float* __restrict__ bias) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;  // one 8-element fragment
   if (i < 4 * (int64_t)H) bias[i] = b_ih[i] + b_hh[i];
   if (i >= groups) return;
-  const int nk_in = Kpad / 32, nk = nk_in + H / 32;
-  const int lane = (int)(i & 63);
-  int64_t q = i >> 6;
-  const int g = (int)(q & 3);
-  q >>= 2;
-  const int kk = (int)(q % nk);
-  const int sl = (int)(q / nk);
-  const int64_t row = (int64_t)g * H + sl * kStackSlice + (lane & 15);
-  float v[8];
-  if (kk < nk_in) {
-    const int k = kk * 32 + 8 * (lane >> 4);
-#pragma unroll
-    for (int e = 0; e < 8; ++e) v[e] = k + e < K ? w_ih[row * K + k + e] : 0.0f;
-  } else {
-    const float* src = w_hh + row * H + (kk - nk_in) * 32 + 8 * (lane >> 4);
-#pragma unroll
-    for (int e = 0; e < 8; ++e) v[e] = src[e];
-  }
-  u32x4 o;
-  o[0] = pack2_bf16(v[0], v[1]);
-  o[1] = pack2_bf16(v[2], v[3]);
-  o[2] = pack2_bf16(v[4], v[5]);
-  o[3] = pack2_bf16(v[6], v[7]);
-  *reinterpret_cast<u32x4*>(out + i * 8) = o;
+  const LstmFragment f = lstm_fragment(i, (Kpad + H) / 32);
+  const int64_t row = (int64_t)f.gate * H + f.unit;
+  if (f.k < Kpad) lstm_pack_fragment(w_ih + row * K, f.k, K, out + i * 8);
+  else lstm_pack_fragment(w_hh + row * H, f.k - Kpad, H, out + i * 8);
 }
-
-static int64_t stack_align256(int64_t v) { return (v + 255) & ~(int64_t)255; }
 
 struct StackWs {
   int64_t h, c, total;  // byte offsets
@@ -293,14 +203,13 @@ struct StackWs {
 static StackWs stack_ws(int64_t B, int64_t H, int64_t n_layers) {
   StackWs w;
   w.h = 0;
-  w.c = w.h + stack_align256(n_layers * 2 * B * H * 2);
-  w.total = w.c + stack_align256(n_layers * B * H * 4);
+  w.c = w.h + align256(n_layers * 2 * B * H * 2);
+  w.total = w.c + align256(n_layers * B * H * 4);
   return w;
 }
 
 static bool stack_shape_ok(int64_t T, int64_t B, int64_t Kpad, int64_t H, int64_t n_layers) {
-  return T >= 1 && B >= 1 && H >= 64 && H % 64 == 0 && H <= 4096 && Kpad >= 64 && Kpad % 64 == 0 && n_layers >= 1 &&
-         n_layers <= kStackMaxLayers && B <= 65535 * (int64_t)kStackRowsPerWg && B * 4 * H <= 0x7fffffff && Kpad <= 0x3fffffff;
+  return lstm_shape_ok(T, B, Kpad, H) && n_layers >= 1 && n_layers <= kStackMaxLayers && Kpad <= 0x3fffffff;
 }
 
 }  // namespace ma
@@ -319,7 +228,7 @@ int ma_lstm_stack_pack_f32(const float* w_ih, const float* w_hh, const float* b_
                            void* packed, float* bias, ma_stream_t stream) {
   if (!w_ih || !w_hh || !b_ih || !b_hh || !packed || !bias || K < 1 || Kpad < K || H < 1) return MA_ERR_INVALID_ARG;
   if (!stack_shape_ok(1, 1, Kpad, H, 1)) return MA_ERR_UNSUPPORTED;
-  if ((reinterpret_cast<uintptr_t>(packed) | reinterpret_cast<uintptr_t>(bias)) & 15) return MA_ERR_INVALID_ARG;
+  if (!lstm_aligned16(packed, bias)) return MA_ERR_INVALID_ARG;
   const int64_t groups = 4 * (int64_t)H * (Kpad + H) / 8;
   MA_LAUNCH(lstm_stack_pack_kernel, dim3((unsigned)((groups + 255) / 256)), dim3(256), 0, (hipStream_t)stream, w_ih, w_hh, b_ih, b_hh, K,
             Kpad, H, groups, reinterpret_cast<uint16_t*>(packed), bias);
@@ -331,12 +240,9 @@ int ma_lstm_stack_bf16(const void* x, int64_t T, int64_t B, int32_t Kpad, int32_
                        int64_t workspace_bytes, ma_stream_t stream) {
   if (!x || !packed || !bias || !out_f32 || !workspace || T < 1 || B < 1 || Kpad < 1 || H < 1 || n_layers < 1) return MA_ERR_INVALID_ARG;
   if (!stack_shape_ok(T, B, Kpad, H, n_layers)) return MA_ERR_UNSUPPORTED;
-  uintptr_t bits = reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(workspace);
-  for (int l = 0; l < n_layers; ++l) {
-    if (!packed[l] || !bias[l]) return MA_ERR_INVALID_ARG;
-    bits |= reinterpret_cast<uintptr_t>(packed[l]) | reinterpret_cast<uintptr_t>(bias[l]);
-  }
-  if (bits & 15) return MA_ERR_INVALID_ARG;
+  for (int l = 0; l < n_layers; ++l)
+    if (!packed[l] || !bias[l] || !lstm_aligned16(packed[l], bias[l])) return MA_ERR_INVALID_ARG;
+  if (!lstm_aligned16(x, workspace)) return MA_ERR_INVALID_ARG;
   const StackWs ws = stack_ws(B, H, n_layers);
   if (workspace_bytes < ws.total) return MA_ERR_WORKSPACE;
   hipStream_t st = (hipStream_t)stream;
@@ -370,21 +276,21 @@ int ma_lstm_stack_bf16(const void* x, int64_t T, int64_t B, int32_t Kpad, int32_
   auto block_of = [](int nk) { return nk % 32 == 0 ? 8 : nk % 16 == 0 ? 4 : nk % 8 == 0 ? 2 : 1; };
   const int kb_all = n_layers > 1 ? (block_of(nk0) < block_of(nk1) ? block_of(nk0) : block_of(nk1)) : block_of(nk0);
   const int kb_upper = block_of(nk1);
-  const unsigned gz = small ? 1u : (unsigned)((B + kStackRowsPerWg - 1) / kStackRowsPerWg);
+  const unsigned gz = small ? 1u : (unsigned)((B + kLstmRowsPerWg - 1) / kLstmRowsPerWg);
   for (int64_t d = 0; d < T + n_layers - 1; ++d) {
     const int l0 = (int)(d - T + 1 > 0 ? d - T + 1 : 0), l1 = (int)(d < n_layers - 1 ? d : n_layers - 1);
     p.d = d;
     p.l0 = l0;
-    const dim3 grid((unsigned)(H / kStackSlice), (unsigned)(l1 - l0 + 1), gz);
+    const dim3 grid((unsigned)(H / kLstmSlice), (unsigned)(l1 - l0 + 1), gz);
     if (!small) {
-      MA_LAUNCH(lstm_stack_tile_kernel, grid, dim3(kStackThreads), 0, st, p);
+      MA_LAUNCH(lstm_stack_tile_kernel, grid, dim3(kLstmThreads), 0, st, p);
       continue;
     }
     const int kb = l0 == 0 ? kb_all : kb_upper;
-    if (kb == 8) MA_LAUNCH(lstm_stack_ksplit_kernel<8>, grid, dim3(kStackThreads), 0, st, p);
-    else if (kb == 4) MA_LAUNCH(lstm_stack_ksplit_kernel<4>, grid, dim3(kStackThreads), 0, st, p);
-    else if (kb == 2) MA_LAUNCH(lstm_stack_ksplit_kernel<2>, grid, dim3(kStackThreads), 0, st, p);
-    else MA_LAUNCH(lstm_stack_ksplit_kernel<1>, grid, dim3(kStackThreads), 0, st, p);
+    if (kb == 8) MA_LAUNCH(lstm_stack_ksplit_kernel<8>, grid, dim3(kLstmThreads), 0, st, p);
+    else if (kb == 4) MA_LAUNCH(lstm_stack_ksplit_kernel<4>, grid, dim3(kLstmThreads), 0, st, p);
+    else if (kb == 2) MA_LAUNCH(lstm_stack_ksplit_kernel<2>, grid, dim3(kLstmThreads), 0, st, p);
+    else MA_LAUNCH(lstm_stack_ksplit_kernel<1>, grid, dim3(kLstmThreads), 0, st, p);
   }
   return MA_OK;
 }

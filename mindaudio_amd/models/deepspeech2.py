@@ -19,6 +19,7 @@ import torch
 import torch.nn as nn
 
 from .. import _host, _lib
+from . import _lstm
 
 __all__ = ["DeepSpeechModel", "PredictWithSoftmax", "fold_batchnorm", "permute_wih_columns"]
 
@@ -85,10 +86,6 @@ class _SequenceWise(nn.Module):
         self.module = module
 
 
-def _ceil64(n):
-    return (n + 63) // 64 * 64
-
-
 class DeepSpeechModel(nn.Module):
     """DeepSpeechModel(batch_size, labels, rnn_hidden_size, nb_layers, audio_conf, rnn_type="LSTM", bidirectional=True): the
     reference's signature.  Not built (NotImplementedError): rnn_type != "LSTM", bidirectional=False, rnn_hidden_size % 64 != 0.
@@ -141,14 +138,7 @@ class DeepSpeechModel(nn.Module):
     # ---- weights ---------------------------------------------------------------------------------------------------------------
     def load_weights(self, params, strict=True):
         """{reference name: array} -> the module's parameters (the names of utils.ckpt.convert_deepspeech2_names)."""
-        own = self.state_dict()
-        state = {k: torch.as_tensor(np.asarray(v)).to(own[k].dtype) for k, v in params.items() if k in own}
-        missing = [k for k in own if k not in state]
-        unexpected = [k for k in params if k not in own]
-        if strict and (missing or unexpected):
-            raise KeyError("parameters do not match the model: missing %s, unexpected %s" % (missing[:8], unexpected[:8]))
-        self.load_state_dict(state, strict=False)
-        return missing, unexpected
+        return _lstm.load_named_weights(self, params, strict)
 
     def load_checkpoint(self, path, strict=True):
         from ..utils.ckpt import load_mindspore_checkpoint
@@ -158,10 +148,8 @@ class DeepSpeechModel(nn.Module):
     @torch.no_grad()
     def prepare(self):
         dev = self.fc.module.weight.device
-        lib, f32, bf = _lib.load(), torch.float32, torch.bfloat16
-        H = self.hidden_size
+        f32, bf = torch.float32, torch.bfloat16
         self._ws = {}
-        s = _host.current_stream_ptr()
         c = self.conv
         P = {"layers": []}
         P["w1t"] = c.conv1.weight.detach().to(f32).reshape(32, 41 * 11).t().contiguous()  # (451, 32)
@@ -173,22 +161,11 @@ class DeepSpeechModel(nn.Module):
         w2[:, :, :21, :] = c.conv2.weight.detach().to(f32).permute(0, 3, 2, 1)
         P["w2"] = w2.reshape(32, 11 * 704).to(bf).contiguous()
         for k, cell in enumerate(self.RNN.lstms):
-            K = self.rnn_input_size if k == 0 else H
-            Kpad = _ceil64(K)
-
-            def both(name):
-                a, b = getattr(cell, name + "_l0").detach().to(f32), getattr(cell, name + "_l0_reverse").detach().to(f32)
-                if name == "weight_ih" and k == 0:
-                    a, b = permute_wih_columns(a, 32, self.F2), permute_wih_columns(b, 32, self.F2)
-                return torch.stack([a, b]).contiguous()
-
-            wih, whh = torch.empty((2, 4 * H, Kpad), dtype=bf, device=dev), torch.empty((2 * 4 * H * H,), dtype=bf, device=dev)
-            bias = torch.empty((2, 4 * H), dtype=f32, device=dev)
-            src = [both(n) for n in ("weight_ih", "weight_hh", "bias_ih", "bias_hh")]
-            _lib.check(lib.ma_lstm_pack_f32(src[0].data_ptr(), src[1].data_ptr(), src[2].data_ptr(), src[3].data_ptr(), K, Kpad, H,
-                                            wih.data_ptr(), whh.data_ptr(), bias.data_ptr(), s), "lstm_pack")
-            torch.cuda.current_stream().synchronize()  # (`src` goes out of scope)
-            P["layers"].append(dict(wih=wih, whh=whh, bias=bias, Kpad=Kpad))
+            fwd, bwd = ([getattr(cell, n + "_l0" + d).detach().to(f32) for n in ("weight_ih", "weight_hh", "bias_ih", "bias_hh")]
+                        for d in ("", "_reverse"))
+            if k == 0:
+                fwd[0], bwd[0] = permute_wih_columns(fwd[0], 32, self.F2), permute_wih_columns(bwd[0], 32, self.F2)
+            P["layers"].append(_lstm.pack_bidir_layer(fwd, bwd, self.rnn_input_size if k == 0 else self.hidden_size, self.hidden_size))
         P["fc"] = self.fc.module.weight.detach().to(bf).contiguous()
         self._prepared = P
         return self
@@ -199,20 +176,13 @@ class DeepSpeechModel(nn.Module):
         if ws is None:
             if len(self._ws) >= 2:
                 self._ws.clear()
-            lib, H, bf, f32 = _lib.load(), self.hidden_size, torch.bfloat16, torch.float32
+            bf = torch.bfloat16
             T1 = (T - 1) // 2 + 1
             Fpad = 2 * (self.F2 - 1) + 22
-            chunk = max(1, min(T1, (1 << 26) // (B * 4 * H)))
-            nbytes = lib.ma_lstm_workspace_bytes(T1, B, H, chunk)
-            if nbytes < 0:
-                _lib.check(int(nbytes), "lstm_workspace_bytes")
             ws = self._ws[key] = dict(
-                T1=T1, Fpad=Fpad, chunk=chunk,
+                _lstm.layer_buffers(T1, B, self.hidden_size, dev), T1=T1, Fpad=Fpad,
                 act1=torch.zeros((T1 + 10, B, Fpad * 32), dtype=bf, device=dev),  # halo frames and padding rows stay zero
-                xin=torch.zeros((T1, B, _ceil64(self.rnn_input_size)), dtype=bf, device=dev),  # columns past 32 F2 stay zero
-                hf=[torch.empty((T1, B, H), dtype=f32, device=dev) for _ in range(2)],
-                hb=[torch.empty((T1, B, H), dtype=bf, device=dev) for _ in range(2)],
-                lstm=torch.empty((int(nbytes),), dtype=torch.uint8, device=dev))
+                xin=torch.zeros((T1, B, _lstm.ceil64(self.rnn_input_size)), dtype=bf, device=dev))  # columns past 32 F2 stay zero
         return ws
 
     # ---- forward ---------------------------------------------------------------------------------------------------------------
@@ -251,19 +221,8 @@ class DeepSpeechModel(nn.Module):
     @torch.no_grad()
     def lstm_stack(self, xin):
         """The BatchRNN on a (T1, B, Kpad) bf16 input: (float32 (T1, B, H), its bf16 rounding) of the last layer."""
-        P, lib, H = self._prepared, _lib.load(), self.hidden_size
-        T1, B, _ = xin.shape
         ws = next(w for w in self._ws.values() if w["xin"] is xin)
-        cur = xin
-        with _host.pinned_stream():
-            s = _host.current_stream_ptr()
-            for k, L in enumerate(P["layers"]):
-                of, ob = ws["hf"][k & 1], ws["hb"][k & 1]
-                _lib.check(lib.ma_lstm_bidir_bf16(cur.data_ptr(), T1, B, L["Kpad"], H, L["wih"].data_ptr(), L["whh"].data_ptr(),
-                                                  L["bias"].data_ptr(), 3, ws["chunk"], of.data_ptr(), ob.data_ptr(), None,
-                                                  ws["lstm"].data_ptr(), ws["lstm"].numel(), s), "lstm_bidir")
-                cur = ob
-        return of, ob
+        return _lstm.run_layers(self._prepared["layers"], xin, self.hidden_size, 3, ws)
 
     @torch.no_grad()
     def forward(self, x, lengths):

@@ -19,6 +19,7 @@ import torch
 import torch.nn as nn
 
 from .. import _host, _lib
+from . import _lstm
 
 __all__ = ["TasNet"]
 
@@ -68,10 +69,6 @@ class _Decoder(nn.Module):
         nn.init.xavier_uniform_(self.basis_signals.weight)
 
 
-def _ceil64(n):
-    return (n + 63) // 64 * 64
-
-
 class TasNet(nn.Module):
     """TasNet(L, N, hidden_size, num_layers, bidirectional=False, nspk=2, schedule="pipelined"): the reference's arguments plus
     `schedule` ("pipelined" | "layered", see the module docstring; it may also be set on the instance between calls).
@@ -110,15 +107,7 @@ class TasNet(nn.Module):
         or MindSpore's (N, L, 1, 1))."""
         from ..utils.ckpt import convert_tasnet_names
 
-        params = convert_tasnet_names(state)
-        own = self.state_dict()
-        new = {k: torch.as_tensor(np.asarray(v)).to(own[k].dtype).reshape(own[k].shape) for k, v in params.items() if k in own}
-        missing = [k for k in own if k not in new]
-        unexpected = [k for k in params if k not in own]
-        if strict and (missing or unexpected):
-            raise KeyError("parameters do not match the model: missing %s, unexpected %s" % (missing[:8], unexpected[:8]))
-        self.load_state_dict(new, strict=False)
-        return missing, unexpected
+        return _lstm.load_named_weights(self, convert_tasnet_names(state), strict, reshape=True)
 
     def load_checkpoint(self, path, strict=True):
         from ..utils.ckpt import load_mindspore_checkpoint
@@ -128,11 +117,9 @@ class TasNet(nn.Module):
     @torch.no_grad()
     def prepare(self):
         """Device copies in the kernels' layouts: transposed encoder weights, both packings of the LSTM weights, the bf16 fc weight."""
-        dev = self.separator.fc.weight.device
-        lib, f32, bf = _lib.load(), torch.float32, torch.bfloat16
+        f32, bf = torch.float32, torch.bfloat16
         H, N = self.hidden_size, self.N
         self._ws = {}
-        s = _host.current_stream_ptr()
         enc, sep, lstm = self.encoder, self.separator, self.separator.lstm
 
         def f(t):
@@ -143,26 +130,14 @@ class TasNet(nn.Module):
              "gamma": f(sep.layer_norm.gamma), "beta": f(sep.layer_norm.beta),
              "fc": sep.fc.weight.detach().to(bf).contiguous(), "fc_bias": f(sep.fc.bias),
              "basis": f(self.decoder.basis_signals.weight), "basis_bias": f(self.decoder.basis_signals.bias),  # (L, N), (L)
-             "layers": []}
+             "layers": [], "layered": []}  # one entry per layer and schedule: pipelined, layered
         for k in range(self.num_layers):
             K = N if k == 0 else H
-            Kpad = _ceil64(K)
             src = [f(getattr(lstm, "%s_l%d" % (n, k))) for n in ("weight_ih", "weight_hh", "bias_ih", "bias_hh")]
-            packed = torch.empty((4 * H * (Kpad + H),), dtype=bf, device=dev)
-            bias = torch.empty((4 * H,), dtype=f32, device=dev)
-            _lib.check(lib.ma_lstm_stack_pack_f32(src[0].data_ptr(), src[1].data_ptr(), src[2].data_ptr(), src[3].data_ptr(), K, Kpad, H,
-                                                  packed.data_ptr(), bias.data_ptr(), s), "lstm_stack_pack")
-            # the layered schedule's operands: ma_lstm_pack_f32 takes both directions stacked; the reverse half is zero and never run
-            two = [torch.stack([a, torch.zeros_like(a)]).contiguous() for a in src]
-            wih, whh = torch.empty((2, 4 * H, Kpad), dtype=bf, device=dev), torch.empty((2 * 4 * H * H,), dtype=bf, device=dev)
-            bias2 = torch.empty((2, 4 * H), dtype=f32, device=dev)
-            _lib.check(lib.ma_lstm_pack_f32(two[0].data_ptr(), two[1].data_ptr(), two[2].data_ptr(), two[3].data_ptr(), K, Kpad, H,
-                                            wih.data_ptr(), whh.data_ptr(), bias2.data_ptr(), s), "lstm_pack")
-            torch.cuda.current_stream().synchronize()  # (`src` and `two` go out of scope)
-            P["layers"].append(dict(packed=packed, bias=bias, wih=wih, whh=whh, bias2=bias2, Kpad=Kpad))
-        n = self.num_layers
-        P["packed_ptrs"] = (ctypes.c_void_p * n)(*[L["packed"].data_ptr() for L in P["layers"]])
-        P["bias_ptrs"] = (ctypes.c_void_p * n)(*[L["bias"].data_ptr() for L in P["layers"]])
+            P["layers"].append(_lstm.pack_stack_layer(src, K, H))
+            P["layered"].append(_lstm.pack_bidir_layer(src, None, K, H))
+        for what in ("packed", "bias"):  # ma_lstm_stack_bf16 takes one pointer per layer
+            P[what + "_ptrs"] = (ctypes.c_void_p * self.num_layers)(*[L[what].data_ptr() for L in P["layers"]])
         self._prepared = P
         return self
 
@@ -172,22 +147,17 @@ class TasNet(nn.Module):
         if ws is None:
             if len(self._ws) >= 2:
                 self._ws.clear()
-            lib, H, N, bf, f32 = _lib.load(), self.hidden_size, self.N, torch.bfloat16, torch.float32
-            chunk = max(1, min(K, (1 << 26) // (B * 4 * H)))
-            sizes = (lib.ma_lstm_stack_workspace_bytes(K, B, H, self.num_layers), lib.ma_lstm_workspace_bytes(K, B, H, chunk))
-            for v, what in zip(sizes, ("lstm_stack_workspace_bytes", "lstm_workspace_bytes")):
-                if v < 0:
-                    _lib.check(int(v), what)
+            H, N, f32 = self.hidden_size, self.N, torch.float32
+            nbytes = _lib.load().ma_lstm_stack_workspace_bytes(K, B, H, self.num_layers)
+            if nbytes < 0:
+                _lib.check(int(nbytes), "lstm_stack_workspace_bytes")
             ld = (self.nspk * N + 7) // 8 * 8
             ws = self._ws[key] = dict(
-                chunk=chunk, ld=ld,
+                _lstm.layer_buffers(K, B, H, dev), ld=ld,  # (the pipelined schedule writes into the first of its output buffers)
                 mw=torch.empty((B, K, N), dtype=f32, device=dev), coef=torch.empty((B, K), dtype=f32, device=dev),
-                xin=torch.zeros((K, B, _ceil64(N)), dtype=bf, device=dev),  # columns past N stay zero
-                hf=[torch.empty((K, B, H), dtype=f32, device=dev) for _ in range(2)],
-                hb=[torch.empty((K, B, H), dtype=bf, device=dev) for _ in range(2)],
+                xin=torch.zeros((K, B, _lstm.ceil64(N)), dtype=torch.bfloat16, device=dev),  # columns past N stay zero
                 score=torch.empty((K * B, ld), dtype=f32, device=dev),
-                stack=torch.empty((int(sizes[0]),), dtype=torch.uint8, device=dev),
-                lstm=torch.empty((int(sizes[1]),), dtype=torch.uint8, device=dev))
+                stack=torch.empty((int(nbytes),), dtype=torch.uint8, device=dev))
         return ws
 
     # ---- forward ---------------------------------------------------------------------------------------------------------------
@@ -224,24 +194,16 @@ class TasNet(nn.Module):
         schedule = schedule or self.schedule
         if schedule not in SCHEDULES:
             raise ValueError("schedule must be one of %s" % (SCHEDULES,))
-        P, lib, H = self._prepared, _lib.load(), self.hidden_size
+        P, H = self._prepared, self.hidden_size
         K, B, Kpad = xin.shape
         ws = next(w for w in self._ws.values() if w["xin"] is xin)
+        if schedule == "layered":
+            return _lstm.run_layers(P["layered"], xin, H, 1, ws)
+        of, ob = ws["hf"][0], ws["hb"][0]
         with _host.pinned_stream():
-            s = _host.current_stream_ptr()
-            if schedule == "pipelined":
-                of, ob = ws["hf"][0], ws["hb"][0]
-                _lib.check(lib.ma_lstm_stack_bf16(xin.data_ptr(), K, B, Kpad, H, self.num_layers, P["packed_ptrs"], P["bias_ptrs"],
-                                                  of.data_ptr(), ob.data_ptr(), None, None, ws["stack"].data_ptr(), ws["stack"].numel(), s),
-                           "lstm_stack")
-                return of, ob
-            cur = xin
-            for k, L in enumerate(P["layers"]):
-                of, ob = ws["hf"][k & 1], ws["hb"][k & 1]
-                _lib.check(lib.ma_lstm_bidir_bf16(cur.data_ptr(), K, B, L["Kpad"], H, L["wih"].data_ptr(), L["whh"].data_ptr(),
-                                                  L["bias2"].data_ptr(), 1, ws["chunk"], of.data_ptr(), ob.data_ptr(), None,
-                                                  ws["lstm"].data_ptr(), ws["lstm"].numel(), s), "lstm_layer")
-                cur = ob
+            _lib.check(_lib.load().ma_lstm_stack_bf16(xin.data_ptr(), K, B, Kpad, H, self.num_layers, P["packed_ptrs"], P["bias_ptrs"],
+                                                      of.data_ptr(), ob.data_ptr(), None, None, ws["stack"].data_ptr(),
+                                                      ws["stack"].numel(), _host.current_stream_ptr()), "lstm_stack")
         return of, ob
 
     @torch.no_grad()

@@ -18,9 +18,10 @@ pytestmark = pytest.mark.gpu
 U = 2.0 ** -24  # float32 unit roundoff
 SCHEDULES = ["pipelined", "layered"]
 # (T, B, H, K, layers): T < layers twice; one layer; four layers at small B; a second batch tile (B > 16: the tile kernel); a second
-# workgroup row (B > 64); the yaml geometry (32 k-steps per layer: the 8-k-step blocks)
+# workgroup row (B > 64); the yaml geometry (32 k-steps per layer: the 8-k-step blocks); 16 k-steps per layer at small B (the
+# 4-k-step blocks)
 STACK_TABLE = [(1, 1, 64, 64, 4), (2, 2, 64, 40, 4), (3, 1, 128, 64, 1), (19, 3, 64, 40, 4), (7, 17, 128, 160, 3), (5, 70, 256, 64, 2),
-               (12, 1, 512, 500, 4)]
+               (12, 1, 512, 500, 4), (5, 2, 256, 256, 2)]
 
 
 @pytest.fixture(scope="module")
