@@ -1714,6 +1714,100 @@ int ma_wavegrad_reverse(const ma_wavegrad_plan_t* plan, float* audio, const floa
                         const float* c2, const float* sigma, const float* noise, int32_t S, int32_t first_step, int32_t n_steps,
                         void* workspace, int64_t workspace_bytes, ma_stream_t stream);
 
+/* ---- FastSpeech2 inference (mindaudio/models/fastspeech2/, mindaudio/models/transformer/) -------------------------------------------------
+ * The residual stream is time-major, channel-last float32 (B, T, C), compact.  bf16 exists only as an MFMA operand image (B, T + 2 * halo,
+ * C) with zero halo rows around every utterance, the layout of ma_conv1d_taps_bf16.  No atomics, no cross-workgroup waiting: the same
+ * bits from run to run.  All: every argument check comes before any HIP call; nothing allocates or synchronises.
+ *
+ * ma_mha_d128_bf16: ScaledDotProductAttention under a key-padding mask (transformer/score_function.py:21-35 as MultiHeadAttention calls
+ *   it, sublayers.py:73-92), d_k in {32, 64, 128}:  ctx[b, t, h] = softmax_j(scale * q[b, t, h] . k[b, j, h], j < lens[b]) . v[b, j, h].
+ *   q, k, v bf16 matrices with row strides ldq / ldk / ldv (in practice three column ranges of one fused QKV GEMM output), head h in
+ *   columns h * d_k ..; utterance b starts at row b * rows_in (rows_in >= T: the operand image's T + 2 * halo).  ctx bf16, utterance b at
+ *   row b * rows_out, row stride ldc.  Every one of the T query rows is computed (the reference's padded rows take part in the block's
+ *   norm statistics).  Keys are walked in tiles of 32 with an online softmax; no probability reaches memory; products on MFMA, scores,
+ *   running max / sum and the accumulator float32; probabilities are rounded to bf16 for the second product and the rounded values are
+ *   the ones summed.  A key >= lens[b] has probability exactly 0 and neither its K nor its V row can reach the result, whatever they hold.
+ *   Departure: an utterance with lens[b] <= 0 gets zero rows (the reference's softmax over all -inf gives NaN).  lens is clamped to T.
+ *   Strides % 8 == 0, 16-byte aligned bases, B, H <= 65535: MA_ERR_UNSUPPORTED / MA_ERR_INVALID_ARG otherwise.
+ * ma_groupnorm_stats / ma_groupnorm_apply: GroupNorm(G, C) of the (B, C, T, 1) view (sublayers.py:96-98, 141-143, with the constructor
+ *   call read as 8 groups over d_model channels): per (b, group) mean and biased variance over ALL T rows x C / G channels, padded
+ *   rows included.  stats: x (B, T, C) float32 -> part (B, ma_groupnorm_parts(T), G, 2) float64: mean and centred second moment of
+ *   each 64-row part, fixed summation order.  apply joins the parts in part order and writes, for t < lens[b] (lens NULL: all rows),
+ *   ((x - mean) * rstd) * gamma[c] + beta[c], rstd = 1 / sqrt(var + eps), and exact zeros for t >= lens[b] (the `* non_pad_mask` of
+ *   layers.py:29,32): out (B, T, C) float32 (may alias x; optional) and img (B, T + 2 halo, Cpad) bf16 (optional) whose halo rows and
+ *   columns C .. Cpad - 1 are written as zeros on every call.  C % G == 0, (C / G) % 4 == 0, C / 4 a divisor of 256, G <= 64, C % 8 == 0.
+ * ma_fs2_layernorm_pack_f32: LayerNorm over F (biased variance, eps) of the rows t < lens[b] of x (B, T, F) float32, zeros for the other
+ *   rows -> out (B, T, F) float32 (optional, may alias x) and img (B, T + 2 halo, F) bf16 with zero halo rows (optional).  The norm
+ *   between the convolutions of a VariancePredictor (variance_adapter.py:74,78) and norm = "layer" of an FFT block.  F % 64 == 0, <= 1024.
+ * ma_variance_head_f32: the tail of a VariancePredictor fused with its consumer (variance_adapter.py:78-89, 152-166, 305-313), one row
+ *   per wave:  v = (LayerNorm_eps(hid[b, t]) . w + bias[0]) * (t < lens[b], lens NULL: 1) * control -> pred (B, T) float32;
+ *   index = #{j < n_bins - 1: bins[j] < v} (searchsorted, side left) or index_in[b, t] clamped when given -> index_out (optional);
+ *   x_out[b, t] = x[b, t] + table[index] as float32 (B, T, C); with pos != NULL (the decoder's position table, models.py:123) x_pos =
+ *   x_out + pos[t] as float32; img (B, T + 2 halo, C) bf16 with zero halo rows holds x_pos when pos is given, x_out otherwise (each of
+ *   the three optional).  table == NULL (the duration predictor): only pred is written.
+ * ma_fs2_embed_f32: out[b, t] = table[ids[b, t]] + pos[t] (models.py:63-67) as float32 and as the operand image; an id outside
+ *   0 .. V - 1 adds nothing.  C % 8 == 0.
+ * ma_fs2_durations_f32: dur = max(round(exp(logd) - 1) * d_control, 0) (variance_adapter.py:290-291): round half to even, exp through
+ *   float64 rounded once, the subtraction and the product single float32 operations (no contraction).
+ * ma_length_regulate_i32: LengthRegulator on token ids (variance_adapter.py:12-31, 292).  dur (B, T_src) float32, already rounded and
+ *   clipped; each is truncated to int32 (above 2^18: clamped).  -> prefix (B, T_src) exclusive sums (optional), mel_len (B), and, when
+ *   expanded != NULL, expanded (B, T_cap) int32: ids[b, i] for prefix[i] <= t < prefix[i] + dur[i] by binary search, 0 (PAD) for
+ *   t >= mel_len[b]; frames beyond T_cap are not written (the caller reads mel_len).  T_src <= 4096. */
+int ma_mha_d128_bf16(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv, const int32_t* lens, int64_t B,
+                     int64_t T, int64_t rows_in, int32_t H, int32_t d_k, float scale, void* ctx, int64_t ldc, int64_t rows_out,
+                     ma_stream_t stream);
+int32_t ma_groupnorm_parts(int64_t T);
+int ma_groupnorm_stats(const float* x, int64_t B, int64_t T, int32_t C, int32_t G, double* part, ma_stream_t stream);
+int ma_groupnorm_apply(const float* x, int64_t B, int64_t T, int32_t C, int32_t Cpad, int32_t G, int32_t halo, const double* part, float eps,
+                       const float* gamma, const float* beta, const int32_t* lens, float* out, void* img, ma_stream_t stream);
+int ma_fs2_layernorm_pack_f32(const float* x, int64_t B, int64_t T, int32_t F, int32_t halo, const float* gamma, const float* beta, float eps,
+                              const int32_t* lens, float* out, void* img, ma_stream_t stream);
+int ma_variance_head_f32(const float* hid, int64_t B, int64_t T, int32_t F, const float* gamma, const float* beta, float eps, const float* w,
+                         const float* bias, const int32_t* lens, float control, float* pred, const float* bins, int32_t n_bins,
+                         const int32_t* index_in, int32_t* index_out, const float* table, const float* x, const float* pos, int32_t C,
+                         int32_t halo, float* x_out, float* x_pos, void* img, ma_stream_t stream);
+int ma_fs2_embed_f32(const int32_t* ids, int64_t B, int64_t T, int32_t C, int32_t V, int32_t halo, const float* table, const float* pos,
+                     float* out, void* img, ma_stream_t stream);
+int ma_fs2_durations_f32(const float* logd, int64_t n, float d_control, float* dur, ma_stream_t stream);
+int ma_length_regulate_i32(const float* dur, const int32_t* ids, int64_t B, int32_t T_src, int32_t* prefix, int32_t* mel_len,
+                           int32_t* expanded, int32_t T_cap, ma_stream_t stream);
+
+/* One FFT block (transformer/layers.py:27-34, sublayers.py:64-100, 130-145): device pointers.  w_qkv (3 C, C) bf16 = w_qs | w_ks | w_vs
+ * stacked by rows, b_qkv [3 C]; w_fc (C, C) bf16; w_1 (d_inner, k1, C) bf16, w_2 (C, d_inner) bf16 (kernel 1); gamma / beta [C] of the
+ * two norms. */
+typedef struct ma_fs2_layer {
+  const void* w_qkv;
+  const float* b_qkv;
+  const void* w_fc;
+  const float* b_fc;
+  const float *gamma1, *beta1;
+  const void* w_1;
+  const float* b_1;
+  const void* w_2;
+  const float* b_2;
+  const float *gamma2, *beta2;
+} ma_fs2_layer_t;
+
+/* A stack of FFT blocks for one (B, T) shape: plain data.  groups > 0: GroupNorm(groups, d_model); groups == 0: LayerNorm.  halo >= k1 / 2.
+ * d_model % 64 == 0 (<= 1024), d_inner % 64 == 0, d_model / heads in {32, 64, 128}. */
+typedef struct ma_fs2_plan {
+  int32_t n_layers, heads, d_model, d_inner, k1, groups, halo, reserved;
+  int64_t B, T;
+  float eps;
+  int32_t reserved2;
+  const ma_fs2_layer_t* layers; /* host */
+} ma_fs2_plan_t;
+
+/* ma_fs2_fft_stack: the blocks of one stack over one workspace inside one call: per block the QKV product (one N = 3 C GEMM over the
+ *   operand image), ma_mha_d128_bf16, fc with the residual in its epilogue, the norm (x and img rewritten), w_1 with bias and ReLU (one
+ *   ma_conv1d_taps_bf16 per utterance), w_2 with the residual in its epilogue, the norm.  x (B, T, C) float32 and img (B, T + 2 halo, C)
+ *   bf16 hold the stack's input on entry and its output on return; lens (B) masks keys and rows.  No host synchronisation, read-back
+ *   or allocation between the first and the last launch.  MA_ERR_WORKSPACE when workspace_bytes < ma_fs2_workspace_bytes(plan) (a
+ *   negative MA_ERR_* for a plan the stack would refuse); a failed launch returns MA_ERR_LAUNCH and ends the call. */
+int64_t ma_fs2_workspace_bytes(const ma_fs2_plan_t* plan);
+int ma_fs2_fft_stack(const ma_fs2_plan_t* plan, float* x, void* img, const int32_t* lens, void* workspace, int64_t workspace_bytes,
+                     ma_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -119,6 +119,20 @@ class WaveGradPlan(ctypes.Structure):
                 ("ops", ctypes.POINTER(WaveGradOp))]
 
 
+class Fs2Layer(ctypes.Structure):
+    """struct ma_fs2_layer (include/mindaudio_amd.h)."""
+
+    _fields_ = [(n, ctypes.c_void_p) for n in ("w_qkv", "b_qkv", "w_fc", "b_fc", "gamma1", "beta1", "w_1", "b_1", "w_2", "b_2", "gamma2",
+                                               "beta2")]
+
+
+class Fs2Plan(ctypes.Structure):
+    """struct ma_fs2_plan (include/mindaudio_amd.h); layers is a HOST array of Fs2Layer."""
+
+    _fields_ = [("n_layers", i32), ("heads", i32), ("d_model", i32), ("d_inner", i32), ("k1", i32), ("groups", i32), ("halo", i32),
+                ("reserved", i32), ("B", i64), ("T", i64), ("eps", f32), ("reserved2", i32), ("layers", ctypes.POINTER(Fs2Layer))]
+
+
 class GemmEpilogue(ctypes.Structure):
     """struct ma_gemm_epilogue (include/mindaudio_amd.h)."""
 
@@ -447,6 +461,19 @@ PROTOTYPES = {
     "ma_wavegrad_forward": (ctypes.c_int, [ctypes.POINTER(WaveGradPlan), vp, vp, vp, i64, vp, vp, i64, vp]),
     "ma_wavegrad_reverse": (ctypes.c_int, [ctypes.POINTER(WaveGradPlan), vp, vp, vp, ctypes.POINTER(f32), ctypes.POINTER(f32),
                                            ctypes.POINTER(f32), vp, i32, i32, i32, vp, i64, vp]),
+    # ---- FastSpeech2 inference ----
+    "ma_mha_d128_bf16": (ctypes.c_int, [vp, i64, vp, i64, vp, i64, vp, i64, i64, i64, i32, i32, f32, vp, i64, i64, vp]),
+    "ma_groupnorm_parts": (i32, [i64]),
+    "ma_groupnorm_stats": (ctypes.c_int, [vp, i64, i64, i32, i32, vp, vp]),
+    "ma_groupnorm_apply": (ctypes.c_int, [vp, i64, i64, i32, i32, i32, i32, vp, f32, vp, vp, vp, vp, vp, vp]),
+    "ma_fs2_layernorm_pack_f32": (ctypes.c_int, [vp, i64, i64, i32, i32, vp, vp, f32, vp, vp, vp, vp]),
+    "ma_variance_head_f32": (ctypes.c_int, [vp, i64, i64, i32, vp, vp, f32, vp, vp, vp, f32, vp, vp, i32, vp, vp, vp, vp, vp, i32, i32, vp,
+                                            vp, vp, vp]),
+    "ma_fs2_embed_f32": (ctypes.c_int, [vp, i64, i64, i32, i32, i32, vp, vp, vp, vp, vp]),
+    "ma_fs2_durations_f32": (ctypes.c_int, [vp, i64, f32, vp, vp]),
+    "ma_length_regulate_i32": (ctypes.c_int, [vp, vp, i64, i32, vp, vp, vp, i32, vp]),
+    "ma_fs2_workspace_bytes": (i64, [ctypes.POINTER(Fs2Plan)]),
+    "ma_fs2_fft_stack": (ctypes.c_int, [ctypes.POINTER(Fs2Plan), vp, vp, vp, vp, i64, vp]),
 }
 WAVEGRAD_OP_INIT, WAVEGRAD_OP_PACK, WAVEGRAD_OP_CONV, WAVEGRAD_OP_DOWN, WAVEGRAD_OP_LAST = range(5)  # MA_WAVEGRAD_OP_*
 WAVEGRAD_BUF_NONE, WAVEGRAD_BUF_AUDIO, WAVEGRAD_BUF_MEL = -1, -2, -3  # MA_WAVEGRAD_BUF_*

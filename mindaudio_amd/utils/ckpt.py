@@ -404,6 +404,56 @@ def _is_wavegrad(module):
     return type(module).__name__ == "WaveGrad"
 
 
+_FS2_BINS = {"pitch_bins_log": "pitch_bins", "pitch_bins": "pitch_bins", "energy_bins_log": "energy_bins", "energy_bins": "energy_bins"}
+
+
+def convert_fastspeech2_names(ref_params):
+    """Reference FastSpeech2 (mindaudio/models/fastspeech2/fastspeech2_v190.py) parameter names -> mindaudio_amd.models.FastSpeech2's
+    state dict.  The cell attributes already carry this package's names ({encoder, expanded_encoder, decoder}.layer_stack.<n>.
+    {slf_attn.{w_qs, w_ks, w_vs, fc, layer_norm}, pos_ffn.{w_1, w_2, layer_norm}}, variance_adaptor.<x>_predictor.{conv1.0, norm1,
+    conv2.0, norm2, linear_layer}, mel_linear).  What differs: nn.Embedding's leaf (`embedding_table` -> `weight`), the unit axis
+    MindSpore's nn.Conv1d keeps in its weight ((out, in, 1, k) -> (out, in, k)), and the explicitly named bin parameters
+    (`pitch_bins_log` / `pitch_bins`, `energy_bins` / `energy_bins_log`, with or without the `variance_adaptor.` prefix) ->
+    variance_adaptor.pitch_bins / energy_bins.  A checkpoint without bins leaves the module's own (computed from `stats`).
+    Not verified against a file MindSpore wrote (none can be produced here): the names are inferred from the cell definitions."""
+    out = {}
+    for name, arr in ref_params.items():
+        n = _strip(name)
+        if _SKIP.match(n):
+            continue
+        leaf = n.rsplit(".", 1)[-1]
+        if leaf in _FS2_BINS and n in (leaf, "variance_adaptor." + leaf):
+            n = "variance_adaptor." + _FS2_BINS[leaf]
+        elif leaf == "embedding_table":
+            n = n[:-len(leaf)] + "weight"
+        elif leaf == "weight" and np.ndim(arr) == 4 and np.shape(arr)[2] == 1:
+            arr = np.asarray(arr)[:, :, 0, :]
+        out[n] = arr
+    return out
+
+
+def fastspeech2_to_reference_names(state, prefix="", pitch_quantization="log", energy_quantization="linear"):
+    """Inverse of `convert_fastspeech2_names`: a FastSpeech2 state dict of this package -> {reference name: ndarray in MindSpore's
+    layout}; the bins go out under the names the reference gives them for the two quantization settings."""
+    out = {}
+    for k, v in state.items():
+        a = v.detach().float().cpu().numpy() if hasattr(v, "detach") else np.asarray(v)
+        if k == "variance_adaptor.pitch_bins":
+            k = "variance_adaptor.pitch_bins" + ("_log" if pitch_quantization == "log" else "")
+        elif k == "variance_adaptor.energy_bins":
+            k = "variance_adaptor.energy_bins" + ("_log" if energy_quantization == "log" else "")
+        elif k.endswith(("src_word_emb.weight", "_embedding.weight")):
+            k = k[:-len("weight")] + "embedding_table"
+        elif k.endswith(".weight") and a.ndim == 3:
+            a = a[:, :, None, :]
+        out[prefix + k] = a
+    return out
+
+
+def _is_fastspeech2(module):
+    return type(module).__name__ == "FastSpeech2"
+
+
 def read_epoch_num(path):
     """`int(param_dict.get("epoch_num", 0))` of examples/conformer/train.py:121 - the number of finished epochs the reference's
     ModelCheckpoint appends to every file (`append_info=[{"epoch_num": ...}]`, train.py:157-163)."""
@@ -425,6 +475,8 @@ def load_mindspore_checkpoint(module, path, strict=True):
         params = convert_tasnet_names(raw)
     elif _is_wavegrad(module):
         params = convert_wavegrad_names(raw)
+    elif _is_fastspeech2(module):
+        params = convert_fastspeech2_names(raw)
     else:
         params = convert_ecapa_names(raw) if _is_ecapa(module) else convert_names(raw)
     own = module.state_dict()
@@ -438,6 +490,8 @@ def load_mindspore_checkpoint(module, path, strict=True):
             raise ValueError("shape mismatch for %s: checkpoint %s, module %s" % (k, tuple(t.shape), tuple(own[k].shape)))
         state[k] = t.to(own[k].dtype)
     missing = [k for k in own if k not in state and not k.endswith("num_batches_tracked")]
+    if _is_fastspeech2(module):  # a checkpoint without bins keeps the ones the module computed from `stats`
+        missing = [k for k in missing if k not in ("variance_adaptor.pitch_bins", "variance_adaptor.energy_bins")]
     if strict and (missing or unexpected):
         raise KeyError("checkpoint does not match the module: missing %s, unexpected %s" % (missing[:8], unexpected[:8]))
     # (ConformerEncoder / CTC drop their bf16 / packed weight copies in load_state_dict post-hooks)
