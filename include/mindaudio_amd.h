@@ -1080,7 +1080,8 @@ int ma_adam_mirror_f32(float* param, const float* grad, float* m, float* v, int6
 /* Res2NetBlock (ecapatdnn.py:66-114) in one launch: y_0 = x_0, y_i = BN(ReLU(conv_{k=3,dil}(x_i + y_{i-1}) + b_i)), i = 1..scale-1
  * (y_1 from x_1 alone), x_i = columns [i cc, (i+1) cc) of x.  x, y: (batch, T + 2 halo, >= scale * cc) bf16 with zero halo rows
  * (pointers at the first halo row of utterance 0); w (scale-1, cc, 3 cc) bf16 with K = tap * cc + c; bias / bn_scale / bn_shift
- * (scale-1, cc) float32.  cc in {64, 128}, scale 8, dil <= halo, T + 2 halo <= 384; a workgroup owns one utterance for the whole chain. */
+ * (scale-1, cc) float32.  cc in {64, 128}, scale 8, dil <= halo, T + 2 halo <= 384, ldx % 8 == ldy % 8 == 0 and 16-byte aligned x, y, w
+ * (MA_ERR_UNSUPPORTED otherwise); a workgroup owns one utterance for the whole chain. */
 int64_t ma_res2net_fused_lds_bytes(int32_t cc, int64_t tp, int32_t dil);
 int ma_res2net_fused_bf16(const void* x, int64_t ldx, void* y, int64_t ldy, int64_t batch, int64_t T, int32_t halo, int32_t cc,
                           int32_t scale, int32_t dil, const void* w, const float* bias, const float* bn_scale,

@@ -232,7 +232,9 @@ int ma_res2net_fused_bf16(const void* x, int64_t ldx, void* y, int64_t ldy, int6
     return MA_ERR_INVALID_ARG;
   const int64_t tp = T + 2 * halo;
   if ((cc != 64 && cc != 128) || dil > halo || tp > kR2MaxRowTiles * 16 || (ldx & 7) || (ldy & 7) || ldx < (int64_t)cc * scale ||
-      ldy < (int64_t)cc * scale)
+      ldy < (int64_t)cc * scale ||
+      // x, y and w move through 16-byte loads and stores
+      ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(w)) & 15))
     return MA_ERR_UNSUPPORTED;
   const int64_t lds = ma_res2net_fused_lds_bytes(cc, tp, dil);
   if (lds > 160 * 1024) return MA_ERR_UNSUPPORTED;
