@@ -939,6 +939,15 @@ int ma_subsample_fused_pack_bf16(const float* W1, const void* W2, int64_t idim, 
 int ma_subsample_fused_bf16(const float* x, int64_t stride_b, int64_t stride_t, int64_t stride_f, int64_t batch, int64_t T,
                             int32_t idim, const float* cmvn_mean, const float* cmvn_istd, const void* packed, const float* b1,
                             const float* b2, int64_t C, void* out, ma_stream_t stream);
+/* The same launch with its grid bounded.  ma_subsample_fused_bf16 runs a kernel whose workgroups WALK the 128-position tiles
+ * (workgroup w takes tiles w, w + workgroups, ...; the next tile's input rows, im2col view and first patch are built under the
+ * current tile's last chunk and epilogue) with one workgroup per compute unit; max_workgroups > 0 caps the grid instead (tests use
+ * it for long walks on small inputs), 0 = that default, < 0 = MA_ERR_INVALID_ARG.  The output is bit-identical for every grid, and to
+ * the one-tile-per-workgroup kernel, which MINDAUDIO_AMD_SUBSAMPLE=tile (read once per process) selects for
+ * ma_subsample_fused_bf16. */
+int ma_subsample_fused_walk_bf16(const float* x, int64_t stride_b, int64_t stride_t, int64_t stride_f, int64_t batch, int64_t T,
+                                 int32_t idim, const float* cmvn_mean, const float* cmvn_istd, const void* packed, const float* b1,
+                                 const float* b2, int64_t C, void* out, int32_t max_workgroups, ma_stream_t stream);
 
 /* Input gradient of the same convolution without the im2col-shaped intermediate (conv2_dinput.hip; the training step's
  * replacement for ma_gemm (dy . W) + ma_col2im_3x3s2_relu_bf16): dact (batch, H, Wd, C) bf16 = [act > 0] * conv_transpose(dy, W),

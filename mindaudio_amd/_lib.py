@@ -336,6 +336,7 @@ PROTOTYPES = {
     "ma_subsample_fused_packed_bytes": (i64, [i64, i64]),
     "ma_subsample_fused_pack_bf16": (ctypes.c_int, [vp, vp, i64, i64, vp, vp]),
     "ma_subsample_fused_bf16": (ctypes.c_int, [vp, i64, i64, i64, i64, i64, i32, vp, vp, vp, vp, vp, i64, vp, vp]),
+    "ma_subsample_fused_walk_bf16": (ctypes.c_int, [vp, i64, i64, i64, i64, i64, i32, vp, vp, vp, vp, vp, i64, vp, i32, vp]),
     "ma_gemm_rows_packed_bytes": (i64, [i64, i64]),
     "ma_gemm_rows_pack_bf16": (ctypes.c_int, [vp, i64, i64, i64, vp, vp]),
     "ma_gemm_rows_packed_f32": (ctypes.c_int, [vp, i64, i64, i64, vp, i64, vp, f32, vp, i64, vp]),

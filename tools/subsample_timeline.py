@@ -1,6 +1,9 @@
 """Phase timeline of subsample_fused_kernel from a -DMA_SF_PROF build of subsample_fused.hip
-(SRC=subsample_fused.hip bash tools/ffn_variants.sh build "prof:-DMA_SF_PROF"; run with MINDAUDIO_AMD_LIB=.../variants/prof.so):
-s_memtime stamps of consumer wave 0 and producer wave 4 of three workgroups, in shader-clock cycles since the workgroup's entry."""
+(SRC=subsample_fused.hip bash tools/ffn_variants.sh build "prof:-DMA_SF_PROF"; run with MINDAUDIO_AMD_LIB=.../variants/prof.so;
+MINDAUDIO_AMD_SUBSAMPLE=tile times the one-tile-per-workgroup kernel instead of the walking one):
+s_memtime stamps of consumer wave 0 and producer wave 4 of three workgroups (the first, the middle one, the sixth from the end of
+the grid) for four tiles of each workgroup's walk - its first, the middle one, the one after that, its last - in shader-clock
+cycles since the workgroup's entry.  The one-tile kernel has one tile per workgroup: only "first" is printed."""
 import ctypes
 import os
 import sys
@@ -35,21 +38,34 @@ acc = []
 for it in range(10):
     fn()
     torch.cuda.synchronize()
-    buf = (ctypes.c_ulonglong * 192)()
+    buf = (ctypes.c_ulonglong * 768)()
     assert lib.ma_debug_sf_prof(buf) == 0
-    acc.append(np.array(buf[:], dtype=np.int64).reshape(2, 3, 32))
+    a = np.array(buf[:], dtype=np.int64).reshape(2, 3, 4, 32)
+    # cycles since the workgroup's entry (consumer wave 0's first stamp); stamps that were never written stay 0
+    acc.append(np.where(a != 0, a - a[0, :, 0, 0][None, :, None, None], 0))
 a = np.median(np.stack(acc), axis=0)
+TILES = ("first", "middle", "middle + 1", "last")
 for role, name in ((0, "consumer wave 0"), (1, "producer wave 4")):
-    print("== %s: cycles since the wave's entry, workgroups 0 / 1200 / 2300" % name)
-    labels = {0: "entry", 1: "rows staged", 2: "X built", 3: "patch 0 built", 20: "loop end / last barrier", 21: "end"}
+    labels = {0: "entry / join barrier passed", 1: "rows staged", 2: "X built", 3: "patch 0 built",
+              20: "B7 passed" if role else "Bx passed (chunk 7 left by all)", 21: "epilogue end",
+              22: "next rows requested", 23: "next rows written", 24: "next X built", 27: "Bx passed", 25: "next patch 0 built"}
     for k in range(8):
         labels[4 + 2 * k] = ("chunk %d start" % k) if role == 0 else ("patch %d start" % (k + 1))
         labels[5 + 2 * k] = ("chunk %d end" % k) if role == 0 else ("patch %d built" % (k + 1))
-    prev = None
-    for k in sorted(labels):
-        v = a[role, :, k] - a[role, :, 0]
-        if a[role, 0, k] == 0:
+    order = sorted(labels, key=lambda k: {22: 16.3, 17: 16.6, 23: 17.5, 20: 18, 24: 24, 27: 24.5, 25: 25}.get(k, k) if role else k)
+    for ts, tname in enumerate(TILES):
+        if not a[role, :, ts, :].any():
             continue
-        d = "" if prev is None else "  (+%s)" % " / ".join("%6d" % int(x) for x in (v - prev))
-        print("%-24s %s%s" % (labels[k], " / ".join("%7d" % int(x) for x in v), d))
-        prev = v
+        print("== %s, the workgroup's %s tile: cycles since the workgroup's entry, three workgroups" % (name, tname))
+        prev = None
+        for k in order:
+            v = a[role, :, ts, k]
+            if not v.any() and not (k == 0 and ts == 0 and role == 0):
+                continue
+            d = "" if prev is None else "  (+%s)" % " / ".join("%6d" % int(x) for x in (v - prev))
+            print("%-32s %s%s" % (labels[k], " / ".join("%8d" % int(x) for x in v), d))
+            prev = v
+if a[0, :, 2, 4].any():
+    gap = a[0, :, 2, 4] - a[0, :, 1, 19]
+    print("consumer wave 0, end of chunk 7 of the middle tile -> start of chunk 0 of the next: %s cycles"
+          % " / ".join("%d" % int(x) for x in gap))
