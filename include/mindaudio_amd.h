@@ -1553,6 +1553,64 @@ int ma_tasnet_decode_f32(const float* score, const float* mixture_w, int64_t M, 
 int ma_si_snr_pairwise(const float* source, const float* estimate, const int64_t* lengths, int64_t B, int32_t C, int64_t T, double* out,
                        ma_stream_t stream);
 
+/* ---- Conv-TasNet training (examples/conv_tasnet/train.py): the launches of the backward between its GEMMs, and the optimizer ---------
+ * dX = dY . W is ma_gemm_bf16 on a transposed weight copy (the residual stream's gradient rides in its residual epilogue), dW = dY^T . X
+ * is ma_gemm_tn_bf16_f32; in the float32 validation mode both are ma_gemm_x32.  Layout, tiles and the (count, sum, M2) partials as above.
+ * The backward of a global layer norm, dx = (dy - mean(dy) - xhat mean(dy xhat)) / sigma, needs two more whole-utterance sums; they
+ * travel as part2[(m * P + p) * 2] = (sum(dy), sum(dy * xhat)) of tile p, float64, joined in index order by the consumer.  xhat is
+ * recomputed from the saved pre-activation, the PReLU slope and the forward's partials.  Parameter gradients leave as float32 partials,
+ * one per workgroup, for ma_reduce_splits_batch_f32.  No atomics: the same bits from run to run.
+ *
+ * ma_gln_dwconv_prelu_train: ma_gln_dwconv_prelu that also writes `pre`, the depthwise output before its PReLU (same z, same part_out).
+ * ma_gln_apply_f32: ma_gln_apply_bf16 with a float32 output.
+ * ma_si_snr_grad_f32: grad (B, C, T) float32 = d(-mean_b(sum_j snr[b, perm[b, j], j] / C)) / d estimate in closed float64 form, snr as
+ *   ma_si_snr_pairwise computes it (zero-mean over the first lengths[b] samples, the same EPS placement); perm (B, C) int64 on the
+ *   device, target j <- estimate perm[b, j], a permutation of 0 .. C - 1 per row (every estimate row is then written exactly once).
+ *   grad is exactly 0 at and beyond lengths[b].
+ * ma_tasnet_decode_bwd_f32: the backward of ma_tasnet_decode_f32 for both overlaps.  d_out (M, C, (K + 1) L / 2) -> d_score
+ *   (M * K, C * N) = d_source_w * mixture_w * (score > 0), d_mixture_w (M * K, N) = sum_c d_source_w * relu(score) (the decoder's share
+ *   only), d_basis_part [M * G][L][N] with G = ma_tasnet_decode_bwd_parts(K, C, N, L) (0: unsupported).  L even and <= 64, N % 64 == 0,
+ *   L * N <= 12288, C <= 16.
+ * ma_tasnet_encode_bwd_f32: d_mixture_w_total = d_mixture_w + gLN backward of d_norm (the gradient at the normalised mixture_w, with
+ *   part2 from ma_gln_bwd_stats(d_norm, mixture_w, weight = 1)); d_Ut_part [M * G][L][N] (the order of Wt) = sum over the workgroup's frames of
+ *   d_mixture_w_total * (mixture_w > 0) (x) the frame's samples, G = ma_tasnet_encode_bwd_parts(K, N, L).  Same shape limits.
+ * ma_gln_bwd_stats: part2 of dy against xhat = gLN(prelu(v, weight[0])) with v's forward partials `part` (weight = 1: no PReLU).
+ * ma_gln2_bwd_dwconv: d_h (the gradient at the second gLN's output), d0 (the depthwise output before PReLU, partials part_b of its
+ *   PReLU), y0 (the conv1x1 output before PReLU, partials part_a of its PReLU) -> d_u (the gradient at the FIRST gLN's output) through
+ *   the gLN backward (part2_h), the PReLU backward and the three dilated taps, each checked against [0, K) of its own utterance;
+ *   part2_u = ma_gln_bwd_stats of d_u against y0; d_weight2_part [M * P] (the second slope), d_Wt_part [M * P][3][C] (the taps, the
+ *   order of Wt).  C in {64, 128, 256, 512, 1024}; d_u must not be an input.
+ * ma_gln1_bwd: d_u, y0 -> out (M * K, C) = the gradient at y0, bf16 (out_bf16 != 0, round to nearest even) or float32;
+ *   d_weight_part [M * P] (the first slope).
+ * ma_sgd_momentum_f32: nn.SGD as train.py:91-96 builds it.  g = grad + weight_decay * param; momentum > 0: buf = g on the first step
+ *   (first_step != 0; buf is then not read), else buf = momentum * buf + g, and param -= lr * buf; momentum == 0: param -= lr * g (buf
+ *   may be NULL).  mirror_bf16 (n) bf16, optional: the updated parameters rounded to nearest even.  n % 4 == 0, 16-byte aligned.
+ * All: MA_ERR_INVALID_ARG for a null pointer, a dimension < 1 or a misaligned base, MA_ERR_UNSUPPORTED for a shape outside the above;
+ * nothing is launched on a refusal. */
+int ma_gln_dwconv_prelu_train(const float* y, int64_t M, int64_t K, int32_t C, const double* part_in, const float* Wt, int32_t P,
+                              int32_t dilation, const float* weight, float* pre, float* z, double* part_out, ma_stream_t stream);
+int ma_gln_apply_f32(const float* y, int64_t M, int64_t K, int32_t C, const double* part, float* out, ma_stream_t stream);
+int ma_si_snr_grad_f32(const float* source, const float* estimate, const int64_t* lengths, const int64_t* perm, int64_t B, int32_t C,
+                       int64_t T, float* grad, ma_stream_t stream);
+int32_t ma_tasnet_decode_bwd_parts(int64_t K, int32_t C, int32_t N, int32_t L);
+int ma_tasnet_decode_bwd_f32(const float* d_out, const float* score, const float* mixture_w, int64_t M, int64_t K, int32_t C, int32_t N,
+                             const float* basis, int32_t L, int32_t overlap, float* d_score, float* d_mixture_w, float* d_basis_part,
+                             ma_stream_t stream);
+int32_t ma_tasnet_encode_bwd_parts(int64_t K, int32_t N, int32_t L);
+int ma_tasnet_encode_bwd_f32(const float* x, int64_t M, int64_t T, int64_t ldx, const float* mixture_w, const double* part,
+                             const float* d_norm, const double* part2, const float* d_mixture_w, int32_t L, int32_t N, float* d_Ut_part,
+                             ma_stream_t stream);
+int ma_gln_bwd_stats(const float* dy, const float* v, int64_t M, int64_t K, int32_t C, const double* part, const float* weight,
+                     double* part2, ma_stream_t stream);
+int ma_gln2_bwd_dwconv(const float* d_h, const float* d0, const float* y0, int64_t M, int64_t K, int32_t C, const double* part_a,
+                       const double* part_b, const double* part2_h, const float* weight1, const float* weight2, const float* Wt,
+                       int32_t P, int32_t dilation, float* d_u, double* part2_u, float* d_weight2_part, float* d_Wt_part,
+                       ma_stream_t stream);
+int ma_gln1_bwd(const float* d_u, const float* y0, int64_t M, int64_t K, int32_t C, const double* part_a, const double* part2_u,
+                const float* weight, void* out, int32_t out_bf16, float* d_weight_part, ma_stream_t stream);
+int ma_sgd_momentum_f32(float* param, const float* grad, float* buf, int64_t n, float lr, float momentum, float weight_decay,
+                        int32_t first_step, void* mirror_bf16, ma_stream_t stream);
+
 /* ---- Bidirectional LSTM layer, inference (mindaudio/models/deepspeech2.py:119-187: nn.LSTM(bidirectional=True, has_bias=True), the
  * two directions summed) --------------------------------------------------------------------------------------------------------------
  * Cell, PyTorch gate order i, f, g, o:  gates = x W_ih^T + b_ih + h W_hh^T + b_hh,  c' = sigmoid(f) c + sigmoid(i) tanh(g),

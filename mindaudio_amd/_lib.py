@@ -441,6 +441,18 @@ PROTOTYPES = {
     "ma_gln_apply_bf16": (ctypes.c_int, [vp, i64, i64, i32, vp, vp, vp]),
     "ma_tasnet_decode_f32": (ctypes.c_int, [vp, vp, i64, i64, i32, i32, vp, i32, i32, vp, vp]),
     "ma_si_snr_pairwise": (ctypes.c_int, [vp, vp, vp, i64, i32, i64, vp, vp]),
+    # ---- Conv-TasNet training ----
+    "ma_gln_dwconv_prelu_train": (ctypes.c_int, [vp, i64, i64, i32, vp, vp, i32, i32, vp, vp, vp, vp, vp]),
+    "ma_gln_apply_f32": (ctypes.c_int, [vp, i64, i64, i32, vp, vp, vp]),
+    "ma_si_snr_grad_f32": (ctypes.c_int, [vp, vp, vp, vp, i64, i32, i64, vp, vp]),
+    "ma_tasnet_decode_bwd_parts": (i32, [i64, i32, i32, i32]),
+    "ma_tasnet_decode_bwd_f32": (ctypes.c_int, [vp, vp, vp, i64, i64, i32, i32, vp, i32, i32, vp, vp, vp, vp]),
+    "ma_tasnet_encode_bwd_parts": (i32, [i64, i32, i32]),
+    "ma_tasnet_encode_bwd_f32": (ctypes.c_int, [vp, i64, i64, i64, vp, vp, vp, vp, vp, i32, i32, vp, vp]),
+    "ma_gln_bwd_stats": (ctypes.c_int, [vp, vp, i64, i64, i32, vp, vp, vp, vp]),
+    "ma_gln2_bwd_dwconv": (ctypes.c_int, [vp, vp, vp, i64, i64, i32, vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, vp]),
+    "ma_gln1_bwd": (ctypes.c_int, [vp, vp, i64, i64, i32, vp, vp, vp, vp, i32, vp, vp]),
+    "ma_sgd_momentum_f32": (ctypes.c_int, [vp, vp, vp, i64, f32, f32, f32, i32, vp, vp]),
     # ---- LSTM layer, DeepSpeech2 ----
     "ma_lstm_workspace_bytes": (i64, [i64, i64, i32, i64]),
     "ma_lstm_pack_f32": (ctypes.c_int, [vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp]),

@@ -1,5 +1,5 @@
-"""Conv-TasNet on MI355X - mirror of mindaudio.models.conv_tasnet.ConvTasNet (conv_tasnet.py:12-77), forward only (inference and
-evaluation; the backward is not built).
+"""Conv-TasNet on MI355X - mirror of mindaudio.models.conv_tasnet.ConvTasNet (conv_tasnet.py:12-77), the forward (inference and
+evaluation); the training step around the same weights is models/conv_tasnet_train.py.
 
 Activations are time-major (M * K, channels) float32.  The 1 x 1 convolutions (bottleneck, conv1x1, pointwise_conv, mask_conv1x1)
 are ma_gemm_bf16 calls with float32 outputs, the block's residual added in the GEMM epilogue; the strided encoder, PReLU, global
