@@ -23,6 +23,7 @@
 
 #include "gemm8.h"
 #include "launch.h"
+#include "reduce_splits.h"
 
 namespace ma {
 
@@ -709,22 +710,10 @@ __global__ __launch_bounds__(kWsThreads, 1) void gemm_ws512_kernel(const GemmPar
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the duplicate tile loads land before the LDS is handed back
 }
 
-// out[m][n] (+)= alpha * sum_s part[s][m][n]
-__global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restrict__ part, int splits, int64_t mn,
-                                                            float* __restrict__ out, int64_t ldo, int N, float alpha,
-                                                            int accumulate) {
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < mn; i += (int64_t)gridDim.x * 256) {
-    float s = 0.0f;
-    for (int k = 0; k < splits; ++k) s += part[(int64_t)k * mn + i];
-    const int64_t m = i / N;
-    float* o = out + m * ldo + (i - m * N);
-    *o = accumulate ? *o + alpha * s : alpha * s;
-  }
-}
-
 // The split-K product feeding a branch JOIN (N = 256; ma_gemm_bf16_splitk_join_f32): the fixed-order sum of the splits and the join's
 // element-wise work - z = bf16((sum + bias) * row_scale); out = residual + alpha * dropout(z); optionally LayerNorm(out) - one wave per
-// row, 4 columns per lane.  The arithmetic of splitk_reduce_kernel, a bf16 rounding, dropout_add_kernel and layernorm_kernel<1> in turn.
+// row, 4 columns per lane.  The arithmetic of tn_reduce_kernel (reduce_splits.hip), a bf16 rounding, dropout_add_kernel and
+// layernorm_kernel<1> in turn.
 __global__ __launch_bounds__(256) void splitk_join_kernel(const float* __restrict__ part, int splits, int64_t M,
                                                           float* __restrict__ out, int64_t ldo, TrainEpi e) {
   const int lane = threadIdx.x & 63;
@@ -1096,12 +1085,8 @@ int ma_gemm_bf16_splitk_f32(const void* A, int64_t lda, const void* W, int64_t l
   if (workspace_bytes < (int64_t)splits * M * N * 4) return MA_ERR_WORKSPACE;
   const int rc = launch_gemm_tile<64, 128, 3, 0, 2>(p, (hipStream_t)stream);
   if (rc != MA_OK) return rc;
-  const int64_t mn = M * N;
-  int64_t blocks = (mn + 255) / 256;
-  if (blocks > 2048) blocks = 2048;
-  MA_LAUNCH(splitk_reduce_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream,
-            reinterpret_cast<const float*>(workspace), splits, mn, out, ldo, (int)N, alpha, (int)accumulate);
-  return MA_OK;
+  return reduce_splits_launch(reinterpret_cast<const float*>(workspace), splits, M * N, out, ldo, (int)N, alpha, (int)accumulate,
+                              (hipStream_t)stream);
 }
 
 int ma_gemm_bf16_splitk_join_f32(const void* A, int64_t lda, const void* W, int64_t ldw, float* out, int64_t ldo, int64_t M,

@@ -26,7 +26,7 @@
 #include <type_traits>
 
 #include "../../include/mindaudio_amd.h"
-#include "gemm_tn8.h"
+#include "gemm_tn_common.h"
 #include "device_common.h"
 #include "gemm8.h"
 #include "launch.h"
@@ -52,19 +52,14 @@ struct Tn8Group {
   int32_t n, total;
 };
 
-// IM2COL: B is the im2col matrix of a 3x3 stride-2 valid convolution over an NHWC activation (batch, H, Wd, C), C % 256 == 0: row
-// m = (b, ho, wo), column (kh, kw, c) - the 256 columns of a tile are the channels [c0, c0 + 256) of ONE tap (kh, kw)
-struct Tn8Conv {
-  int32_t H, Wd, C, Ho, Wo;
-  float inv_wo, inv_ho;
-};
-
 // One 256 x 256 tile over the K-tiles [kt_lo, kt_lo + nk) of the contraction (Kc rows in all): out (+ i0 rows, j0 columns) is stored.
+// IM2COL: B is the im2col matrix `cv` (gemm_tn_common.h), C % 256 == 0: the 256 columns of a tile are the channels [c0, c0 + 256) of
+// one tap.
 template <bool IM2COL>
 __device__ __forceinline__ void t8_tile(char* smem, const uint16_t* const A, const uint16_t* const B, float* const out,
                                         float* const colsum, const int lda, const int ldb, const int ldo, const int Kc,
                                         const int kt_lo, const int nk, const int i0, const int j0, const bool want_cs,
-                                        const Tn8Conv cv) {
+                                        const TnConv cv) {
   const int tid = threadIdx.x, lane = tid & 63;
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wr = wid >> 2, wc = wid & 3;
@@ -85,12 +80,7 @@ __device__ __forceinline__ void t8_tile(char* smem, const uint16_t* const A, con
     for (int q = 0; q < 2; ++q) {
       a_src[q][ii] = A + i0 + (sch >> 3) * 128 + 64 * q + (sch & 7) * 8;
       const int col = j0 + (sch >> 2) * 64 + 32 * q + (sch & 3) * 8;
-      if (IM2COL) {
-        const int khw = col / cv.C, kh = khw / 3, kw = khw - 3 * kh;
-        b_src[q][ii] = B + ((int64_t)kh * cv.Wd + kw) * cv.C + (col - khw * cv.C);
-      } else {
-        b_src[q][ii] = B + col;
-      }
+      b_src[q][ii] = IM2COL ? tn_conv_tap(cv, B, col) : B + col;
     }
   }
   int64_t offa[2], offb[2];  // row offsets of the K-tile being staged
@@ -100,13 +90,7 @@ __device__ __forceinline__ void t8_tile(char* smem, const uint16_t* const A, con
       int m = (kt_lo + kt) * kT8BK + srow[ii];
       if (m >= Kc) m = Kc - 1;  // rows past Kc: finite duplicates, masked out of the A fragments below
       offa[ii] = (int64_t)m * lda;
-      if (IM2COL) {
-        const int t = div_small(m, cv.Wo, cv.inv_wo), wo = m - t * cv.Wo;
-        const int b = div_small(t, cv.Ho, cv.inv_ho), ho = t - b * cv.Ho;
-        offb[ii] = (((int64_t)b * cv.H + 2 * ho) * cv.Wd + 2 * wo) * cv.C;
-      } else {
-        offb[ii] = (int64_t)m * ldb;
-      }
+      offb[ii] = IM2COL ? tn_conv_row(cv, m) : (int64_t)m * ldb;
     }
   };
   // unit index U in a buffer: 0 = A q0, 1 = B q0, 2 = B q1, 3 = A q1; the K-tile is the one set_rows was last called for
@@ -242,19 +226,19 @@ __global__ __launch_bounds__(k8Threads, 1) void gemm_tn8_group_kernel(const Tn8G
   const int t = bid - g.it[item].first, tiles_n = g.it[item].tiles_n;
   const int tile_m = t / tiles_n, tile_n = t - tile_m * tiles_n;
   t8_tile<false>(smem, g.it[item].A, g.it[item].B, g.it[item].out, g.it[item].colsum, g.it[item].lda, g.it[item].ldb, g.it[item].ldo,
-                 Kc, 0, (Kc + kT8BK - 1) / kT8BK, tile_m * 256, tile_n * 256, g.it[item].colsum != nullptr && tile_n == 0, Tn8Conv{});
+                 Kc, 0, (Kc + kT8BK - 1) / kT8BK, tile_m * 256, tile_n * 256, g.it[item].colsum != nullptr && tile_n == 0, TnConv{});
 }
 
 // The weight gradient of the subsampling layer's second convolution: dW (Cout, 9 C) = dy^T im2col(act), the contraction
 // (batch x Ho x Wo = 193 800 rows at cfg 4) split over blockIdx.y; partial products [split][Cout][9 C] and partial column sums
-// [split][Cout] go to the workspace and are added in split order by tn_reduce_kernel (gemm_tn_bf16.hip).
+// [split][Cout] go to the workspace and are added in split order by tn_reduce_kernel (reduce_splits.hip).
 struct Tn8ConvParams {
   const uint16_t* dy;
   const uint16_t* act;
   float* part;
   float* cs_part;  // NULL: no bias gradient
   int32_t ld_dy, Cout, No, Kc, kt_split, tiles_n;
-  Tn8Conv cv;
+  TnConv cv;
 };
 __global__ __launch_bounds__(k8Threads, 1) void gemm_tn8_conv_kernel(const Tn8ConvParams p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];

@@ -9,17 +9,18 @@
 // rows 0..3 — measured with tools/ubench/tr_read.hip), two reads per 8-element fragment.  The 16 rows touched by one
 // read share a column offset, so 32-byte granules of every LDS row are XOR-swizzled by row bits (applied to the
 // per-lane SOURCE address of the LDS-DMA, whose destinations are lane-linear).
-// The contraction is split over blockIdx.y; partial products go to a workspace and are summed by splitk_reduce_kernel
-// (deterministic).  Optional column sums of A (bias gradients) ride on one extra MFMA per fragment with an all-ones
+// The contraction is split over blockIdx.y; partial products go to a workspace and are summed in split order by tn_reduce_kernel
+// (reduce_splits.hip; deterministic).  Optional column sums of A (bias gradients) ride on one extra MFMA per fragment with an all-ones
 // operand in the workgroups of the first column tile.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "../../include/mindaudio_amd.h"
 
-#include "gemm_tn8.h"
+#include "gemm_tn_common.h"
 #include "device_common.h"
 #include "launch.h"
+#include "reduce_splits.h"
 
 namespace ma {
 
@@ -32,10 +33,7 @@ struct TnParams {
   float* cs_part;     // [splits][Mo_store]
   int64_t lda, ldb;
   int32_t Mo, No, Kc, Mo_store, kt_split;
-  // IM2COL: B is the im2col matrix of a 3x3 stride-2 valid convolution over an NHWC activation (batch, H, Wd, C):
-  // row m = (b, ho, wo), column (kh, kw, c); B points at the activation
-  int32_t H, Wd, C, Ho, Wo;
-  float inv_wo, inv_ho;
+  TnConv cv;  // IM2COL: B is this im2col matrix (gemm_tn_common.h), C % 128 == 0
 };
 
 constexpr int kTnBK = 64, kTnStages = 3, kTnThreads = 256;
@@ -82,12 +80,7 @@ __device__ __forceinline__ void tn_body(const TnParams& p, const int bx, const i
     int col = j0 + sch * 8;
     if (col + 8 > p.No) col = p.No - 8;
     b_row[g] = r;
-    if (IM2COL) {  // C % 128 == 0: the 128 columns of this tile share one (kh, kw)
-      const int khw = col / p.C, kh = khw / 3, kw = khw - 3 * kh;
-      b_src[g] = p.B + ((int64_t)kh * p.Wd + kw) * p.C + (col - khw * p.C);
-    } else {
-      b_src[g] = p.B + col;
-    }
+    b_src[g] = IM2COL ? tn_conv_tap(p.cv, p.B, col) : p.B + col;  // (the 128 columns of this tile share one tap)
   }
   const int nk_all = (p.Kc + kTnBK - 1) / kTnBK;
   const int kt_lo = by * p.kt_split;
@@ -105,14 +98,7 @@ __device__ __forceinline__ void tn_body(const TnParams& p, const int bx, const i
     for (int g = 0; g < GB; ++g) {
       int m = m0 + b_row[g];
       if (m >= p.Kc) m = p.Kc - 1;
-      int64_t roff;
-      if (IM2COL) {
-        const int t = div_small(m, p.Wo, p.inv_wo), wo = m - t * p.Wo;
-        const int b = div_small(t, p.Ho, p.inv_ho), ho = t - b * p.Ho;
-        roff = (((int64_t)b * p.H + 2 * ho) * p.Wd + 2 * wo) * p.C;
-      } else {
-        roff = (int64_t)m * p.ldb;
-      }
+      const int64_t roff = IM2COL ? tn_conv_row(p.cv, m) : (int64_t)m * p.ldb;
       __builtin_amdgcn_global_load_lds((gl_cvoid_t*)(b_src[g] + roff),
                                        (lds_void_t*)(st + kABytes + (wave + 4 * g) * 1024), 16, 0, 0);
     }
@@ -264,107 +250,6 @@ __global__ __launch_bounds__(kTnThreads, 2) void gemm_tn_group_kernel(const TnGr
   tn_body<64, false>(g.p[it], local % tiles, local / tiles, smem);
 }
 
-__global__ __launch_bounds__(256) void tn_reduce_kernel(const float* __restrict__ part, int splits, int64_t mn,
-                                                        float* __restrict__ out, int64_t ldo, int N, float alpha,
-                                                        int accumulate) {
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < mn; i += (int64_t)gridDim.x * 256) {
-    float s = 0.0f;
-    for (int k = 0; k < splits; ++k) s += part[(int64_t)k * mn + i];
-    const int64_t m = i / N;
-    float* o = out + m * ldo + (i - m * N);
-    *o = accumulate ? *o + alpha * s : alpha * s;
-  }
-}
-
-// The split sums of a list of products in one launch (ma_reduce_splits_batch_f32): splits are added in the order k = 0 .. splits - 1.
-//   short items (accumulate bit 1 clear; weight-gradient splits, a handful of partials of many elements): workgroup b owns 1024
-//     consecutive elements of item block_item[b], one thread per 4 elements;
-//   tall items (accumulate bit 1 set; per-workgroup partials of a parameter reduction: hundreds of partials of a few hundred
-//     elements): workgroup b owns 16 consecutive elements, thread (tx = 4 elements, ty = one of 64 groups of partials) adds the
-//     partials ty, ty + 64, ... in order and the 64 group sums are added in order through LDS - a fixed order either way.
-__global__ __launch_bounds__(256) void tn_reduce_batch_kernel(const ma_reduce_item_t* __restrict__ items,
-                                                              const int32_t* __restrict__ block_item) {
-  __shared__ float4 red[64][4];
-  const ma_reduce_item_t it = items[block_item[blockIdx.x]];
-  const int64_t ps = it.pstride ? (int64_t)it.pstride : it.mn;
-  const bool acc = it.accumulate & 1, tall = it.accumulate & 2;
-  const bool vec = !(it.N & 3) && !(it.ldo & 3) && !(it.mn & 3) && !(ps & 3) &&
-                   !((reinterpret_cast<uintptr_t>(it.out) | reinterpret_cast<uintptr_t>(it.part)) & 15);  // a piece never straddles a row
-  auto store4 = [&](int64_t i0, float4 sum) {
-    const float v[4] = {sum.x, sum.y, sum.z, sum.w};
-    if (vec) {
-      const int64_t m = i0 / it.N;
-      float4* o = reinterpret_cast<float4*>(it.out + m * it.ldo + (i0 - m * it.N));
-      float4 r = make_float4(it.alpha * v[0], it.alpha * v[1], it.alpha * v[2], it.alpha * v[3]);
-      if (acc) {
-        const float4 old = *o;
-        r.x += old.x; r.y += old.y; r.z += old.z; r.w += old.w;
-      }
-      *o = r;
-      return;
-    }
-    for (int e = 0; e < 4 && i0 + e < it.mn; ++e) {
-      const int64_t i = i0 + e, m = i / it.N;
-      float* o = it.out + m * it.ldo + (i - m * it.N);
-      *o = acc ? *o + it.alpha * v[e] : it.alpha * v[e];
-    }
-  };
-  auto load4 = [&](int64_t k, int64_t i0) -> float4 {
-    const float* src = it.part + k * ps + i0;
-    if (vec) return *reinterpret_cast<const float4*>(src);
-    return make_float4(src[0], i0 + 1 < it.mn ? src[1] : 0.f, i0 + 2 < it.mn ? src[2] : 0.f, i0 + 3 < it.mn ? src[3] : 0.f);
-  };
-  if (tall) {
-    const int tx = threadIdx.x & 3, ty = threadIdx.x >> 2;
-    const int64_t i0 = ((int64_t)((int)blockIdx.x - it.first_block) * 4 + tx) * 4;
-    float4 sum = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (i0 < it.mn) {
-      // twelve partials of a thread group in flight (the depthwise convolution's 640 partials were ten dependent round trips at four)
-      int k = ty;
-      for (; k + 11 * 64 < it.splits; k += 12 * 64) {
-        float4 v[12];
-#pragma unroll
-        for (int u = 0; u < 12; ++u) v[u] = load4(k + 64 * u, i0);
-#pragma unroll
-        for (int u = 0; u < 12; ++u) { sum.x += v[u].x; sum.y += v[u].y; sum.z += v[u].z; sum.w += v[u].w; }
-      }
-#pragma unroll 4
-      for (; k < it.splits; k += 64) {
-        const float4 v = load4(k, i0);
-        sum.x += v.x; sum.y += v.y; sum.z += v.z; sum.w += v.w;
-      }
-    }
-    red[ty][tx] = sum;
-    __syncthreads();
-    if (ty == 0 && i0 < it.mn) {
-      sum = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll 8
-      for (int k = 0; k < 64; ++k) {
-        const float4 v = red[k][tx];
-        sum.x += v.x; sum.y += v.y; sum.z += v.z; sum.w += v.w;
-      }
-      store4(i0, sum);
-    }
-    return;
-  }
-  const int64_t i0 = ((int64_t)((int)blockIdx.x - it.first_block) * 256 + threadIdx.x) * 4;
-  if (i0 >= it.mn) return;
-  float4 sum = make_float4(0.f, 0.f, 0.f, 0.f);
-  int k = 0;
-  for (; k + 8 <= it.splits; k += 8) {  // eight partials in flight (the partials are cold: written by GEMMs many launches ago)
-    float4 v[8];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) v[u] = load4(k + u, i0);
-#pragma unroll
-    for (int u = 0; u < 8; ++u) { sum.x += v[u].x; sum.y += v[u].y; sum.z += v[u].z; sum.w += v[u].w; }
-  }
-  for (; k < it.splits; ++k) {
-    const float4 v = load4(k, i0);
-    sum.x += v.x; sum.y += v.y; sum.z += v.z; sum.w += v.w;
-  }
-  store4(i0, sum);
-}
-
 static int tn_plan(int64_t Mo, int64_t No, int64_t Kc, int* bm, int* kt_split) {
   // 128-row tiles when there are enough of them; about two workgroups per CU; >= 8 K-tiles per split
   const int64_t big = ((Mo + 127) / 128) * ((No + 127) / 128);
@@ -393,42 +278,79 @@ MA_LDS_ATTR(gemm_tn_group_kernel, 80 * 1024);  // (the launch asks for tn_lds_by
 
 using namespace ma;
 
-extern "C" {
+// The checks of one TN product, in the order every entry point answers in: null pointers and sizes, then & 7 / strides / 2^31, then
+// the 16-byte alignment.  `part` is the partial buffer (the workspace); out / ldo take part only where the entry point has an `out`.
+static int tn_check(const void* A, int64_t lda, const void* B, int64_t ldb, const void* part, int64_t Mo, int64_t No, int64_t Kc,
+                    int64_t Mo_store, bool has_out = false, const void* out = nullptr, int64_t ldo = 0) {
+  if (!A || !B || (has_out && !out) || !part || Mo < 8 || No < 8 || Kc < 1 || Mo_store < 1 || Mo_store > Mo) return MA_ERR_INVALID_ARG;
+  if ((Mo & 7) || (No & 7) || (lda & 7) || (ldb & 7) || lda < Mo || ldb < No || (has_out && ldo < No) || Mo > 0x7fffffff ||
+      No > 0x7fffffff || Kc > 0x7fffffff)
+    return MA_ERR_UNSUPPORTED;
+  if ((reinterpret_cast<uintptr_t>(A) | reinterpret_cast<uintptr_t>(B) | reinterpret_cast<uintptr_t>(part)) & 15) return MA_ERR_INVALID_ARG;
+  return MA_OK;
+}
 
-static int tn_launch(TnParams& p, bool im2col, float* out, int64_t ldo, float alpha, int accumulate, void* workspace,
-                     int64_t workspace_bytes, hipStream_t s, bool reduce = true) {
-  int bm = 64, kt = 0;
-  const int splits = tn_plan(p.Mo, p.No, p.Kc, &bm, &kt);
+// colsum: non-NULL = the kernel also writes partial column sums (to cs_part; the pointer itself is only read by the reduction)
+static TnParams tn_params(const void* A, int64_t lda, const void* B, int64_t ldb, void* part, float* colsum, int64_t Mo, int64_t No,
+                          int64_t Kc, int64_t Mo_store) {
+  TnParams p = TnParams{};
+  p.A = reinterpret_cast<const uint16_t*>(A);
+  p.B = reinterpret_cast<const uint16_t*>(B);
+  p.part = reinterpret_cast<float*>(part);
+  p.colsum = colsum;
+  p.lda = lda;
+  p.ldb = ldb;
+  p.Mo = (int32_t)Mo;
+  p.No = (int32_t)No;
+  p.Kc = (int32_t)Kc;
+  p.Mo_store = (int32_t)Mo_store;
+  return p;
+}
+
+// Plans the product (tile height *bm, return value = splits, p.kt_split) and places its partial column sums behind the partial
+// products in the `bytes` bytes at p.part; 0 splits = the buffer is too small.
+static int tn_place(TnParams& p, int64_t bytes, int* bm) {
+  int kt = 0;
+  const int splits = tn_plan(p.Mo, p.No, p.Kc, bm, &kt);
+  if (bytes < tn_partial_bytes(splits, p.Mo_store, p.No)) return 0;
   p.kt_split = kt;
-  if (workspace_bytes < (int64_t)splits * p.Mo_store * (p.No + 1) * 4) return MA_ERR_WORKSPACE;
-  p.cs_part = reinterpret_cast<float*>(workspace) + (int64_t)splits * p.Mo_store * p.No;
+  p.cs_part = p.part + tn_cs_offset(splits, p.Mo_store, p.No);
+  return splits;
+}
+
+// The partial products (and partial column sums) of p into the `bytes` bytes at p.part; *splits = how many there are.
+static int tn_launch(TnParams& p, bool im2col, int64_t bytes, hipStream_t s, int* splits) {
+  int bm = 64;
+  *splits = tn_place(p, bytes, &bm);
+  if (*splits < 1) return MA_ERR_WORKSPACE;
   const int tiles = (int)(((p.Mo + bm - 1) / bm) * ((p.No + 127) / 128));
-  const int lds = kTnStages * (kTnBK * bm * 2 + kTnBK * 256);
 #define MA_TN_GO(BM_, IM_)                                                                                            \
   {                                                                                                                   \
-    MA_LAUNCH((gemm_tn_bf16_kernel<BM_, IM_>), dim3(tiles, splits), dim3(kTnThreads), lds, s, p);                     \
+    MA_LAUNCH((gemm_tn_bf16_kernel<BM_, IM_>), dim3(tiles, *splits), dim3(kTnThreads), tn_lds_bytes(bm), s, p);       \
   }
   if (bm == 128 && im2col) MA_TN_GO(128, true)
   else if (bm == 128) MA_TN_GO(128, false)
   else if (im2col) MA_TN_GO(64, true)
   else MA_TN_GO(64, false)
 #undef MA_TN_GO
-  if (!reduce) return MA_OK;
-  const int64_t mn = (int64_t)p.Mo_store * p.No;
-  int64_t blocks = (mn + 255) / 256;
-  if (blocks > 2048) blocks = 2048;
-  MA_LAUNCH(tn_reduce_kernel, dim3((unsigned)blocks), dim3(256), 0, s, reinterpret_cast<const float*>(workspace), splits, mn,
-            out, ldo, p.No, alpha, accumulate);
-  if (p.colsum)  // colsum[i] += the splits' partial column sums, in split order
-    MA_LAUNCH(tn_reduce_kernel, dim3((unsigned)((p.Mo_store + 255) / 256)), dim3(256), 0, s, p.cs_part, splits, (int64_t)p.Mo_store,
-              p.colsum, (int64_t)p.Mo_store, p.Mo_store, 1.0f, 1);
   return MA_OK;
 }
+
+// out (rows, No) (+)= alpha * the sum of the `splits` partial products at `part`; colsum (rows) += the sum of the partial column sums
+// behind them (NULL: none) - both in split order
+static int tn_sum_splits(const float* part, int splits, int64_t rows, int64_t No, float* out, int64_t ldo, float alpha, int accumulate,
+                         float* colsum, hipStream_t s) {
+  const int rc = reduce_splits_launch(part, splits, rows * No, out, ldo, (int)No, alpha, accumulate, s);
+  if (rc != MA_OK || !colsum) return rc;
+  return reduce_splits_launch(part + tn_cs_offset(splits, rows, No), splits, rows, colsum, rows, (int)rows, 1.0f, 1, s);
+}
+
+extern "C" {
 
 int64_t ma_gemm_tn_workspace_bytes(int64_t Mo, int64_t No, int64_t Kc) {
   if (Mo < 1 || No < 1 || Kc < 1) return MA_ERR_INVALID_ARG;
   int bm = 0, kt = 0;
-  return (int64_t)tn_plan(Mo, No, Kc, &bm, &kt) * Mo * (No + 1) * 4;  // partial products + one partial column-sum vector per split
+  return tn_partial_bytes(tn_plan(Mo, No, Kc, &bm, &kt), Mo, No);
 }
 
 int32_t ma_gemm_tn_splits(int64_t Mo, int64_t No, int64_t Kc) {
@@ -440,81 +362,42 @@ int32_t ma_gemm_tn_splits(int64_t Mo, int64_t No, int64_t Kc) {
 int ma_gemm_tn_bf16_f32(const void* A, int64_t lda, const void* B, int64_t ldb, float* out, int64_t ldo, int64_t Mo,
                         int64_t No, int64_t Kc, int64_t Mo_store, float alpha, int32_t accumulate, float* colsum,
                         void* workspace, int64_t workspace_bytes, ma_stream_t stream) {
-  if (!A || !B || !out || !workspace || Mo < 8 || No < 8 || Kc < 1 || Mo_store < 1 || Mo_store > Mo) return MA_ERR_INVALID_ARG;
-  if ((Mo & 7) || (No & 7) || (lda & 7) || (ldb & 7) || lda < Mo || ldb < No || ldo < No || Mo > 0x7fffffff ||
-      No > 0x7fffffff || Kc > 0x7fffffff)
-    return MA_ERR_UNSUPPORTED;
-  if ((reinterpret_cast<uintptr_t>(A) & 15) || (reinterpret_cast<uintptr_t>(B) & 15) || (reinterpret_cast<uintptr_t>(workspace) & 15))
-    return MA_ERR_INVALID_ARG;
-  TnParams p = TnParams{};
-  p.A = reinterpret_cast<const uint16_t*>(A);
-  p.B = reinterpret_cast<const uint16_t*>(B);
-  p.part = reinterpret_cast<float*>(workspace);
-  p.colsum = colsum;
-  p.lda = lda;
-  p.ldb = ldb;
-  p.Mo = (int32_t)Mo;
-  p.No = (int32_t)No;
-  p.Kc = (int32_t)Kc;
-  p.Mo_store = (int32_t)Mo_store;
-  return tn_launch(p, false, out, ldo, alpha, accumulate, workspace, workspace_bytes, (hipStream_t)stream);
+  int rc = tn_check(A, lda, B, ldb, workspace, Mo, No, Kc, Mo_store, true, out, ldo);
+  if (rc != MA_OK) return rc;
+  TnParams p = tn_params(A, lda, B, ldb, workspace, colsum, Mo, No, Kc, Mo_store);
+  int splits = 0;
+  rc = tn_launch(p, false, workspace_bytes, (hipStream_t)stream, &splits);
+  if (rc != MA_OK) return rc;
+  return tn_sum_splits(p.part, splits, Mo_store, No, out, ldo, alpha, accumulate, colsum, (hipStream_t)stream);
 }
 
 int ma_gemm_tn_partial_bf16(const void* A, int64_t lda, const void* B, int64_t ldb, int64_t Mo, int64_t No, int64_t Kc,
                             int64_t Mo_store, int32_t with_colsum, void* partial, int64_t partial_bytes, ma_stream_t stream) {
-  if (!A || !B || !partial || Mo < 8 || No < 8 || Kc < 1 || Mo_store < 1 || Mo_store > Mo) return MA_ERR_INVALID_ARG;
-  if ((Mo & 7) || (No & 7) || (lda & 7) || (ldb & 7) || lda < Mo || ldb < No || Mo > 0x7fffffff || No > 0x7fffffff ||
-      Kc > 0x7fffffff)
-    return MA_ERR_UNSUPPORTED;
-  if ((reinterpret_cast<uintptr_t>(A) & 15) || (reinterpret_cast<uintptr_t>(B) & 15) || (reinterpret_cast<uintptr_t>(partial) & 15))
-    return MA_ERR_INVALID_ARG;
-  TnParams p = TnParams{};
-  p.A = reinterpret_cast<const uint16_t*>(A);
-  p.B = reinterpret_cast<const uint16_t*>(B);
-  p.part = reinterpret_cast<float*>(partial);
-  p.colsum = with_colsum ? reinterpret_cast<float*>(partial) : nullptr;  // (flag only: the kernel writes cs_part, set by tn_launch)
-  p.lda = lda;
-  p.ldb = ldb;
-  p.Mo = (int32_t)Mo;
-  p.No = (int32_t)No;
-  p.Kc = (int32_t)Kc;
-  p.Mo_store = (int32_t)Mo_store;
-  return tn_launch(p, false, nullptr, 0, 1.0f, 0, partial, partial_bytes, (hipStream_t)stream, false);
+  const int rc = tn_check(A, lda, B, ldb, partial, Mo, No, Kc, Mo_store);
+  if (rc != MA_OK) return rc;
+  TnParams p = tn_params(A, lda, B, ldb, partial, with_colsum ? reinterpret_cast<float*>(partial) : nullptr, Mo, No, Kc, Mo_store);
+  int splits = 0;
+  return tn_launch(p, false, partial_bytes, (hipStream_t)stream, &splits);
 }
 
 int ma_gemm_tn_partial_group_bf16(const ma_tn_item_t* items, int32_t n, ma_stream_t stream) {
   if (!items || n < 1) return MA_ERR_INVALID_ARG;
-  for (int base = 0; base < n; base += kTnGroupMax) {
+  for (int base = 0; base < n; base += kTnGroupMax) {  // checked and launched per group of eight: an error leaves the earlier groups issued
     const int cnt = n - base < kTnGroupMax ? n - base : kTnGroupMax;
     TnGroup g = TnGroup{};
     int total = 0;
     bool groupable = true;
     for (int k = 0; k < cnt; ++k) {
       const ma_tn_item_t& it = items[base + k];
-      if (!it.A || !it.B || !it.partial || it.Mo < 8 || it.No < 8 || it.Kc < 1 || it.Mo_store < 1 || it.Mo_store > it.Mo)
-        return MA_ERR_INVALID_ARG;
-      if ((it.Mo & 7) || (it.No & 7) || (it.lda & 7) || (it.ldb & 7) || it.lda < it.Mo || it.ldb < it.No || it.Mo > 0x7fffffff ||
-          it.No > 0x7fffffff || it.Kc > 0x7fffffff)
-        return MA_ERR_UNSUPPORTED;
-      if ((reinterpret_cast<uintptr_t>(it.A) | reinterpret_cast<uintptr_t>(it.B) | reinterpret_cast<uintptr_t>(it.partial)) & 15)
-        return MA_ERR_INVALID_ARG;
-      int bm = 64, kt = 0;
-      const int splits = tn_plan(it.Mo, it.No, it.Kc, &bm, &kt);
-      if (it.partial_bytes < (int64_t)splits * it.Mo_store * (it.No + 1) * 4) return MA_ERR_WORKSPACE;
-      if (bm != 64) groupable = false;
+      const int rc = tn_check(it.A, it.lda, it.B, it.ldb, it.partial, it.Mo, it.No, it.Kc, it.Mo_store);
+      if (rc != MA_OK) return rc;
       TnParams& p = g.p[k];
-      p.A = reinterpret_cast<const uint16_t*>(it.A);
-      p.B = reinterpret_cast<const uint16_t*>(it.B);
-      p.part = reinterpret_cast<float*>(it.partial);
-      p.colsum = it.with_colsum ? p.part : nullptr;  // (flag only: the kernel writes cs_part)
-      p.cs_part = p.part + (int64_t)splits * it.Mo_store * it.No;
-      p.lda = it.lda;
-      p.ldb = it.ldb;
-      p.Mo = (int32_t)it.Mo;
-      p.No = (int32_t)it.No;
-      p.Kc = (int32_t)it.Kc;
-      p.Mo_store = (int32_t)it.Mo_store;
-      p.kt_split = kt;
+      p = tn_params(it.A, it.lda, it.B, it.ldb, it.partial, it.with_colsum ? reinterpret_cast<float*>(it.partial) : nullptr, it.Mo, it.No,
+                    it.Kc, it.Mo_store);
+      int bm = 64;
+      const int splits = tn_place(p, it.partial_bytes, &bm);
+      if (splits < 1) return MA_ERR_WORKSPACE;
+      if (bm != 64) groupable = false;
       g.tiles[k] = (int)(((it.Mo + 63) / 64) * ((it.No + 127) / 128));
       g.first[k] = total;
       total += g.tiles[k] * splits;
@@ -530,23 +413,15 @@ int ma_gemm_tn_partial_group_bf16(const ma_tn_item_t* items, int32_t n, ma_strea
       }
       continue;
     }
-    const int lds = kTnStages * (kTnBK * 64 * 2 + kTnBK * 256);
-    MA_LAUNCH(gemm_tn_group_kernel, dim3((unsigned)total), dim3(kTnThreads), lds, (hipStream_t)stream, g);
+    MA_LAUNCH(gemm_tn_group_kernel, dim3((unsigned)total), dim3(kTnThreads), tn_lds_bytes(64), (hipStream_t)stream, g);
   }
-  return MA_OK;
-}
-
-int ma_reduce_splits_batch_f32(const ma_reduce_item_t* items, const int32_t* block_item, int32_t n_blocks, ma_stream_t stream) {
-  if (!items || !block_item || n_blocks < 1) return MA_ERR_INVALID_ARG;
-  MA_LAUNCH(tn_reduce_batch_kernel, dim3((unsigned)n_blocks), dim3(256), 0, (hipStream_t)stream, items, block_item);
   return MA_OK;
 }
 
 int64_t ma_conv2d_3x3s2_dw_workspace_bytes(int64_t rows, int64_t C, int64_t Cout) {
   if (rows < 1 || C < 1 || Cout < 1) return MA_ERR_INVALID_ARG;
   const int64_t old_bytes = ma_gemm_tn_workspace_bytes(Cout, 9 * C, rows);
-  const int64_t s8 = tn8_conv_splits(rows, C, Cout);
-  const int64_t new_bytes = s8 * Cout * (9 * C + 1) * 4;
+  const int64_t new_bytes = tn_partial_bytes(tn8_conv_splits(rows, C, Cout), Cout, 9 * C);
   return new_bytes > old_bytes ? new_bytes : old_bytes;
 }
 
@@ -557,38 +432,23 @@ int ma_conv2d_3x3s2_dw_bf16(const void* dy, int64_t ld_dy, const void* act, int6
   if ((C % 128) || (Cout & 7) || (ld_dy & 7) || ld_dy < Cout) return MA_ERR_UNSUPPORTED;
   const int64_t Ho = (H - 3) / 2 + 1, Wo = (Wd - 3) / 2 + 1, M = batch * Ho * Wo;
   if (M >= (1 << 24)) return MA_ERR_UNSUPPORTED;
+  float* part = reinterpret_cast<float*>(workspace);
   // 256 x 256 tiles (gemm_tn8_bf16.hip) when the shape fits and the caller's workspace holds its partials: half the operand bytes per
   // flop of the 128 x 128 tile below
-  const int s8 = tn8_conv_splits(M, C, Cout);
-  if (s8 > 0 && (ld_dy & 7) == 0 && workspace_bytes >= (int64_t)s8 * Cout * (9 * C + 1) * 4) {
-    float* part = reinterpret_cast<float*>(workspace);
-    float* cs_part = part + (int64_t)s8 * Cout * 9 * C;
-    const int rc = tn8_conv_launch(dy, ld_dy, act, batch, H, Wd, C, Cout, part, dbias ? cs_part : nullptr, (hipStream_t)stream);
+  int splits = tn8_conv_splits(M, C, Cout);
+  if (splits > 0 && workspace_bytes >= tn_partial_bytes(splits, Cout, 9 * C)) {
+    const int rc = tn8_conv_launch(dy, ld_dy, act, batch, H, Wd, C, Cout, part, dbias ? part + tn_cs_offset(splits, Cout, 9 * C) : nullptr,
+                                   (hipStream_t)stream);
     if (rc != MA_OK) return rc;
-    const int64_t mn = Cout * 9 * C;
-    int64_t blocks = (mn + 255) / 256;
-    if (blocks > 2048) blocks = 2048;
-    MA_LAUNCH(tn_reduce_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, part, s8, mn, dw, 9 * C, (int32_t)(9 * C), 1.0f,
-              1);
-    if (dbias)
-      MA_LAUNCH(tn_reduce_kernel, dim3((unsigned)((Cout + 255) / 256)), dim3(256), 0, (hipStream_t)stream, cs_part, s8, Cout, dbias, Cout,
-                (int32_t)Cout, 1.0f, 1);
-    return MA_OK;
+  } else {
+    TnParams p = tn_params(dy, ld_dy, act, 0, workspace, dbias, Cout, 9 * C, M, Cout);
+    p.cv.H = (int32_t)H; p.cv.Wd = (int32_t)Wd; p.cv.C = (int32_t)C; p.cv.Ho = (int32_t)Ho; p.cv.Wo = (int32_t)Wo;
+    p.cv.inv_wo = 1.0f / (float)Wo;
+    p.cv.inv_ho = 1.0f / (float)Ho;
+    const int rc = tn_launch(p, true, workspace_bytes, (hipStream_t)stream, &splits);
+    if (rc != MA_OK) return rc;
   }
-  TnParams p = TnParams{};
-  p.A = reinterpret_cast<const uint16_t*>(dy);
-  p.B = reinterpret_cast<const uint16_t*>(act);
-  p.part = reinterpret_cast<float*>(workspace);
-  p.colsum = dbias;
-  p.lda = ld_dy;
-  p.Mo = (int32_t)Cout;
-  p.No = (int32_t)(9 * C);
-  p.Kc = (int32_t)M;
-  p.Mo_store = (int32_t)Cout;
-  p.H = (int32_t)H; p.Wd = (int32_t)Wd; p.C = (int32_t)C; p.Ho = (int32_t)Ho; p.Wo = (int32_t)Wo;
-  p.inv_wo = 1.0f / (float)Wo;
-  p.inv_ho = 1.0f / (float)Ho;
-  return tn_launch(p, true, dw, 9 * C, 1.0f, 1, workspace, workspace_bytes, (hipStream_t)stream);
+  return tn_sum_splits(part, splits, Cout, 9 * C, dw, 9 * C, 1.0f, 1, dbias, (hipStream_t)stream);
 }
 
 }  // extern "C"

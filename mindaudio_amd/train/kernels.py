@@ -107,6 +107,13 @@ def gemm_tn_direct_ok(a, b, out):
             a.data_ptr() % 16 == 0 and b.data_ptr() % 16 == 0 and out.data_ptr() % 16 == 0)
 
 
+def _fill_direct_item(it, a, b, out, colsum):
+    """One slot of a TnDirectItem table: out (Mo, No) = a^T b for a (Kc, Mo), b (Kc, No); colsum (Mo) or None."""
+    it.A, it.B, it.out, it.colsum = a.data_ptr(), b.data_ptr(), out.data_ptr(), (colsum.data_ptr() if colsum is not None else None)
+    it.lda, it.ldb, it.ldo = a.stride(0), b.stride(0), out.stride(0)
+    it.Mo, it.No, it.Kc = a.shape[1], b.shape[1], a.shape[0]
+
+
 def gemm_tn_direct_group(quads):
     """out (Mo, No) f32 = a^T b and colsum (Mo) = column sums of a (or None) for a list of (a, b, out, colsum): one launch per
     ma_gemm_tn_direct_max_items() products, every 256 x 256 tile with the full contraction (stored, not accumulated)."""
@@ -115,10 +122,8 @@ def gemm_tn_direct_group(quads):
     for lo in range(0, len(quads), cap):
         part = quads[lo:lo + cap]
         items = (_lib.TnDirectItem * len(part))()
-        for it, (a, b, out, colsum) in zip(items, part):
-            it.A, it.B, it.out, it.colsum = a.data_ptr(), b.data_ptr(), out.data_ptr(), (colsum.data_ptr() if colsum is not None else None)
-            it.lda, it.ldb, it.ldo = a.stride(0), b.stride(0), out.stride(0)
-            it.Mo, it.No, it.Kc = a.shape[1], b.shape[1], a.shape[0]
+        for it, quad in zip(items, part):
+            _fill_direct_item(it, *quad)
         _lib.check(lib.ma_gemm_tn_direct_group_bf16(items, len(part), _s()), "gemm_tn_direct_group")
 
 
@@ -139,10 +144,7 @@ class DirectGroup:
             # nothing but the launch count (a 7-layer decoder queues 49 products into one group)
             self.launch()
             self.clear()
-        it = self.items[self.n]
-        it.A, it.B, it.out, it.colsum = a.data_ptr(), b.data_ptr(), out.data_ptr(), (colsum.data_ptr() if colsum is not None else None)
-        it.lda, it.ldb, it.ldo = a.stride(0), b.stride(0), out.stride(0)
-        it.Mo, it.No, it.Kc = a.shape[1], b.shape[1], a.shape[0]
+        _fill_direct_item(self.items[self.n], a, b, out, colsum)
         self.n += 1
         self.keep.append((a, b))
 

@@ -124,6 +124,34 @@ def test_gemm8_schedule_and_launch_helpers_have_one_home():
         assert "MA_G8_MAINLOOP(" in files[fn] and '#include "gemm8.h"' in files[fn], fn
 
 
+# files where the text "+ 1) * 4" is something else than the size of a TN partial buffer
+_OTHER_PLUS_ONE_TIMES_FOUR = {
+    "decoder_kernels.hip": "LDS rows of kcap + 1 floats (bank padding)",
+    "ctc.hip": "the 2 L + 1 states of the CTC lattice",
+}
+
+
+def test_tn_checks_plans_and_split_sums_have_one_home():
+    """csrc/reduce_splits.hip holds the kernels that sum partials and the one launch rule of tn_reduce_kernel; gemm_tn_common.h the
+    size of a TN partial buffer: no other file launches a reduction kernel, keeps a copy of it (splitk_reduce_kernel was one),
+    caps a reduction grid or spells the size out."""
+    csrc = os.path.join(ROOT, "mindaudio_amd", "csrc")
+    files = {fn: open(os.path.join(csrc, fn)).read() for fn in sorted(os.listdir(csrc)) if fn.endswith((".hip", ".h", ".inc"))}
+    hip = {fn: src for fn, src in files.items() if fn.endswith(".hip")}
+    assert [fn for fn, src in hip.items() if "MA_LAUNCH(tn_reduce_kernel" in src] == ["reduce_splits.hip"]
+    assert [fn for fn, src in hip.items() if "MA_LAUNCH(tn_reduce_batch_kernel" in src] == ["reduce_splits.hip"]
+    assert [fn for fn, src in files.items() if "splitk_reduce_kernel" in src] == []
+    assert sum(src.count("blocks > 2048") for src in hip.values()) == 1 and "blocks > 2048" in hip["reduce_splits.hip"]
+    sized = [fn for fn, src in files.items() if "+ 1) * 4" in src and fn not in _OTHER_PLUS_ONE_TIMES_FOUR]
+    assert sized == ["gemm_tn_common.h"] and files["gemm_tn_common.h"].count("+ 1) * 4") == 1
+    tn = hip["gemm_tn_bf16.hip"]
+    assert "MA_LAUNCH(tn_reduce" not in tn and "reduce_splits_launch(" in tn and "reduce_splits_launch(" in hip["gemm_bf16.hip"]
+    # at most one copy of each argument check
+    for check in ("Mo_store > Mo", "(Mo & 7)", "Kc > 0x7fffffff", "uintptr_t>(A)"):
+        assert tn.count(check) <= 1, check
+    assert tn.count("kTnStages * (kTnBK") == 1  # the LDS formula: tn_lds_bytes() only
+
+
 def test_host_tables_match_oracle():
     """Host-built tables (window, mel banks) of the product vs the oracle's restatement."""
     import numpy as np

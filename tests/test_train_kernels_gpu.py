@@ -154,6 +154,31 @@ def test_transpose_batch_and_batched_split_sums(K):
     assert torch.equal(tall_out, tall_again)  # fixed summation order: bit-identical from run to run
 
 
+def test_partial_group_bad_ninth_item_leaves_first_group_issued(K):
+    """ma_gemm_tn_partial_group_bf16 checks and launches per group of eight: a ninth item whose buffer is one byte short is answered
+    with MA_ERR_WORKSPACE after the first eight products have been issued (their partials are those of the single-product entry
+    point, bit for bit) and before anything of the second group is."""
+    from mindaudio_amd import _lib
+
+    lib = _lib.load()
+    g = torch.Generator().manual_seed(9)
+    kc, mo, no = 130, 64, 72
+    nbytes = int(lib.ma_gemm_tn_workspace_bytes(mo, no, kc))
+    ops = [(bf(torch.randn(kc, mo, generator=g)).cuda(), bf(torch.randn(kc, no, generator=g)).cuda()) for _ in range(9)]
+    parts = [torch.full((nbytes,), 0x5A, dtype=torch.uint8, device="cuda") for _ in range(9)]
+    items = (_lib.TnItem * 9)()
+    for it, (a, b), part in zip(items, ops, parts):
+        it.A, it.B, it.partial, it.lda, it.ldb = a.data_ptr(), b.data_ptr(), part.data_ptr(), a.stride(0), b.stride(0)
+        it.Mo, it.No, it.Kc, it.Mo_store, it.partial_bytes, it.with_colsum = mo, no, kc, mo, nbytes, 1
+    items[8].partial_bytes = nbytes - 1
+    assert lib.ma_gemm_tn_partial_group_bf16(items, 9, torch.cuda.current_stream().cuda_stream) == _lib.MA_ERR_WORKSPACE
+    for (a, b), part in zip(ops[:8], parts[:8]):
+        alone = torch.full((nbytes,), 0x5A, dtype=torch.uint8, device="cuda")
+        K.gemm_tn_partial(a, b, alone, with_colsum=True)
+        assert torch.equal(part, alone)
+    assert bool((parts[8] == 0x5A).all())
+
+
 def test_gemm_splitk(K):
     g = torch.Generator().manual_seed(1)
     for m, n, k in ((256, 256, 10240), (2048, 256, 4096), (100, 300, 640), (256, 2304, 64 * 300)):
