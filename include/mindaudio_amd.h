@@ -1782,6 +1782,74 @@ int ma_wavegrad_reverse(const ma_wavegrad_plan_t* plan, float* audio, const floa
                         const float* c2, const float* sigma, const float* noise, int32_t S, int32_t first_step, int32_t n_steps,
                         void* workspace, int64_t workspace_bytes, ma_stream_t stream);
 
+/* ---- WaveGrad training (examples/wavegrad/train.py: L1 loss, MyTrainOneStepCell's unscale / clip_by_global_norm / nn.Adam) ---------------
+ * The backward pass walks the forward's op list in reverse around existing products: the gradient of a CONV / DOWN output becomes an
+ * operand image through ma_wavegrad_pack_bf16 (slope 1, mul = the convolution's alpha); dX is ma_conv1d_taps_bf16 / ma_gemm_bf16 on the
+ * transposed weight copies of ma_wavegrad_weights_bf16, dW ma_gemm_tn_bf16_f32 per tap.  The entries below are what sits between them.
+ * The rules of the WaveGrad section hold: every argument check comes before any HIP call, 16-byte aligned bases, nothing allocates or
+ * synchronises, no atomics - the same bits from run to run.  Sums over per-workgroup float32 partials are left to
+ * ma_reduce_splits_batch_f32 (the caller's item table).
+ *
+ * ma_wavegrad_l1_last_bwd_f32: the L1 loss and the backward of last_conv (Conv1d(C -> 1, `taps` odd <= 7, pad same)) in one launch, plus
+ *   a one-workgroup launch that joins the loss.  pred, noise (B, T); x (B, T, C) the convolution's input; w (taps, C) float32.
+ *     loss[0] = mean |pred - noise| as float64: |float32 difference| summed in float64, one partial per workgroup (loss_part, >=
+ *       ma_wavegrad_last_bwd_parts(B, T) doubles), joined in a fixed order;
+ *     g[b, t] = sign(pred - noise) * loss_scale / (B T), sign(0) = 0                                           (B, T) float32
+ *     dx[b, t, c] = sum_j g[b, t - (j - taps/2)] w[j, c], taps outside the utterance are zero                    (B, T, C) float32, stored
+ *     wpart[p * pstride + j * C + c] = workgroup p's sum of g[b, t] x[b, t + j - taps/2, c];  wpart[p * pstride + taps * C] = its sum of g
+ *   p < ma_wavegrad_last_bwd_parts(B, T); pstride >= taps * C + 1, a multiple of 4.  C % 4 == 0, C <= 1024, B <= 65535.
+ * ma_wavegrad_pack_bwd_f32: the backward of ma_wavegrad_pack_bf16 / ma_wavegrad_pack_f32.  dop = the gradient with respect to the operand
+ *   values, float32 (B * T_in * f rows of >= C floats, row stride ld_dop; NULL: the op had no operand output); x, film, slope, mul, f,
+ *   res_mul as the forward got them; dres = the gradient of the res side output (B, T_in * f, C) or NULL.  Per output row and channel,
+ *   with v = x[b, t / f, c] and pre = the forward's value in front of the LeakyReLU recomputed in the forward's fma order:
+ *     g = dop * mul * (pre >= 0 ? 1 : slope)
+ *     film:  dshift = g / sqrt 2,  dscale = g * v / sqrt 2  -> dfilm (row stride ld_dfilm, shift | scale as the film matrix; stored, or
+ *            added to what is there when acc_film != 0);  g = g * scale / sqrt 2
+ *     g += dres * res_mul
+ *   dx[b, t / f, c] = (acc_dx ? dx : 0) + the sum over the f repeated rows in row order.  The encoding has no gradient.  dx or dfilm may
+ *   be NULL.  C % 4 == 0, strides % 4 == 0.
+ * ma_wavegrad_init_conv_bwd_f32: the parameter gradients of ma_wavegrad_init_conv_f32 as per-workgroup partials: part[p * (taps + 1) * C0
+ *   + j * C0 + c] = sum of dout[b, t, c] audio[b, t + j - taps/2], and behind the taps [.. + taps * C0 + c] = sum of dout[b, t, c];
+ *   p < ma_wavegrad_init_bwd_parts(B, T).  C0 % 4 == 0, C0 <= 1024.
+ * ma_wavegrad_sumsq_f64: part[p] = float64 partial of sum g^2, p < ma_wavegrad_sumsq_parts(n) (<= 1024).  n % 4 == 0.
+ * ma_wavegrad_clip_adam_f32: one launch over one flat parameter buffer.  Every workgroup joins the partials in the same order;
+ *   norm = sqrt(sum) / loss_scale (the norm after the reference's unscaling; stored as float32 in norm[0]); a non-finite norm sets
+ *   overflow[0] = 1 and leaves param, m and v untouched; else overflow[0] = 0 and, with factor = clip / max(norm, clip)
+ *   (ops.clip_by_global_norm), ma_adam_f32's update on g = (grad / loss_scale) * factor.  n % 4 == 0.
+ * ma_wavegrad_weights_bf16: the bf16 operand copies of every convolution from the float32 masters (N, taps, C) in ONE launch; items /
+ *   block_item are DEVICE arrays, workgroup b handles elements [256 (b - first_block), + 256) of item block_item[b]'s Npad * taps * Cpad.
+ *     fwd (rows_fwd, taps, Cpad): the forward operand, zero columns C .. Cpad - 1 and zero rows N .. rows_fwd - 1 (rows_fwd <= Npad);
+ *     rev, mode 0: (C, taps, Npad) with rev[c, taps - 1 - j, n] = w[n, j, c] - the weights of the input-gradient convolution;
+ *          mode 1: (taps * Cpad, Npad) with rev[j * Cpad + c, n] = w[n, j, c] - the transposed matrix of a kernel = stride convolution.
+ *   Either may be NULL.  Round to nearest even, as ma_cast_f32_bf16.
+ * ma_wavegrad_pack_f32: ma_wavegrad_pack_bf16 with a float32 image (B, T_in * f + 2 * halo, C) and no padded columns: the operand
+ *   producer of the float32 validation mode (products through ma_gemm_x32).  C % 4 == 0. */
+typedef struct ma_wavegrad_weight_item {
+  const float* src;
+  void* fwd;
+  void* rev;
+  int32_t N, taps, C, Cpad, Npad, rows_fwd, mode, first_block;
+} ma_wavegrad_weight_item_t;
+int32_t ma_wavegrad_last_bwd_parts(int64_t B, int64_t T);
+int32_t ma_wavegrad_init_bwd_parts(int64_t B, int64_t T);
+int32_t ma_wavegrad_sumsq_parts(int64_t n);
+int ma_wavegrad_l1_last_bwd_f32(const float* pred, const float* noise, const float* x, int64_t B, int64_t T, int32_t C, const float* w,
+                                int32_t taps, float loss_scale, float* g, float* dx, float* wpart, int64_t pstride, double* loss_part,
+                                double* loss, ma_stream_t stream);
+int ma_wavegrad_pack_bwd_f32(const float* dop, int64_t ld_dop, const float* x, int64_t B, int64_t T_in, int32_t f, int32_t C,
+                             const float* film, int64_t ld_film, float slope, float mul, const float* dres, float res_mul, float* dx,
+                             int32_t acc_dx, float* dfilm, int64_t ld_dfilm, int32_t acc_film, ma_stream_t stream);
+int ma_wavegrad_init_conv_bwd_f32(const float* dout, const float* audio, int64_t B, int64_t T, int32_t taps, int32_t C0, float* part,
+                                  ma_stream_t stream);
+int ma_wavegrad_sumsq_f64(const float* g, int64_t n, double* part, ma_stream_t stream);
+int ma_wavegrad_clip_adam_f32(float* param, const float* grad, float* m, float* v, int64_t n, const double* part, int32_t n_parts,
+                              float loss_scale, float clip, float lr_t, float beta1, float beta2, float eps, int32_t* overflow,
+                              float* norm, ma_stream_t stream);
+int ma_wavegrad_weights_bf16(const ma_wavegrad_weight_item_t* items, const int32_t* block_item, int32_t n_blocks, ma_stream_t stream);
+int ma_wavegrad_pack_f32(const float* x, int64_t B, int64_t T_in, int32_t f, int32_t C, int32_t halo, const float* film, int64_t ld_film,
+                         const float* enc, int64_t ld_enc, float slope, float mul, float* out, float* res, float res_mul,
+                         ma_stream_t stream);
+
 /* ---- FastSpeech2 inference (mindaudio/models/fastspeech2/, mindaudio/models/transformer/) -------------------------------------------------
  * The residual stream is time-major, channel-last float32 (B, T, C), compact.  bf16 exists only as an MFMA operand image (B, T + 2 * halo,
  * C) with zero halo rows around every utterance, the layout of ma_conv1d_taps_bf16.  No atomics, no cross-workgroup waiting: the same

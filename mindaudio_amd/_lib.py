@@ -119,6 +119,13 @@ class WaveGradPlan(ctypes.Structure):
                 ("ops", ctypes.POINTER(WaveGradOp))]
 
 
+class WaveGradWeightItem(ctypes.Structure):
+    """struct ma_wavegrad_weight_item (include/mindaudio_amd.h)."""
+
+    _fields_ = [("src", ctypes.c_void_p), ("fwd", ctypes.c_void_p), ("rev", ctypes.c_void_p), ("N", i32), ("taps", i32), ("C", i32),
+                ("Cpad", i32), ("Npad", i32), ("rows_fwd", i32), ("mode", i32), ("first_block", i32)]
+
+
 class Fs2Layer(ctypes.Structure):
     """struct ma_fs2_layer (include/mindaudio_amd.h)."""
 
@@ -474,6 +481,17 @@ PROTOTYPES = {
     "ma_wavegrad_forward": (ctypes.c_int, [ctypes.POINTER(WaveGradPlan), vp, vp, vp, i64, vp, vp, i64, vp]),
     "ma_wavegrad_reverse": (ctypes.c_int, [ctypes.POINTER(WaveGradPlan), vp, vp, vp, ctypes.POINTER(f32), ctypes.POINTER(f32),
                                            ctypes.POINTER(f32), vp, i32, i32, i32, vp, i64, vp]),
+    # ---- WaveGrad training ----
+    "ma_wavegrad_last_bwd_parts": (i32, [i64, i64]),
+    "ma_wavegrad_init_bwd_parts": (i32, [i64, i64]),
+    "ma_wavegrad_sumsq_parts": (i32, [i64]),
+    "ma_wavegrad_l1_last_bwd_f32": (ctypes.c_int, [vp, vp, vp, i64, i64, i32, vp, i32, f32, vp, vp, vp, i64, vp, vp, vp]),
+    "ma_wavegrad_pack_bwd_f32": (ctypes.c_int, [vp, i64, vp, i64, i64, i32, i32, vp, i64, f32, f32, vp, f32, vp, i32, vp, i64, i32, vp]),
+    "ma_wavegrad_init_conv_bwd_f32": (ctypes.c_int, [vp, vp, i64, i64, i32, i32, vp, vp]),
+    "ma_wavegrad_sumsq_f64": (ctypes.c_int, [vp, i64, vp, vp]),
+    "ma_wavegrad_clip_adam_f32": (ctypes.c_int, [vp, vp, vp, vp, i64, vp, i32, f32, f32, f32, f32, f32, f32, vp, vp, vp]),
+    "ma_wavegrad_weights_bf16": (ctypes.c_int, [vp, vp, i32, vp]),
+    "ma_wavegrad_pack_f32": (ctypes.c_int, [vp, i64, i64, i32, i32, i32, vp, i64, vp, i64, f32, f32, vp, vp, f32, vp]),
     # ---- FastSpeech2 inference ----
     "ma_mha_d128_bf16": (ctypes.c_int, [vp, i64, vp, i64, vp, i64, vp, i64, i64, i64, i32, i32, f32, vp, i64, i64, vp]),
     "ma_groupnorm_parts": (i32, [i64]),

@@ -1,5 +1,5 @@
 """WaveGrad on MI355X - mirror of mindaudio.models.wavegrad.WaveGrad (wavegrad_v190.py:174-241), forward only (the vocoder's
-reverse loop is mindaudio_amd.wavegrad.reverse; training is not built).
+reverse loop is mindaudio_amd.wavegrad.reverse; training is models.wavegrad_train.WaveGradTrainer, on this forward).
 
 Activations are time-major, channel-last float32.  Every convolution with more than one input channel is an MFMA product on bf16
 operands: ma_conv1d_taps_bf16 for the plain / dilated "same" convolutions, ma_gemm_bf16 for the kernel = stride = factor downscales.

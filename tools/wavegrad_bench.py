@@ -98,8 +98,8 @@ def ours(a, torch):
     return out
 
 
-def eager(a, torch):
-    """The reference's forward (wavegrad_v190.py) on nn.Conv1d layers, float32 eager."""
+def eager_net(torch):
+    """The reference's forward (wavegrad_v190.py) on nn.Conv1d layers: a throw-away float32 module (tools/wavegrad_train_bench.py trains it)."""
     import torch.nn as nn
     import torch.nn.functional as F
 
@@ -158,7 +158,11 @@ def eager(a, torch):
                 x = (x + b3) / r2
             return self.last(x)[:, 0]
 
-    net = Net().cuda().eval()
+    return Net()
+
+
+def eager(a, torch):
+    net = eager_net(torch).cuda().eval()
     audio, spec, level = torch.randn((1, 300 * a.frames), device="cuda"), torch.rand((1, 128, a.frames), device="cuda"), torch.tensor([0.5], device="cuda")
     try:
         with torch.no_grad():
