@@ -359,6 +359,53 @@ int ma_hyp_score_f32(const float* logits, int64_t ld, int32_t V, int64_t n_utt, 
                      double ctc_weight, double* workspace, double* hyp_score, int32_t* best_index, double* best_score,
                      ma_stream_t stream);
 
+/* ---- the autoregressive `attention` decode mode (utils/recognize.py:78-251, decoder_factory.py:59-192, 278-413) --------------
+ * One decode step of the decoder's self-attention on a key / value cache, with the beam reorder and the append in the launch:
+ *   qkv (R, 3 d) bf16 with row stride ldqkv: row r's new query | key | value, R = batch * beam, d = heads * 64;
+ *   k_in, v_in (R, Lmax, d) bf16 contiguous: the cache as the previous step left it, t cached positions, 0 <= t < Lmax;
+ *   parent (R) int32 or NULL (the identity): the cache row that row r continues (values outside [0, R) are clamped into it).
+ *   k_out[r, 0:t] = k_in[parent[r], 0:t] bit for bit, k_out[r, t] = the new key; v_out likewise; positions above t of the out
+ *   cache are not written.  ctx (R, d) bf16 with row stride ldc: softmax(scale * q . k_j, j <= t) v with no mask (every cached key
+ *   is valid).  In and out are different buffers (the caller alternates two by the step's parity): two children may share a parent,
+ *   the launch never reads what it writes, the stream order is the only synchronisation, and there are no atomics - two runs
+ *   give the same bits.
+ * Rounding points, those of ma_mha_small_fwd_bf16: q, k, v are bf16 and their products exact in float32; scores (float32 fma
+ * sums, then * scale), the row maximum, exp and the sum are float32 (__expf: a key more than 104 below the row maximum weighs
+ * exactly 0); the normalised probability is rounded to bf16 (the operand of the P V product); the P V sum is float32; ctx is
+ * rounded to bf16 once.  One wave per (row, head); the launch is bound by latency, not by bandwidth or the matrix pipe.
+ * MA_ERR_UNSUPPORTED: d_k != 64, d != heads * 64, Lmax > 2048, a row stride that is no multiple of 8.  MA_ERR_INVALID_ARG:
+ * t >= Lmax, R == 0, a NULL or not 16-byte aligned buffer, an in buffer that overlaps an out buffer. */
+int ma_decoder_self_attn_step_bf16(const void* qkv, int64_t ldqkv, const void* k_in, const void* v_in, const int32_t* parent,
+                                   int64_t R, int32_t Lmax, int32_t t, int32_t heads, int32_t d_k, int32_t d, float scale, void* ctx,
+                                   int64_t ldc, void* k_out, void* v_out, ma_stream_t stream);
+
+/* Steps 2.2-2.6 of the attention beam search (PredictNet.construct, decoder_factory.py:387-413, and recognize.py:236-242) for a
+ * batch: one workgroup per utterance, one launch, no atomics.  N = beam, rows u * N .. u * N + N - 1 belong to utterance u.
+ *   topk_logp / topk_index (batch * N, N): ma_ctc_topk_f32 of the step's logits with k = N (1 <= N <= 16, N <= V);
+ *   scores_in (batch * N) float32, end_in (batch * N) int32, tokens_in (batch * N, W) int32 with sos in column 0,
+ *   length (batch) int32: tokens generated so far, done (batch) int32; max_new <= W - 1 (the reference's maxlen - 1).
+ * Per utterance that is not done, in float32: candidate (r, j) = scores[r] + m, m = logp[r][j] for an unfinished row; for a
+ * finished row m is exactly +0.0 for j == 0 and logp[r][j] + (-10000.0f) for j > 0, and its token is eos (mask_finished_scores /
+ * mask_finished_preds; -10000 is the reference's constant.  The reference multiplies the finished row's first logp by 0, which is
+ * NaN for an infinite logp; here that branch ADDS 0).  The N best of the N * N candidates in descending order, equal values lower
+ * flat index r * N + j first (the reference's topk_fun is a stable sort), -inf last (NaN ranks as -inf).  For output slot s:
+ * scores_out[s] = the candidate's value, parent[s] = its GLOBAL row index, pred[s] = its token, tokens_out[s] = tokens_in[parent[s]]
+ * with column length + 1 set to the token, end_out[s] = (token == eos).  Then length += 1 and done = 1 when every end_out of the
+ * utterance is set or length >= max_new.
+ * An utterance that is done is frozen: scores, flags and tokens are copied through, parent is the identity, pred is eos, length
+ * stays - so every utterance of a batch gets the result of a one-utterance call.  (The reference goes on appending eos to a finished
+ * utterance until the whole batch has finished; that is deliberately not kept.)  The in and out arrays must not overlap; length
+ * and done are updated in place; the host reads `done`.  beam > 16: MA_ERR_UNSUPPORTED. */
+int ma_attn_beam_step_f32(const float* topk_logp, const int32_t* topk_index, const float* scores_in, const int32_t* end_in,
+                          const int32_t* tokens_in, int64_t batch, int32_t beam, int32_t W, int32_t eos, int32_t max_new,
+                          int32_t* length, int32_t* done, float* scores_out, int32_t* end_out, int32_t* tokens_out, int32_t* parent,
+                          int32_t* pred, ma_stream_t stream);
+
+/* topk_fun(scores, 1) of the search's end (recognize.py:244-251): per utterance the first slot with the highest score;
+ * best_hyp (batch, W - 1) int32 = that slot's token row without column 0, best_len (batch) = length, best_score (batch) float32. */
+int ma_attn_beam_best_f32(const float* scores, const int32_t* tokens, const int32_t* length, int64_t batch, int32_t beam, int32_t W,
+                          int32_t* best_hyp, int32_t* best_len, float* best_score, ma_stream_t stream);
+
 /* float32 -> bf16 (round to nearest even), n % 4 == 0: the `cast` in front of a matmul operand. */
 int ma_cast_f32_bf16(const float* x, void* y, int64_t n, ma_stream_t stream);
 

@@ -220,6 +220,9 @@ PROTOTYPES = {
     "ma_ctc_prefix_beam_search_f32": (ctypes.c_int, [vp, vp, vp, i64, i32, i32, i32, vp, vp, vp, vp, vp]),
     "ma_hyp_score_f32": (ctypes.c_int, [vp, i64, i32, i64, i32, i32, vp, i64, vp, vp, i32, vp, ctypes.c_double, vp, vp, vp, vp,
                                         vp]),
+    "ma_decoder_self_attn_step_bf16": (ctypes.c_int, [vp, i64, vp, vp, vp, i64, i32, i32, i32, i32, i32, f32, vp, i64, vp, vp, vp]),
+    "ma_attn_beam_step_f32": (ctypes.c_int, [vp, vp, vp, vp, vp, i64, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "ma_attn_beam_best_f32": (ctypes.c_int, [vp, vp, vp, i64, i32, i32, vp, vp, vp, vp]),
     "ma_cast_f32_bf16": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, i64, ctypes.c_void_p]),
     "ma_ecapa_pack_input_bf16": (ctypes.c_int, [vp, i64, i64, i32, i32, i32, vp, vp]),
     "ma_add_bf16": (ctypes.c_int, [vp, i64, vp, i64, vp, i64, i64, i64, vp]),

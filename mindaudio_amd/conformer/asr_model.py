@@ -6,7 +6,7 @@ ASRModel.forward takes the 11 columns of the reference batch in the reference or
 import torch
 import torch.nn as nn
 
-from .. import ops
+from .. import _host, ops
 from ..models.conformer import ConformerEncoder
 
 
@@ -279,3 +279,90 @@ def attention_rescoring(model_ctc, model_rescore, xs_pad, xs_masks, xs_lengths, 
     best, best_score = best.cpu().tolist(), best_score.cpu().tolist()
     hyp_h, lens_h = hyp.cpu(), hyp_len.cpu()
     return [hyp_h[u, best[u], :int(lens_h[u, best[u]])].tolist() for u in range(b)], best_score
+
+
+class Attention(nn.Module):
+    """Attention net (models/decoders/decoder_factory.py:59-192), the `full_graph` form of decode_mode `attention`: the beam search
+    on the Transformer decoder with the whole loop on the device.  Where the reference repeats the encoder output beam_size times
+    and re-runs the decoder on the maxlen-padded prefix at every step, `begin` runs the encoder once, computes the source
+    attention's K / V once per utterance (TransformerDecoder.init_cache) and hands out a step callable that advances every beam by
+    one token on the key / value cache (TransformerDecoder.step); `recognize` drives it."""
+
+    def __init__(self, backbone, beam_size, eos, pretrained_model=False):
+        super().__init__()
+        if pretrained_model:
+            raise NotImplementedError("wav2vec front ends are outside the built path")
+        if getattr(backbone, "decoder", None) is None:
+            raise NotImplementedError("the attention decode mode needs the attention decoder (model_conf.ctc_weight < 1.0)")
+        self.backbone, self.beam_size, self.eos = backbone, int(beam_size), int(eos)
+
+    @torch.no_grad()
+    def begin(self, xs_pad, xs_masks, xs_lengths=None):
+        """xs_pad (B, T, feat), xs_masks (B, 1, T) un-subsampled -> (maxlen = the encoder's frame count, step) with
+        step(tokens (B * beam,), t, parent) -> the decoder's scores (B * beam, V) float32 at position t."""
+        sub = xs_masks[:, :, :-2:2][:, :, :-2:2].contiguous()
+        enc, enc_mask = self.backbone.encoder(xs_pad, sub, sub)
+        maxlen = enc.shape[1]
+        decoder = self.backbone.decoder
+        cache = decoder.init_cache(enc, enc_mask, self.beam_size, maxlen)
+        return maxlen, lambda tokens, t, parent=None: decoder.step(cache, tokens, t, parent)
+
+
+def recognize(model, xs_pad, xs_masks, start_token, base_index, scores, end_flag, beam_size, eos, xs_lengths=None, full_graph=True,
+              chunk=8):
+    """utils/recognize.py:78-251 for a batch of B >= 1 -> (best_hyps (B, maxlen - 1) int32 array, best_scores (B,) float32 array).
+    `model` is an Attention (anything with beam_size and begin(xs_pad, xs_masks, xs_lengths) -> (maxlen, step callable) will do: the
+    logits source of a step is a callable).  start_token (1,) = [sos], scores (beam,) = [0, -inf, ...] and end_flag (beam,) are the
+    reference's initial state, tiled over the batch here; base_index is accepted for the signature (parents are global row indices).
+
+    The encoder runs once and maxlen is its frame count.  Every step is: the callable's logits -> ma_ctc_topk_f32 (k = beam) ->
+    ma_attn_beam_step_f32, whose `pred` and `parent` feed the next step; nothing is read back inside a chunk of `chunk` steps.  The
+    per-utterance `done` flags are read between chunks and the loop stops when all are set (or after maxlen - 1 steps).  Steps issued
+    after an utterance is done are harmless: it is frozen.
+
+    Kept from the reference: -10000 (not -inf) on the extra branches of a finished beam, the trailing eos tokens of beams that
+    finished before their utterance did, sos == eos, no length normalisation.  Not kept: the NaN of `-inf * 0` (the finished beam's
+    first branch adds exactly 0), batch-wide termination (the reference goes on appending eos to a finished utterance until every
+    utterance of the batch has finished; here a finished utterance is frozen, so each gets the result of a one-utterance call), and
+    the host-side width T // 4 - 1 of the reference's full_graph form, which differs from the encoder's frame count only in
+    trailing zeros.  full_graph=False (the host-stepped PredictNet form) is not built."""
+    import numpy as np
+
+    if not full_graph:
+        raise NotImplementedError("the host-stepped form of the attention decode mode (full_graph: false) is not built; "
+                                  "full_graph: true selects the device-resident search")
+    beam = int(beam_size)
+    if getattr(model, "beam_size", beam) != beam:
+        raise ValueError("the search net was built for beam %d, not %d" % (model.beam_size, beam))
+    if chunk < 1:
+        raise ValueError("chunk must be at least 1")
+    dev = xs_pad.device
+    b = xs_pad.shape[0]
+    maxlen, step = model.begin(xs_pad, xs_masks, xs_lengths)
+    max_new = maxlen - 1
+    i32 = torch.int32
+    sc = torch.as_tensor(np.asarray(scores, np.float32).reshape(-1)).to(dev)
+    ef = torch.as_tensor(np.asarray(end_flag).reshape(-1) != 0).to(dev)
+    if sc.numel() != beam or ef.numel() != beam:
+        raise ValueError("scores and end_flag hold one entry per beam")
+    state = (sc.repeat(b).contiguous(), ef.to(i32).repeat(b).contiguous(), torch.zeros((b * beam, maxlen), dtype=i32, device=dev))
+    state[2][:, 0] = int(np.asarray(start_token).reshape(-1)[0])
+    if max_new < 1:
+        return np.zeros((b, 0), np.int32), state[0].view(b, beam).max(1).values.cpu().numpy()
+    length = torch.zeros(b, dtype=i32, device=dev)
+    done = torch.zeros(b, dtype=i32, device=dev)
+    tokens, parent, spare = state[2][:, 0].contiguous(), None, None
+    t = 0
+    with _host.pinned_stream():  # (a step is ~70 launches: torch's current stream is resolved once, not per launch)
+        while t < max_new:
+            for _ in range(min(int(chunk), max_new - t)):
+                logits = step(tokens, t, parent)
+                logp, index = ops.ctc_topk(logits, logits.shape[1], beam)
+                out = ops.attn_beam_step(logp, index, state[0], state[1], state[2], length, done, eos, max_new, out=spare)
+                spare = state + (parent, tokens) if parent is not None else None  # (the buffers of two steps ago are free again)
+                state, parent, tokens = out[:3], out[3], out[4]
+                t += 1
+            if bool(done.all()):  # the one read-back of a chunk
+                break
+    hyp, _, best = ops.attn_beam_best(state[0], state[2], length, beam)
+    return hyp.cpu().numpy(), best.cpu().numpy()

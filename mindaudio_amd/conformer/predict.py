@@ -1,7 +1,8 @@
 """`python -m mindaudio_amd.conformer.predict --config_path conformer.yaml` — the counterpart of examples/conformer/predict.py for
 decode_mode `ctc_greedy_search` (greedy CTC search + CER is the one external pin on the whole model, readme.md:126),
-`ctc_prefix_beam_search` (the best prefix of the CTC prefix beam search) and `attention_rescoring` (the prefix search's hypotheses
-rescored by the attention decoder, the mode of the reference's best CER).
+`ctc_prefix_beam_search` (the best prefix of the CTC prefix beam search), `attention_rescoring` (the prefix search's hypotheses
+rescored by the attention decoder, the mode of the reference's best CER) and `attention` with `full_graph: true` (the autoregressive
+beam search on the attention decoder, the shipped yaml's form: a KV-cached decoder step and a device-resident beam step).
 
 Same yaml keys (test_data, dict, exp_name, decode_ckpt, decode_mode, dataset_conf, collate_conf), same per-utterance flow
 (create_asr_predict_dataset, dataset.py:750-908: utterances outside the frame / token limits are dropped, one utterance per step,
@@ -9,9 +10,10 @@ Kaldi fbank of the waveform x 2^15, zero-padded to its frame bucket, mask of the
 (predict.py:146-154: `w += 2`, stop at eos, ids past the dictionary skipped) and the same outputs: `<exp_name>/test_<mode>/result.txt`
 with "<uttid> <text>" lines, one "cer" log line per utterance, "cer_average" at the end.  The two beam modes take the yaml's top-level
 `beam_size` (default 10) and, for the rescoring, the decode section's top-level `ctc_weight` (default 0.0; not model_conf.ctc_weight);
-both searches run on the GPU (ma_ctc_topk_f32, ma_ctc_prefix_beam_search_f32, ma_hyp_score_f32).  `attention_rescoring` needs the
-attention decoder: a pure-CTC model (model_conf.ctc_weight 1.0) raises NotImplementedError, and so does the autoregressive
-`attention` mode, which is not built."""
+both searches run on the GPU (ma_ctc_topk_f32, ma_ctc_prefix_beam_search_f32, ma_hyp_score_f32).  `attention` takes `beam_size` too and
+writes `<exp_name>/test_attention/result.txt`.  `attention_rescoring` and `attention` need the attention decoder: a pure-CTC model
+(model_conf.ctc_weight 1.0) raises NotImplementedError.  `attention` with `full_graph` absent or false - the reference's host-stepped
+PredictNet form - raises NotImplementedError as well: it is not built, `full_graph: true` (or --full_graph) selects the built one."""
 import argparse
 import os
 
@@ -72,19 +74,22 @@ def predict(config, device=None, log=print, model=None):
 
     from ..data.io import read
     from ..metric import wer
-    from .asr_model import (AttentionRescoring, CTCGreedySearch, CTCPrefixBeamSearch, attention_rescoring, ctc_greedy_search,
-                            ctc_prefix_beam_search)
+    from .asr_model import (Attention, AttentionRescoring, CTCGreedySearch, CTCPrefixBeamSearch, attention_rescoring,
+                            ctc_greedy_search, ctc_prefix_beam_search, recognize)
     from .dataset import compute_fbank_feats_batch
 
     mode = config.get("decode_mode", "ctc_greedy_search")
-    if mode not in ("ctc_greedy_search", "ctc_prefix_beam_search", "attention_rescoring"):
-        raise NotImplementedError("decode_mode %r: ctc_greedy_search, ctc_prefix_beam_search and attention_rescoring are built (the "
-                                  "autoregressive attention search is not)" % mode)
-    if mode == "attention_rescoring":
+    if mode == "attention" and not config.get("full_graph", False):
+        raise NotImplementedError("decode_mode 'attention' without full_graph: the host-stepped form of the attention search is not "
+                                  "built; full_graph: true selects the built, device-resident one")
+    if mode not in ("ctc_greedy_search", "ctc_prefix_beam_search", "attention_rescoring", "attention"):
+        raise NotImplementedError("decode_mode %r: ctc_greedy_search, ctc_prefix_beam_search, attention_rescoring and attention "
+                                  "(full_graph: true) are built" % mode)
+    if mode in ("attention_rescoring", "attention"):
         has_decoder = getattr(model, "decoder", None) is not None if model is not None else \
             float((config.get("model_conf") or {}).get("ctc_weight", 0.3)) != 1.0
         if not has_decoder:
-            raise NotImplementedError("attention_rescoring needs the attention decoder; this model is pure CTC (ctc_weight 1.0)")
+            raise NotImplementedError("%s needs the attention decoder; this model is pure CTC (ctc_weight 1.0)" % mode)
     beam_size = int(config.get("beam_size", 10))
     ctc_weight = float(config.get("ctc_weight", 0.0))
     if device is None:
@@ -104,6 +109,8 @@ def predict(config, device=None, log=print, model=None):
     model.eval()
     if mode == "ctc_greedy_search":
         net = CTCGreedySearch(model)
+    elif mode == "attention":
+        net = Attention(model, beam_size, eos)
     else:
         net = CTCPrefixBeamSearch(model, beam_size)
         rescore = AttentionRescoring(model, beam_size) if mode == "attention_rescoring" else None
@@ -128,6 +135,13 @@ def predict(config, device=None, log=print, model=None):
             elif mode == "ctc_prefix_beam_search":
                 beams, _, _ = ctc_prefix_beam_search(net, xs, masks, beam_size, None)
                 hyps = [list(beams[0][0][0])]
+            elif mode == "attention":  # predict.py:90-111: the search's initial state, one utterance per step
+                start_token = np.array([sos], np.int32)
+                scores = np.array([0.0] + [-float("inf")] * (beam_size - 1), np.float32)
+                end_flag = np.array([0.0] * beam_size, np.float32)
+                base_index = np.arange(xs.shape[0], dtype=np.int32).reshape(-1, 1)
+                hyps, _ = recognize(net, xs, masks, start_token, base_index, scores, end_flag, beam_size, eos, None, True)
+                hyps = [hyp.tolist() for hyp in hyps]
             else:
                 hyps, _ = attention_rescoring(net, rescore, xs, masks, None, sos, eos, beam_size, ctc_weight)
             content = ids_to_text(hyps[0], eos, char_dict)
@@ -159,6 +173,7 @@ def main(argv=None):
     ap.add_argument("--decode_mode")
     ap.add_argument("--beam_size", type=int)
     ap.add_argument("--ctc_weight", type=float)
+    ap.add_argument("--full_graph", action="store_const", const=True, help="decode_mode attention: the device-resident search")
     a = ap.parse_args(argv)
     over = {k: v for k, v in vars(a).items() if k != "config_path" and v is not None}
     predict(load_config(a.config_path, over))

@@ -107,6 +107,78 @@ class TransformerDecoder(nn.Module):
             raise ValueError("ys_in_pad holds %d hypotheses, not %d x %d" % (ys_in_pad.shape[0], memory.shape[0], group))
         return self._decode(memory, memory_mask, ys_in_pad, ys_masks, int(group))
 
+    @torch.no_grad()
+    def init_cache(self, memory, memory_mask, group, max_len):
+        """The state of the step-by-step decode (the `attention` decode mode) of B utterances with `group` beams each: memory
+        (B, T', d) float32, memory_mask (B, 1, T') -> a dict with, per layer, the source attention's K | V rows (B * T', 2 d) bf16 -
+        computed ONCE per utterance here, not repeated per beam and not recomputed per step - and the two parities of the
+        self-attention's key / value cache (B * group, max_len, d) bf16 (step t reads parity t % 2 and writes the other one)."""
+        if self.training:
+            raise NotImplementedError("the training-mode decoder (dropout) runs inside mindaudio_amd.train.engine")
+        if self._prepared is None:
+            self.prepare()
+        bm, t2, d = memory.shape
+        if max_len < 1 or max_len > self.pe.shape[0]:
+            raise ValueError("max_len %d outside the positional table (%d rows)" % (max_len, self.pe.shape[0]))
+        f32, bf = torch.float32, torch.bfloat16
+        mem_bf = ops.cast_bf16(memory.reshape(bm * t2, d).to(f32).contiguous())
+        rows = bm * int(group)
+        layers = []
+        for W in self._prepared["layers"]:
+            layers.append({"kv": ops.gemm(mem_bf, W["ca_kv_w"], bias=W["ca_kv_b"]),
+                           "k": [torch.empty((rows, max_len, d), dtype=bf, device=memory.device) for _ in range(2)],
+                           "v": [torch.empty((rows, max_len, d), dtype=bf, device=memory.device) for _ in range(2)]})
+        vp = self._prepared["out_b"].numel()
+        return {"layers": layers, "emask": memory_mask.reshape(bm, t2).to(f32).contiguous(), "batch": bm, "group": int(group),
+                "rows": rows, "t2": t2, "max_len": int(max_len), "pe": self.pe[:max_len].to(f32).contiguous(),
+                "logits": torch.empty((rows, vp), dtype=f32, device=memory.device)}
+
+    @torch.no_grad()
+    def step(self, cache, tokens, t, parent=None):
+        """One token of every row: tokens (R,) the rows' last tokens (position t of their prefixes), t cached positions, parent (R,)
+        int32 or None: the row of the previous step that row r continues (the beam reorder, done by the self-attention kernel on the
+        cache) -> the scores before the softmax of position t, (R, V) float32 (a view of the cache's 64-padded row buffer, overwritten
+        by the next step).  The same arithmetic as row t of `forward` on the prefix: embedding + positional row t, per layer the
+        LayerNorms and the GEMMs with their bias / residual / ReLU epilogues, ma_decoder_self_attn_step_bf16 on the cache and the
+        source attention through ma_mha_small_fwd_grouped_bf16 with Lq = 1, then after_norm and the output layer."""
+        from ..train import kernels as K
+
+        P = self._prepared
+        f32 = torch.float32
+        d, rows, group = self.d, cache["rows"], cache["group"]
+        dk = d // self.heads
+        scale, eps = 1.0 / dk, 1e-12
+        if not 0 <= t < cache["max_len"]:
+            raise ValueError("step %d outside the cache (%d positions)" % (t, cache["max_len"]))
+        toks = tokens.to(torch.int32).contiguous().reshape(-1)
+        if toks.numel() != rows:
+            raise ValueError("%d tokens for %d rows" % (toks.numel(), rows))
+        x = K.embed_posenc(toks, P["embed"], cache["pe"][t:t + 1], 1, self.xscale, 0.0, 0, 0)        # (R, d) float32
+        for l, W, C in zip(self.decoders, P["layers"], cache["layers"]):
+            a = ops.layernorm(x, l.norm1.gamma, l.norm1.beta, eps=eps)
+            qkv = ops.gemm(a, W["sa_qkv_w"], bias=W["sa_qkv_b"])
+            ctx = ops.decoder_self_attn_step(qkv, C["k"][t & 1], C["v"][t & 1], t, C["k"][(t + 1) & 1], C["v"][(t + 1) & 1],
+                                             self.heads, scale, parent=parent)
+            ops.gemm(ctx, W["sa_o_w"], bias=W["sa_o_b"], residual=x, out_dtype=f32, out=x)
+            a = ops.layernorm(x, l.norm2.gamma, l.norm2.beta, eps=eps)
+            q = ops.gemm(a, W["ca_q_w"], bias=W["ca_q_b"])
+            kv = C["kv"]
+            ctx, _ = K.mha_small_fwd_grouped(q, kv[:, :d], kv[:, d:], cache["emask"], 1, rows, 1, cache["t2"], scale, group,
+                                             self.heads, dk)
+            ops.gemm(ctx, W["ca_o_w"], bias=W["ca_o_b"], residual=x, out_dtype=f32, out=x)
+            a = ops.layernorm(x, l.norm3.gamma, l.norm3.beta, eps=eps)
+            h = ops.gemm(a, W["ff_w1"], bias=W["ff_b1"], act=_lib.ACT_RELU)
+            ops.gemm(h, W["ff_w2"], bias=W["ff_b2"], residual=x, out_dtype=f32, out=x)
+        y = ops.layernorm(x, self.after_norm.gamma, self.after_norm.beta, eps=eps)
+        logits = cache["logits"]
+        ops.gemm(y, P["out_w"], bias=P["out_b"], out_dtype=f32, out=logits[:, :self.vocab_size])
+        return logits[:, :self.vocab_size]
+
+    @property
+    def launches_per_step(self):
+        """Kernel launches of one `step`: the embedding, 11 per decoder block, after_norm and the output layer."""
+        return 3 + 11 * len(self.decoders)
+
     def _decode(self, memory, memory_mask, ys_in_pad, ys_masks, group):
         from ..train import kernels as K
 

@@ -551,6 +551,92 @@ def hyp_score(logits, V, n_utt, group, L1, tokens, lens, eos, ctc_score, ctc_wei
     return scores, best, best_score
 
 
+# ---- the autoregressive attention decode mode (csrc/attn_decode.hip) -------------------------------------------------------------
+def decoder_self_attn_step(qkv, k_in, v_in, t, k_out, v_out, heads, scale, parent=None, ctx=None):
+    """One decode step of the self-attention on a key / value cache: qkv (R, 3 d) bf16 (row r's new query | key | value), k_in / v_in
+    (R, Lmax, d) bf16 with t cached positions, parent (R,) int32 or None (identity) -> ctx (R, d) bf16; k_out / v_out (R, Lmax, d)
+    receive rows 0..t-1 of the parent's cache and the new key / value at row t (rows above t are not written)."""
+    tt = _host.torch()
+    bf = tt.bfloat16
+    if qkv.dtype != bf or qkv.dim() != 2 or qkv.stride(1) != 1 or qkv.shape[1] % 3:
+        raise ValueError("qkv must be a (R, 3 d) bf16 tensor with contiguous rows")
+    R, d = qkv.shape[0], qkv.shape[1] // 3
+    for x, what in ((k_in, "k_in"), (v_in, "v_in"), (k_out, "k_out"), (v_out, "v_out")):
+        if x.dtype != bf or x.dim() != 3 or not x.is_contiguous() or x.shape[0] != R or x.shape[2] != d or x.shape[1] != k_in.shape[1]:
+            raise ValueError("%s must be a contiguous (R, Lmax, d) bf16 tensor" % what)
+    if parent is not None and (parent.dtype != tt.int32 or not parent.is_contiguous() or parent.numel() != R):
+        raise ValueError("parent must be a contiguous (R,) int32 tensor")
+    if ctx is None:
+        ctx = tt.empty((R, d), dtype=bf, device=qkv.device)
+    if ctx.dtype != bf or tuple(ctx.shape) != (R, d) or ctx.stride(1) != 1:
+        raise ValueError("ctx must be a (R, d) bf16 tensor with contiguous rows")
+    rc = _lib.load().ma_decoder_self_attn_step_bf16(_host.ptr(qkv), qkv.stride(0), _host.ptr(k_in), _host.ptr(v_in), _opt(parent), R,
+                                                    k_in.shape[1], int(t), int(heads), d // int(heads) if heads else 0, d,
+                                                    float(scale), _host.ptr(ctx), ctx.stride(0), _host.ptr(k_out), _host.ptr(v_out),
+                                                    _host.current_stream_ptr())
+    _lib.check(rc, "decoder_self_attn_step")
+    return ctx
+
+
+def attn_beam_step(topk_logp, topk_index, scores_in, end_in, tokens_in, length, done, eos, max_new, out=None):
+    """Steps 2.2-2.6 of the attention beam search for a batch (ma_attn_beam_step_f32): topk_logp / topk_index (B*N, N) from ctc_topk
+    with k = N, scores_in (B*N,) float32, end_in (B*N,) int32, tokens_in (B*N, W) int32, length / done (B,) int32 updated in place
+    -> (scores_out, end_out, tokens_out, parent (B*N,) global row indices, pred (B*N,)); `out` may hand in that tuple's buffers."""
+    tt = _host.torch()
+    i32 = tt.int32
+    if topk_logp.dtype != tt.float32 or topk_index.dtype != i32 or topk_logp.dim() != 2 or topk_logp.shape != topk_index.shape or \
+            not topk_logp.is_contiguous() or not topk_index.is_contiguous():
+        raise ValueError("topk_logp / topk_index must be contiguous (B*N, N) float32 / int32 tensors")
+    rows, n = topk_logp.shape
+    if tokens_in.dtype != i32 or tokens_in.dim() != 2 or not tokens_in.is_contiguous() or tokens_in.shape[0] != rows:
+        raise ValueError("tokens_in must be a contiguous (B*N, W) int32 tensor")
+    if n < 1 or rows % n or length.numel() * n != rows or done.numel() * n != rows:
+        raise ValueError("%d rows are not length.numel() = %d utterances of beam %d" % (rows, length.numel(), n))
+    if scores_in.dtype != tt.float32 or scores_in.numel() != rows or end_in.dtype != i32 or end_in.numel() != rows or \
+            length.dtype != i32 or done.dtype != i32:
+        raise ValueError("scores_in (B*N,) float32, end_in (B*N,) int32, length / done (B,) int32")
+    for x in (scores_in, end_in, length, done):
+        if not x.is_contiguous():
+            raise ValueError("the beam state must be contiguous")
+    dev, w = topk_logp.device, tokens_in.shape[1]
+    if out is None:
+        out = (tt.empty((rows,), dtype=tt.float32, device=dev), tt.empty((rows,), dtype=i32, device=dev),
+               tt.empty((rows, w), dtype=i32, device=dev), tt.empty((rows,), dtype=i32, device=dev),
+               tt.empty((rows,), dtype=i32, device=dev))
+    scores_out, end_out, tokens_out, parent, pred = out
+    if tuple(tokens_out.shape) != (rows, w) or tokens_out.dtype != i32 or not tokens_out.is_contiguous() or \
+            scores_out.dtype != tt.float32 or scores_out.numel() != rows or any(x.dtype != i32 or x.numel() != rows
+                                                                                for x in (end_out, parent, pred)):
+        raise ValueError("`out` does not match the beam state")
+    rc = _lib.load().ma_attn_beam_step_f32(_host.ptr(topk_logp), _host.ptr(topk_index), _host.ptr(scores_in), _host.ptr(end_in),
+                                           _host.ptr(tokens_in), rows // n, n, w, int(eos), int(max_new), _host.ptr(length),
+                                           _host.ptr(done), _host.ptr(scores_out), _host.ptr(end_out), _host.ptr(tokens_out),
+                                           _host.ptr(parent), _host.ptr(pred), _host.current_stream_ptr())
+    _lib.check(rc, "attn_beam_step")
+    return out
+
+
+def attn_beam_best(scores, tokens, length, beam):
+    """topk_fun(scores, 1) per utterance: scores (B*N,) float32, tokens (B*N, W) int32, length (B,) int32 -> (best_hyp (B, W - 1)
+    int32: the first best slot's token row without column 0, best_len (B,) int32, best_score (B,) float32)."""
+    tt = _host.torch()
+    if scores.dtype != tt.float32 or tokens.dtype != tt.int32 or length.dtype != tt.int32 or tokens.dim() != 2 or \
+            not (scores.is_contiguous() and tokens.is_contiguous() and length.is_contiguous()):
+        raise ValueError("scores (B*N,) float32, tokens (B*N, W) int32 and length (B,) int32, contiguous")
+    rows, w = tokens.shape
+    b = length.numel()
+    if beam < 1 or rows != b * beam or scores.numel() != rows:
+        raise ValueError("%d rows are not %d utterances of beam %d" % (rows, b, beam))
+    dev = scores.device
+    hyp = tt.empty((b, w - 1), dtype=tt.int32, device=dev)
+    best_len = tt.empty((b,), dtype=tt.int32, device=dev)
+    best_score = tt.empty((b,), dtype=tt.float32, device=dev)
+    rc = _lib.load().ma_attn_beam_best_f32(_host.ptr(scores), _host.ptr(tokens), _host.ptr(length), b, int(beam), w, _host.ptr(hyp),
+                                           _host.ptr(best_len), _host.ptr(best_score), _host.current_stream_ptr())
+    _lib.check(rc, "attn_beam_best")
+    return hyp, best_len, best_score
+
+
 # ---- speaker verification scoring (csrc/verification.hip) ------------------------------------------------------------------------
 def _check_emb(x, what):
     t = _host.torch()

@@ -7,7 +7,13 @@ baseline: the reference's prefix search restated in Python (utils/recognize.py:2
 The weights are random, so the CTC head's blank bias is calibrated first: 10 % of the frames are non-blank, about 25 tokens per 10 s
 utterance (a trained Chinese model's rate); without it the hypotheses of a random head run to hundreds of tokens.
 
-usage: python tools/decode_bench.py [--reps 10] [--host-utts 4]"""
+--arm attention measures the autoregressive `attention` decode mode instead, for ONE 10 s utterance at the same model and beam 10:
+the device-resident search (KV-cached decoder step + beam step, conformer.asr_model.recognize), its kernel launches per step, the same
+search done by re-running TransformerDecoder on the growing prefix at every step (what the reference does, minus its maxlen padding
+and its repeated encoder output; this yardstick lives here only) and attention_rescoring on the same input.  With random weights no
+beam ever takes eos, so both searches run to the length limit (248 steps): the per-step figures are the ones to carry over.
+
+usage: python tools/decode_bench.py [--reps 10] [--host-utts 4] [--arm ctc|attention]"""
 import argparse
 import json
 import math
@@ -53,11 +59,84 @@ def host_prefix_search(lp, ix, beam):
     return [(p, log_add(list(v))) for p, v in cur]
 
 
+def attention_arm(a):
+    import torch
+
+    import mindaudio_amd as ma
+    from mindaudio_amd.conformer.asr_model import (Attention, AttentionRescoring, CTCPrefixBeamSearch, attention_rescoring,
+                                                   create_asr_model, recognize)
+
+    dev = torch.device("cuda")
+    torch.manual_seed(777)
+    model = create_asr_model(80, VOCAB, dict(output_size=256, attention_heads=4, linear_units=2048, num_blocks=12), ctc_weight=0.3,
+                             decoder_conf=dict(attention_heads=4, linear_units=2048, num_blocks=6)).to(dev).eval()
+    x = torch.from_numpy((0.1 * np.random.RandomState(1234).randn(1, SAMPLES)).astype(np.float32)).to(dev)
+    xs = ma.fbank(x, n_mels=80, n_fft=512, hop_length=160).transpose(1, 2)[:, :FRAMES].contiguous()
+    masks = torch.ones(1, 1, FRAMES, device=dev)
+    eos = VOCAB - 1
+    net = Attention(model, BEAM, eos)
+    init = (np.array([eos], np.int32), np.zeros((1, 1), np.int32), np.array([0.0] + [-np.inf] * (BEAM - 1), np.float32),
+            np.zeros(BEAM, np.float32))
+
+    class FullPrefix:
+        """The yardstick: every step re-runs the decoder on the whole prefix of every beam (beam reorder by gathering token rows)."""
+        beam_size = BEAM
+
+        def begin(self, xs_pad, xs_masks, xs_lengths=None):
+            sub = xs_masks[:, :, :-2:2][:, :, :-2:2].contiguous()
+            enc, enc_mask = model.encoder(xs_pad, sub, sub)
+            maxlen = enc.shape[1]
+            toks = torch.zeros((BEAM, maxlen), dtype=torch.int32, device=dev)
+            tril = torch.tril(torch.ones(maxlen, maxlen, device=dev))
+
+            def step(tokens, t, parent=None):
+                if parent is not None:
+                    toks[:, :t] = toks[parent.long(), :t]
+                toks[:, t] = tokens
+                m = tril[:t + 1, :t + 1][None].expand(BEAM, t + 1, t + 1).contiguous()
+                return model.decoder.score_hypotheses(enc, enc_mask, toks[:, :t + 1].contiguous(), m, BEAM)[:, t]
+
+            return maxlen, step
+
+    def wall(fn, reps):
+        ts, out = [], None
+        for r in range(reps + 1):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            out = fn()
+            torch.cuda.synchronize()
+            if r >= 1:
+                ts.append((time.perf_counter() - t0) * 1e3)
+        return statistics.median(ts), out
+
+    sub = masks[:, :, :-2:2][:, :, :-2:2].contiguous()
+    enc_ms, (enc, _) = wall(lambda: model.encoder(xs, sub, sub), a.reps)
+    steps = enc.shape[1] - 1
+    cached_ms, (hyp_c, score_c) = wall(lambda: recognize(net, xs, masks, *init, BEAM, eos), a.reps)
+    full_ms, (hyp_f, score_f) = wall(lambda: recognize(FullPrefix(), xs, masks, *init, BEAM, eos), max(1, a.reps // 3))
+    ctc, rescore = CTCPrefixBeamSearch(model, BEAM), AttentionRescoring(model, BEAM)
+    resc_ms, _ = wall(lambda: attention_rescoring(ctc, rescore, xs, masks, None, eos, eos, BEAM, 0.0), a.reps)
+    same = int((hyp_c[0] == hyp_f[0]).sum())
+    print(json.dumps({
+        "workload": "1 x 10 s synthetic, hybrid Conformer (12 + 6 blocks, V %d), attention decode mode, beam %d" % (VOCAB, BEAM),
+        "decoder_steps": steps, "launches_per_step": model.decoder.launches_per_step + 2,
+        "encoder_ms": round(enc_ms, 3),
+        "attention_ms_per_utt": round(cached_ms, 3), "attention_ms_per_step": round((cached_ms - enc_ms) / steps, 4),
+        "full_prefix_ms_per_utt": round(full_ms, 3), "full_prefix_ms_per_step": round((full_ms - enc_ms) / steps, 4),
+        "speedup_over_full_prefix": round(full_ms / cached_ms, 2),
+        "attention_rescoring_ms_per_utt": round(resc_ms, 3),
+        "tokens_equal_to_full_prefix": "%d/%d" % (same, steps), "best_score": [round(float(score_c[0]), 3), round(float(score_f[0]), 3)],
+    }))
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--host-utts", type=int, default=4)
+    ap.add_argument("--arm", choices=("ctc", "attention"), default="ctc")
     a = ap.parse_args()
+    if a.arm == "attention":
+        return attention_arm(a)
 
     import torch
 
