@@ -481,7 +481,10 @@ __global__ __launch_bounds__(256) void convmid_fwd_train_kernel(const AT* __rest
 #pragma unroll
   for (int j = 0; j < KS; ++j) wr[j] = w[c * KS + j];
   const float bc = bias[c];
-  float s1 = 0.0f, s2 = 0.0f;
+  // compensated (Kahan) sums: bn_finalize_kernel takes the variance as E[z^2] - mean^2, where a channel whose mean is far from 0
+  // (|mean| / sigma = 32: 1 + mean^2 / sigma^2 = 1025) magnifies the relative error of both sums by that factor; a plain chain of
+  // 32 additions left 33 u there, these leave 2 u (+ u for the square)
+  float s1 = 0.0f, s2 = 0.0f, c1 = 0.0f, c2 = 0.0f;
   for (int sidx = 0; sidx < kCfPerBlock; ++sidx) {
     const int t0 = (blockIdx.x * kCfPerBlock + sidx) * kCfStrip;
     if (t0 >= T) break;
@@ -509,8 +512,12 @@ __global__ __launch_bounds__(256) void convmid_fwd_train_kernel(const AT* __rest
 #pragma unroll
       for (int j = 0; j < KS; ++j) acc = fmaf(wr[j], s_t[(r + j) * 256 + tid], acc);
       z[(base + t) * C + c] = acc;
-      s1 += acc;
-      s2 += acc * acc;
+      const float y1 = acc - c1, n1 = s1 + y1;
+      c1 = (n1 - s1) - y1;
+      s1 = n1;
+      const float y2 = acc * acc - c2, n2 = s2 + y2;
+      c2 = (n2 - s2) - y2;
+      s2 = n2;
     }
   }
   // per-workgroup partial (sum | sum of squares) of the workgroup's frames; bn_finalize_kernel adds them in a fixed order
@@ -522,12 +529,16 @@ __global__ __launch_bounds__(256) void convmid_fwd_train_kernel(const AT* __rest
 // stats[c] = mean, stats[C + c] = rstd (biased variance, nn.BatchNorm1d training mode); running statistics updated
 // with the unbiased variance: running = (1 - momentum) * running + momentum * batch.  `sums` = nparts partial vectors
 // (sum | sum of squares) of 2 C floats; workgroup = 16 channels x 16 groups of partials, fixed summation order.
+// The partials are added, and mean and E[z^2] - mean^2 formed, in DOUBLE: in float32 the subtraction alone lost
+// u (1 + mean^2 / sigma^2) of the variance and the chain of nparts / 16 + 16 additions that much per step (a derived 2^-7 of rstd
+// at |mean| / sigma = 32 over 16 320 frames, above half a bf16 step of the normalised activations).  A few hundred double
+// additions per channel; the launch stays bound by the latency of its loads.
 __global__ __launch_bounds__(256) void bn_finalize_kernel(const float* __restrict__ sums, int nparts, int C, float count, float eps,
                                                           float momentum, float* run_mean, float* run_var, float* stats) {
-  __shared__ float red[2][16][17];
+  __shared__ double red[2][16][17];
   const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;
   const int c = blockIdx.x * 16 + tx;
-  float a = 0.0f, q = 0.0f;
+  double a = 0.0, q = 0.0;
   if (c < C) {
     // eight partials of a thread in flight (16 workgroups in all: as a plain loop the launch was a chain of nparts / 16 dependent
     // round trips, 9 us); the summation order is unchanged
@@ -541,29 +552,30 @@ __global__ __launch_bounds__(256) void bn_finalize_kernel(const float* __restric
       }
 #pragma unroll
       for (int u = 0; u < 8; ++u) {
-        a += va[u];
-        q += vq[u];
+        a += (double)va[u];
+        q += (double)vq[u];
       }
     }
     for (; b < nparts; b += 16) {
-      a += sums[(int64_t)b * 2 * C + c];
-      q += sums[(int64_t)b * 2 * C + C + c];
+      a += (double)sums[(int64_t)b * 2 * C + c];
+      q += (double)sums[(int64_t)b * 2 * C + C + c];
     }
   }
   red[0][ty][tx] = a;
   red[1][ty][tx] = q;
   __syncthreads();
   if (ty != 0 || c >= C) return;
-  a = 0.0f;
-  q = 0.0f;
+  a = 0.0;
+  q = 0.0;
 #pragma unroll
   for (int k = 0; k < 16; ++k) {
     a += red[0][k][tx];
     q += red[1][k][tx];
   }
-  const float mean = a / count;
-  float var = q / count - mean * mean;
-  var = var < 0.0f ? 0.0f : var;
+  const double meand = a / (double)count;
+  double vard = q / (double)count - meand * meand;
+  vard = vard < 0.0 ? 0.0 : vard;
+  const float mean = (float)meand, var = (float)vard;
   stats[c] = mean;
   stats[C + c] = 1.0f / sqrtf(var + eps);
   if (run_mean) {
