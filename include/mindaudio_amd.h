@@ -1686,6 +1686,39 @@ int ma_lstm_bidir_bf16(const void* x, int64_t T, int64_t B, int32_t Kpad, int32_
                        const float* bias, int32_t dir_mask, int64_t time_chunk, float* out_f32, void* out_bf16, float* c_final,
                        void* workspace, int64_t workspace_bytes, ma_stream_t stream);
 
+/* ---- Bidirectional LSTM layer, training: the forward that keeps a tape, and backward through time -------------------------------------
+ * ma_lstm_bidir_train_bf16: ma_lstm_bidir_bf16 with the same operands, schedule and launches (the step kernels' taping
+ *   instantiations): out_f32, out_bf16 and c_final have the SAME BITS.  It also fills `tape`, ma_lstm_train_tape_bytes(T, B, H) bytes,
+ *   16-byte aligned (MA_ERR_WORKSPACE when tape_bytes is less):
+ *     act (2, T, 5, B, H) float32 at offset 0: per direction and frame the planes i, f, g, o - the ACTIVATED gates - and c_t;
+ *     h   (2, T, B, H) bf16 at ma_lstm_train_tape_h_offset(T, B, H): the h_t that was fed back (the MFMA operand of the next step).
+ *   A direction outside dir_mask leaves its half untouched.  (T = 625, B = 64, H = 1024: 1.80 GB.)
+ * ma_lstm_pack_bwd_f32: w_hh (2, 4H, H) float32 -> whh_bwd_packed, 2 * 4H * H bf16 in the backward step's fragment order
+ *   (csrc/lstm_common.h: per slice of 16 hidden units the k-steps over gate * H + unit), 16-byte aligned.
+ * ma_lstm_bidir_bwd_bf16: dout (T, B, H) float32 = dL/d(out); it feeds both directions, out being their sum.  -> dgates
+ *   (2, T, B, 4H) bf16, gate order i, f, g, o: the gradient with respect to the PRE-ACTIVATION gate sums per direction; the half of a
+ *   direction outside dir_mask is set to zero.  ONE LAUNCH PER TIME STEP from a host loop inside the call, each serving both
+ *   directions (step s: t = T - 1 - s forward, t = s reverse); stream order is the only synchronisation, no atomics: the same bits
+ *   run to run.  Per step: dh = dout[t] + dgates_next . W_hh (MFMA, float32 accumulation), th = tanh(c_t),
+ *     do = dh th o (1 - o),  dc = dh o (1 - th^2) + dc_next,  di = dc g i (1 - i),  dg = dc i (1 - g^2),  df = dc c_{t-1} f (1 - f)
+ *     with c_{-1} = 0,  dc_next <- dc f.
+ *   Rounding points: dgates -> bf16 (round to nearest even) as the stored result and as the next step's MFMA operand, W_hh -> bf16 in
+ *   the pack; dout, dh, dc, the tape and every factor are float32.  The parameter and input gradients follow from dgates by the
+ *   library's products: dW_ih = ma_gemm_tn_bf16_f32(dgates[dir], x) with colsum = db_ih = db_hh, dW_hh the same against the tape's h
+ *   shifted by one frame (B rows), dx = sum over dir of ma_gemm_bf16(dgates[dir], W_ih[dir]^T).
+ *   workspace >= ma_lstm_bwd_workspace_bytes(B, H), 16-byte aligned; it or the tape too short: MA_ERR_WORKSPACE.
+ * Shapes and error codes as for ma_lstm_bidir_bf16. */
+int64_t ma_lstm_train_tape_bytes(int64_t T, int64_t B, int32_t H);
+int64_t ma_lstm_train_tape_h_offset(int64_t T, int64_t B, int32_t H);
+int ma_lstm_bidir_train_bf16(const void* x, int64_t T, int64_t B, int32_t Kpad, int32_t H, const void* wih_bf16, const void* whh_packed,
+                             const float* bias, int32_t dir_mask, int64_t time_chunk, float* out_f32, void* out_bf16, float* c_final,
+                             void* tape, int64_t tape_bytes, void* workspace, int64_t workspace_bytes, ma_stream_t stream);
+int ma_lstm_pack_bwd_f32(const float* w_hh, int32_t H, void* whh_bwd_packed, ma_stream_t stream);
+int64_t ma_lstm_bwd_workspace_bytes(int64_t B, int32_t H);
+int ma_lstm_bidir_bwd_bf16(const float* dout, int64_t T, int64_t B, int32_t H, const void* tape, int64_t tape_bytes,
+                           const void* whh_bwd_packed, int32_t dir_mask, void* dgates, void* workspace, int64_t workspace_bytes,
+                           ma_stream_t stream);
+
 /* ---- DeepSpeech2 (mindaudio/models/deepspeech2.py) outside its LSTM layers and GEMMs ---------------------------------------------------
  * ma_ds2_conv1_bf16: Conv2d(1 -> 32, (41, 11), stride (2, 2), pad (20, 5), no bias) + BatchNorm2d in affine form + tanh.
  *   x (B, F, T) float32; wt (451, 32) float32 = the weight transposed to [frequency tap * 11 + time tap][channel]; scale / shift (32).

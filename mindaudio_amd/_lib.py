@@ -467,6 +467,12 @@ PROTOTYPES = {
     "ma_lstm_workspace_bytes": (i64, [i64, i64, i32, i64]),
     "ma_lstm_pack_f32": (ctypes.c_int, [vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp]),
     "ma_lstm_bidir_bf16": (ctypes.c_int, [vp, i64, i64, i32, i32, vp, vp, vp, i32, i64, vp, vp, vp, vp, i64, vp]),
+    "ma_lstm_train_tape_bytes": (i64, [i64, i64, i32]),
+    "ma_lstm_train_tape_h_offset": (i64, [i64, i64, i32]),
+    "ma_lstm_bidir_train_bf16": (ctypes.c_int, [vp, i64, i64, i32, i32, vp, vp, vp, i32, i64, vp, vp, vp, vp, i64, vp, i64, vp]),
+    "ma_lstm_pack_bwd_f32": (ctypes.c_int, [vp, i32, vp, vp]),
+    "ma_lstm_bwd_workspace_bytes": (i64, [i64, i32]),
+    "ma_lstm_bidir_bwd_bf16": (ctypes.c_int, [vp, i64, i64, i32, vp, i64, vp, i32, vp, vp, i64, vp]),
     "ma_ds2_conv1_bf16": (ctypes.c_int, [vp, i64, i32, i64, vp, vp, vp, i32, vp, vp]),
     "ma_ds2_softmax_f32": (ctypes.c_int, [vp, i64, i64, i64, i32, vp, vp]),
     # ---- layer-pipelined LSTM stack, TasNet ----

@@ -1,6 +1,8 @@
 // Bidirectional LSTM layer, inference (mindaudio/models/deepspeech2.py BatchRNN: nn.LSTM(bidirectional=True, has_bias=True), the two
 // directions SUMMED).  Contract: include/mindaudio_amd.h.  The tile, the cell, the packed weights' fragment order and the K loop are
 // lstm_common.h's; this file holds the schedule, the direction sum and the two ways a workgroup covers its batch rows.
+// The training forward (ma_lstm_bidir_train_bf16) is the same code under the compile-time flag TAPE: it also writes what the backward
+// pass of lstm_train.hip reads.  The TAPE = false instantiations are the inference kernels, instruction for instruction.
 //
 // Schedule.  One layer = the input projection of a time chunk (ma_gemm_bf16, float32 out, b_ih + b_hh as its bias) followed by ONE
 // LAUNCH PER TIME STEP of a step kernel, issued from the host loop of ma_lstm_bidir_bf16.  The stream order between those launches is
@@ -48,6 +50,16 @@ struct LstmStep {
   int32_t B, H;
 };
 
+// The training forward is the same step with a TAPE: the step's frame of the tape per direction (lstm_common.h: five (B, H) float32
+// planes i, f, g, o, c, and the bf16 h image).  The inference step carries none of it: LstmStepT<false> is LstmStep.
+template <bool TAPE>
+struct LstmStepT : LstmStep {};
+template <>
+struct LstmStepT<true> : LstmStep {
+  float* tape_act[2];     // (5, B, H) of frame t
+  uint16_t* tape_h[2];    // (B, H) of frame t
+};
+
 // What the cell of one 16 x 16 tile reads besides the product, in the C/D layout (batch row b0 + 4 (lane >> 4) + r, hidden unit
 // 16 sl + (lane & 15)): the four projections, c and - for the direction that reaches a frame second - the other direction's h.
 // Rows beyond B read nothing.
@@ -75,7 +87,8 @@ __device__ __forceinline__ LstmCellIn lstm_cell_load(const LstmStep& p, int dir,
 }
 
 // The gate sums, the cell and the stores of a tile.  Rows beyond B store nothing.
-__device__ __forceinline__ void lstm_cell_store(const LstmStep& p, int dir, int sl, int b0, int lane, const f32x4 (&acc)[4],
+template <bool TAPE>
+__device__ __forceinline__ void lstm_cell_store(const LstmStepT<TAPE>& p, int dir, int sl, int b0, int lane, const f32x4 (&acc)[4],
                                                 const LstmCellIn& in) {
   const int H = p.H;
   const int64_t dir_off = (int64_t)dir * p.B * H;
@@ -86,10 +99,26 @@ __device__ __forceinline__ void lstm_cell_store(const LstmStep& p, int dir, int 
     const int b = b0 + 4 * (lane >> 4) + r;
     if (b >= p.B) continue;
     const int64_t e = (int64_t)b * H + j;
-    const LstmCell o = lstm_cell(acc[0][r] + in.gate[0][r], acc[1][r] + in.gate[1][r], acc[2][r] + in.gate[2][r],
-                                 acc[3][r] + in.gate[3][r], in.c[r]);
+    const auto o = [&] {
+      if constexpr (TAPE)
+        return lstm_cell_taped(acc[0][r] + in.gate[0][r], acc[1][r] + in.gate[1][r], acc[2][r] + in.gate[2][r],
+                               acc[3][r] + in.gate[3][r], in.c[r]);
+      else
+        return lstm_cell(acc[0][r] + in.gate[0][r], acc[1][r] + in.gate[1][r], acc[2][r] + in.gate[2][r], acc[3][r] + in.gate[3][r],
+                         in.c[r]);
+    }();
     p.c[dir_off + e] = o.c;
     p.h_out[dir_off + e] = f2bf(o.h);
+    if constexpr (TAPE) {
+      const int64_t plane = (int64_t)p.B * H;
+      float* ta = p.tape_act[dir] + e;
+      ta[0] = o.i;
+      ta[plane] = o.f;
+      ta[2 * plane] = o.g;
+      ta[3 * plane] = o.o;
+      ta[4 * plane] = o.c;
+      p.tape_h[dir][e] = f2bf(o.h);
+    }
     if (mode == kLstmFirst) {
       p.out_f32[dir][e] = o.h;
     } else if (mode == kLstmTie) {
@@ -110,8 +139,8 @@ __device__ __forceinline__ const uint16_t* lstm_h_row(const LstmStep& p, int dir
 
 // Each wave runs all of K for its own batch tile (the form for an H / 32 that is no multiple of 4; launched with KB = 2).  KB =
 // k-steps per operand block (5 KB of 16 bytes per lane).
-template <int KB>
-__global__ __launch_bounds__(kLstmThreads) void lstm_step_kernel(const LstmStep p) {
+template <int KB, bool TAPE>
+__global__ __launch_bounds__(kLstmThreads) void lstm_step_kernel(const LstmStepT<TAPE> p) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int b0 = ((int)blockIdx.z * 4 + wave) * 16;
   if (b0 >= p.B) return;  // (no barrier anywhere in this kernel)
@@ -131,8 +160,8 @@ constexpr int kLstmPartialFloats = 4 * 3 * 16 * 64;  // [source wave][other tile
 // four batch tiles of the workgroup, so the workgroup reads its 128 KB slice of W_hh once instead of once per wave.  The partial
 // accumulators of the three tiles a wave does not own go through LDS; after the workgroup's one barrier wave w adds the four
 // partials of tile w in wave order and runs the cell.  Tiles beyond B compute on row 0's operand and store nothing.
-template <int KB>
-__global__ __launch_bounds__(kLstmThreads) void lstm_step_ksplit_kernel(const LstmStep p) {
+template <int KB, bool TAPE>
+__global__ __launch_bounds__(kLstmThreads) void lstm_step_ksplit_kernel(const LstmStepT<TAPE> p) {
   __shared__ float part[kLstmPartialFloats];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int z0 = (int)blockIdx.z * kLstmRowsPerWg;
@@ -282,17 +311,26 @@ int ma_lstm_pack_f32(const float* w_ih, const float* w_hh, const float* b_ih, co
   return MA_OK;
 }
 
-int ma_lstm_bidir_bf16(const void* x, int64_t T, int64_t B, int32_t Kpad, int32_t H, const void* wih_bf16, const void* whh_packed,
-                       const float* bias, int32_t dir_mask, int64_t time_chunk, float* out_f32, void* out_bf16, float* c_final,
-                       void* workspace, int64_t workspace_bytes, ma_stream_t stream) {
-  if (!x || !wih_bf16 || !whh_packed || !bias || !out_f32 || !workspace || T < 1 || B < 1 || Kpad < 1 || H < 1 || time_chunk < 1 ||
-      dir_mask < 1 || dir_mask > 3)
+}  // extern "C"
+
+namespace ma {
+
+// The layer: ma_lstm_bidir_bf16 (TAPE = false) and ma_lstm_bidir_train_bf16 (TAPE = true: the same launches of the step kernels'
+// taping instantiations, which also fill `tape`, lstm_common.h's layout).
+template <bool TAPE>
+static int lstm_bidir_run(const void* x, int64_t T, int64_t B, int32_t Kpad, int32_t H, const void* wih_bf16, const void* whh_packed,
+                          const float* bias, int32_t dir_mask, int64_t time_chunk, float* out_f32, void* out_bf16, float* c_final,
+                          void* tape, int64_t tape_bytes, void* workspace, int64_t workspace_bytes, ma_stream_t stream) {
+  if (!x || !wih_bf16 || !whh_packed || !bias || !out_f32 || !workspace || (TAPE && !tape) || T < 1 || B < 1 || Kpad < 1 || H < 1 ||
+      time_chunk < 1 || dir_mask < 1 || dir_mask > 3)
     return MA_ERR_INVALID_ARG;
   if (!lstm_shape_ok(T, B, Kpad, H)) return MA_ERR_UNSUPPORTED;
-  if (!lstm_aligned16(x, wih_bf16, whh_packed, bias, workspace)) return MA_ERR_INVALID_ARG;
+  if (!lstm_aligned16(x, wih_bf16, whh_packed, bias, workspace) || (TAPE && !lstm_aligned16(tape))) return MA_ERR_INVALID_ARG;
   const int64_t chunk = time_chunk < T ? time_chunk : T;
   const LstmWs ws = lstm_ws(B, H, chunk);
   if (workspace_bytes < ws.total) return MA_ERR_WORKSPACE;
+  const LstmTapeLayout tl = lstm_tape_layout(T, B, H);
+  if (TAPE && tape_bytes < tl.total) return MA_ERR_WORKSPACE;
   hipStream_t st = (hipStream_t)stream;
   char* base = reinterpret_cast<char*>(workspace);
   uint16_t* hbuf = reinterpret_cast<uint16_t*>(base + ws.h);
@@ -323,8 +361,14 @@ int ma_lstm_bidir_bf16(const void* x, int64_t T, int64_t B, int32_t Kpad, int32_
       if (rc != MA_OK) return rc;
     }
     for (int64_t s = s0; s < s0 + n; ++s) {
-      LstmStep p;
+      LstmStepT<TAPE> p;
       const int64_t t[2] = {s, T - 1 - s};
+      if constexpr (TAPE) {
+        for (int d = 0; d < 2; ++d) {
+          p.tape_act[d] = reinterpret_cast<float*>(reinterpret_cast<char*>(tape) + tl.act) + (d * T + t[d]) * 5 * bh;
+          p.tape_h[d] = reinterpret_cast<uint16_t*>(reinterpret_cast<char*>(tape) + tl.h) + (d * T + t[d]) * bh;
+        }
+      }
       p.whh = reinterpret_cast<const uint16_t*>(whh_packed);
       p.h_in = hbuf + (s & 1) * 2 * bh;
       p.h_out = hbuf + ((s + 1) & 1) * 2 * bh;
@@ -340,16 +384,46 @@ int ma_lstm_bidir_bf16(const void* x, int64_t T, int64_t B, int32_t Kpad, int32_
         const int64_t other = T - 1 - s;  // the step at which the other direction serves this frame
         p.mode[d] = !both ? kLstmAlone : s < other ? kLstmFirst : s > other ? kLstmSecond : d == 0 ? kLstmFirst : kLstmTie;
       }
-      if ((H / 32) % 16 == 0) MA_LAUNCH(lstm_step_ksplit_kernel<4>, grid, dim3(kLstmThreads), 0, st, p);
-      else if ((H / 32) % 8 == 0) MA_LAUNCH(lstm_step_ksplit_kernel<2>, grid, dim3(kLstmThreads), 0, st, p);
-      else if ((H / 32) % 4 == 0) MA_LAUNCH(lstm_step_ksplit_kernel<1>, grid, dim3(kLstmThreads), 0, st, p);
-      else MA_LAUNCH(lstm_step_kernel<2>, grid, dim3(kLstmThreads), 0, st, p);
+      if ((H / 32) % 16 == 0) MA_LAUNCH((lstm_step_ksplit_kernel<4, TAPE>), grid, dim3(kLstmThreads), 0, st, p);
+      else if ((H / 32) % 8 == 0) MA_LAUNCH((lstm_step_ksplit_kernel<2, TAPE>), grid, dim3(kLstmThreads), 0, st, p);
+      else if ((H / 32) % 4 == 0) MA_LAUNCH((lstm_step_ksplit_kernel<1, TAPE>), grid, dim3(kLstmThreads), 0, st, p);
+      else MA_LAUNCH((lstm_step_kernel<2, TAPE>), grid, dim3(kLstmThreads), 0, st, p);
       if (both && s == T - 1 - s)
         MA_LAUNCH(lstm_tie_kernel, dim3((unsigned)((bh + 255) / 256)), dim3(256), 0, st, p.out_f32[0], p.out_bf16[0], p.tie, bh);
     }
   }
   if (c_final && hipMemcpyAsync(c_final, c, (size_t)(2 * bh * 4), hipMemcpyDeviceToDevice, st) != hipSuccess) return MA_ERR_LAUNCH;
   return MA_OK;
+}
+
+}  // namespace ma
+
+extern "C" {
+
+int ma_lstm_bidir_bf16(const void* x, int64_t T, int64_t B, int32_t Kpad, int32_t H, const void* wih_bf16, const void* whh_packed,
+                       const float* bias, int32_t dir_mask, int64_t time_chunk, float* out_f32, void* out_bf16, float* c_final,
+                       void* workspace, int64_t workspace_bytes, ma_stream_t stream) {
+  return lstm_bidir_run<false>(x, T, B, Kpad, H, wih_bf16, whh_packed, bias, dir_mask, time_chunk, out_f32, out_bf16, c_final, nullptr, 0,
+                               workspace, workspace_bytes, stream);
+}
+
+int64_t ma_lstm_train_tape_bytes(int64_t T, int64_t B, int32_t H) {
+  if (T < 1 || B < 1 || H < 1) return MA_ERR_INVALID_ARG;
+  if (!lstm_shape_ok(T, B, 64, H)) return MA_ERR_UNSUPPORTED;
+  return lstm_tape_layout(T, B, H).total;
+}
+
+int64_t ma_lstm_train_tape_h_offset(int64_t T, int64_t B, int32_t H) {
+  if (T < 1 || B < 1 || H < 1) return MA_ERR_INVALID_ARG;
+  if (!lstm_shape_ok(T, B, 64, H)) return MA_ERR_UNSUPPORTED;
+  return lstm_tape_layout(T, B, H).h;
+}
+
+int ma_lstm_bidir_train_bf16(const void* x, int64_t T, int64_t B, int32_t Kpad, int32_t H, const void* wih_bf16, const void* whh_packed,
+                             const float* bias, int32_t dir_mask, int64_t time_chunk, float* out_f32, void* out_bf16, float* c_final,
+                             void* tape, int64_t tape_bytes, void* workspace, int64_t workspace_bytes, ma_stream_t stream) {
+  return lstm_bidir_run<true>(x, T, B, Kpad, H, wih_bf16, whh_packed, bias, dir_mask, time_chunk, out_f32, out_bf16, c_final, tape,
+                              tape_bytes, workspace, workspace_bytes, stream);
 }
 
 }  // extern "C"

@@ -30,6 +30,40 @@ __device__ __forceinline__ LstmCell lstm_cell(float gi, float gf, float gg, floa
   return o;
 }
 
+// The same cell for the training forward, which also keeps the ACTIVATED gates for the backward pass.  c and h are the expressions
+// of lstm_cell on the same values, so the two give the same bits (tests/test_lstm_train_gpu.py holds them to that).
+struct LstmCellTaped {
+  float i, f, g, o, c, h;
+};
+__device__ __forceinline__ LstmCellTaped lstm_cell_taped(float gi, float gf, float gg, float go, float c_prev) {
+  LstmCellTaped o;
+  o.i = lstm_sigmoid(gi);
+  o.f = lstm_sigmoid(gf);
+  o.g = tanhf(gg);
+  o.o = lstm_sigmoid(go);
+  o.c = o.f * c_prev + o.i * o.g;
+  o.h = o.o * tanhf(o.c);
+  return o;
+}
+
+// The cell backward.  dh = dL/dh_t (the layer's dout plus what came back through W_hh), dc_next = dL/dc_t carried from the step
+// that follows in the direction's walk; i, f, g, o, c = the tape of this frame, c_prev = c_{t-1} (0 at the walk's first frame).
+// Everything is float32; the gradients of the four pre-activation gate sums leave as they are, the caller rounds them to bf16.
+struct LstmCellGrad {
+  float di, df, dg, dO, dc_prev;
+};
+__device__ __forceinline__ LstmCellGrad lstm_cell_bwd(float dh, float dc_next, float i, float f, float g, float o, float c, float c_prev) {
+  const float th = tanhf(c);
+  const float dc = dh * o * (1.0f - th * th) + dc_next;
+  LstmCellGrad r;
+  r.dO = dh * th * (o * (1.0f - o));
+  r.di = dc * g * (i * (1.0f - i));
+  r.dg = dc * i * (1.0f - g * g);
+  r.df = dc * c_prev * (f * (1.0f - f));
+  r.dc_prev = dc * f;
+  return r;
+}
+
 // ---- the fragment order -----------------------------------------------------------------------------------------------------------
 // A packed weight matrix is [slice of 16 units][k-step of 32][gate][lane][8] bf16: lane l of the wave holds, for hidden unit
 // 16 slice + (l & 15), the 8 columns 32 kstep + 8 (l >> 4) .. + 7 of that unit's row of gate g - the B fragment of one MFMA.  The 64
@@ -53,6 +87,24 @@ __device__ __forceinline__ LstmFragment lstm_fragment(int64_t i, int nk) {
   const int64_t q = i >> 8;  // slice * nk + kstep
   return {q / nk * kLstmSlice + (lane & 15), (int)(i >> 6) & 3, (int)(q % nk) * 32 + 8 * (lane >> 4)};
 }
+// The backward's order of W_hh (ma_lstm_pack_bwd_f32).  dh (B, H) = dgates (B, 4H) . W_hh contracts over the 4H gate rows
+// k = gate * H + unit, and the B operand's column is the hidden unit n that h_{t-1} fed: [slice of 16 units n][k-step of 32 over
+// 4H][lane][8] bf16 - lane l holds W_hh[32 kstep + 8 (l >> 4) .. + 7][16 slice + (l & 15)].  One accumulator per tile, so a k-step
+// is ONE 1 KiB run and a slice's 4H / 32 runs follow each other (the two directions are 2 H / 16 slices, as above).
+__device__ __forceinline__ const uint16_t* lstm_bwd_run(const uint16_t* w, int nk, int64_t slice, int kstep, int lane) {
+  return w + ((slice * nk + kstep) * 64 + lane) * 8;
+}
+// the inverse: fragment i (8 elements) of a matrix with nk = 4H / 32 k-steps per slice holds rows k .. k + 7 of column `unit`
+struct LstmBwdFragment {
+  int64_t unit;  // 16 slice + (lane & 15), over both directions
+  int k;         // first of its 8 gate rows
+};
+__device__ __host__ __forceinline__ LstmBwdFragment lstm_bwd_fragment(int64_t i, int nk) {
+  const int lane = (int)(i & 63);
+  const int64_t q = i >> 6;  // slice * nk + kstep
+  return {q / nk * 16 + (lane & 15), (int)(q % nk) * 32 + 8 * (lane >> 4)};
+}
+
 // columns k .. k + 7 of a float32 weight row of K columns -> one fragment at dst, round to nearest even; columns at or past K are zero
 __device__ __forceinline__ void lstm_pack_fragment(const float* row, int k, int K, uint16_t* dst) {
   float v[8];
@@ -124,6 +176,20 @@ static inline int64_t align256(int64_t v) { return (v + 255) & ~(int64_t)255; }
 static inline bool lstm_shape_ok(int64_t T, int64_t B, int64_t Kpad, int64_t H) {
   return T >= 1 && B >= 1 && H >= 64 && H % 64 == 0 && H <= 4096 && Kpad >= 64 && Kpad % 64 == 0 && B <= 65535 * (int64_t)kLstmRowsPerWg &&
          B * 4 * H <= 0x7fffffff;
+}
+
+// The tape of a training forward (ma_lstm_bidir_train_bf16 writes it, ma_lstm_bidir_bwd_bf16 reads it): act (2, T, 5, B, H) float32,
+// per direction and frame the planes i, f, g, o (activated) and c_t; then h (2, T, B, H) bf16, the h_t that was fed back.  A plane
+// is (B, H) like c, so the C/D layout stores and loads it the way it does c.
+struct LstmTapeLayout {
+  int64_t act, h, total;  // byte offsets
+};
+static inline LstmTapeLayout lstm_tape_layout(int64_t T, int64_t B, int64_t H) {
+  LstmTapeLayout t;
+  t.act = 0;
+  t.h = align256(2 * T * 5 * B * H * 4);
+  t.total = t.h + align256(2 * T * B * H * 2);
+  return t;
 }
 
 // every pointer is 16-byte aligned (the kernels' 16-byte loads and stores start at them)

@@ -1,4 +1,4 @@
-"""examples/deepspeech2/dataset.py, evaluation mode: LoadAudioAndTranscript.parse_audio on the device and ASRDataset's batching.
+"""examples/deepspeech2/dataset.py: LoadAudioAndTranscript.parse_audio on the device and ASRDataset's batching, evaluation and training.
 
 parse_audio: stft(n_fft = win_length = sample_rate * window_size, hop = sample_rate * window_stride) with stft's DEFAULT window - the
 yaml's `window: "hamming"` is never passed on by the reference (dataset.py:39-41) - then magphase(power = 1), log1p and, with
@@ -8,13 +8,23 @@ are float64, as data.processing.normalize computes them).
 ASRDataset (is_training=False): the manifest json {"root_path": ..., "samples": [{"wav_path": ..., "transcript_path": ...}, ...]},
 bins of batch_size utterances with the last bin refilled from the tail of the list (dataset.py:88-91), every utterance zero-padded to
 TEST_INPUT_PAD_LENGTH = 3500 frames, input_length (float32, as the reference returns it), target_indices (n, 2) int64 and the flat
-label_values int32.  The training branch and the MindSpore GeneratorDataset wrapper are not built."""
+label_values int32.
+
+ASRTrainDataset (ASRDataset(is_training=True) itself still refuses, as it always has): the same bins, the refilled last one
+included, every utterance zero-padded to TRAIN_INPUT_PAD_LENGTH = 1250 frames; a longer one is cropped to 1250 frames from a start drawn with np.random.randint(seq_length - 1250), one draw per long
+utterance in batch order - the reference's draws under the same NumPy seed.  Where the reference pads every target row to 350 entries
+with the blank id and hands all 350 to the loss as labels, this returns targets (b, Lmax) int32 (blank-padded) WITH the true
+target_lengths (b,) int32.  Utterances whose transcript has more than MAX_TARGET_LENGTH = 223 labels (the limit of
+ma_ctc_loss_grad_f32) are dropped from the list before it is cut into bins, with one printed count.
+The MindSpore GeneratorDataset wrapper (DistributedSampler, shuffling) is not built."""
 import json
 import os
 
 import numpy as np
 
 TEST_INPUT_PAD_LENGTH = 3500  # the max length in the test dataset (LibriSpeech), dataset.py:15
+TRAIN_INPUT_PAD_LENGTH = 1250  # dataset.py:11
+MAX_TARGET_LENGTH = 223  # labels per utterance that ma_ctc_loss_grad_f32 takes
 
 
 def _conf(audio_conf, key):
@@ -68,12 +78,14 @@ def _lib_const(name):
 
 class ASRDataset(LoadAudioAndTranscript):
     def __init__(self, audio_conf=None, manifest_filepath="", labels=None, normalize=False, batch_size=32, is_training=False):
-        if is_training:
-            raise NotImplementedError("the training branch of ASRDataset is not built")
+        if is_training != isinstance(self, ASRTrainDataset):
+            raise NotImplementedError("ASRDataset is the evaluation data set; the training one is ASRTrainDataset")
         with open(manifest_filepath) as f:
             json_file = json.load(f)
         self.root_path = json_file.get("root_path")
-        ids = [list(x.values()) for x in json_file.get("samples")]
+        self.labels_map = {labels[i]: i for i in range(len(labels))}
+        super().__init__(audio_conf, normalize, self.labels_map)
+        ids = self._select([list(x.values()) for x in json_file.get("samples")])
         self.is_training = is_training
         self.ids = ids
         self.blank_id = int(labels.index("_"))
@@ -83,26 +95,31 @@ class ASRDataset(LoadAudioAndTranscript):
             self.bins.append(ids[-batch_size:])
         self.size = len(self.bins)
         self.batch_size = batch_size
-        self.labels_map = {labels[i]: i for i in range(len(labels))}
-        super().__init__(audio_conf, normalize, self.labels_map)
+
+    def _select(self, ids):
+        return ids
+
+    def _load(self, index):
+        if index >= self.size:
+            raise IndexError(index)
+        batch_spect, batch_script = [], []
+        for data in self.bins[index]:
+            batch_spect.append(self.parse_audio(os.path.join(self.root_path, data[0])))
+            batch_script.append(self.parse_transcript(os.path.join(self.root_path, data[1])))
+        return batch_spect, batch_script
+
+    @staticmethod
+    def _zeros(like, shape):
+        if isinstance(like, np.ndarray):  # (a parse_audio that answers in NumPy is batched in NumPy)
+            return np.zeros(shape, dtype=np.float32)
+        return like.new_zeros(shape)
 
     def __getitem__(self, index):
         """(inputs (b, 1, F, 3500) float32 device tensor, input_length (b,) float32, target_indices (n, 2) int64, targets (n,) int32)"""
-        if index >= self.size:
-            raise IndexError(index)
-        batch_idx = self.bins[index]
-        batch_size = len(batch_idx)
-        batch_spect, batch_script, target_indices, targets = [], [], [], []
+        batch_spect, batch_script = self._load(index)
+        batch_size, target_indices, targets = len(batch_spect), [], []
         input_length = np.zeros(batch_size, np.float32)
-        for data in batch_idx:
-            batch_spect.append(self.parse_audio(os.path.join(self.root_path, data[0])))
-            batch_script.append(self.parse_transcript(os.path.join(self.root_path, data[1])))
-        freq_size = batch_spect[-1].shape[0]
-        shape = (batch_size, 1, freq_size, TEST_INPUT_PAD_LENGTH)
-        if isinstance(batch_spect[-1], np.ndarray):  # (a parse_audio that answers in NumPy is batched in NumPy)
-            inputs = np.zeros(shape, dtype=np.float32)
-        else:
-            inputs = batch_spect[-1].new_zeros(shape)
+        inputs = self._zeros(batch_spect[-1], (batch_size, 1, batch_spect[-1].shape[0], TEST_INPUT_PAD_LENGTH))
         for k, (spect_, scripts_) in enumerate(zip(batch_spect, batch_script)):
             seq_length = spect_.shape[1]
             input_length[k] = seq_length
@@ -113,3 +130,41 @@ class ASRDataset(LoadAudioAndTranscript):
 
     def __len__(self):
         return self.size
+
+
+class ASRTrainDataset(ASRDataset):
+    """ASRDataset's training branch (dataset.py:113-145); `log` receives the one line that counts the dropped utterances."""
+
+    def __init__(self, audio_conf=None, manifest_filepath="", labels=None, normalize=False, batch_size=32, log=print):
+        self.log, self.dropped = log, 0
+        super().__init__(audio_conf, manifest_filepath, labels, normalize, batch_size, is_training=True)
+
+    def _select(self, ids):
+        kept = [x for x in ids if len(self.parse_transcript(os.path.join(self.root_path, x[1]))) <= MAX_TARGET_LENGTH]
+        self.dropped = len(ids) - len(kept)
+        if self.dropped:
+            self.log("dropped %d of %d utterances: more than %d labels" % (self.dropped, len(ids), MAX_TARGET_LENGTH))
+        if not kept:
+            raise ValueError("no utterance to train on")
+        return kept
+
+    def __getitem__(self, index):
+        """(inputs (b, 1, F, 1250) float32, input_length (b,) float32, targets (b, Lmax) int32 padded with the blank id, target_lengths
+        (b,) int32)"""
+        batch_spect, batch_script = self._load(index)
+        b = len(batch_spect)
+        inputs = self._zeros(batch_spect[-1], (b, 1, batch_spect[-1].shape[0], TRAIN_INPUT_PAD_LENGTH))
+        input_length = np.zeros(b, np.float32)
+        target_lengths = np.array([len(s) for s in batch_script], np.int32)
+        targets = np.full((b, max(1, int(target_lengths.max()))), self.blank_id, np.int32)
+        for k, (spect_, scripts_) in enumerate(zip(batch_spect, batch_script)):
+            seq_length = spect_.shape[1]
+            targets[k, :len(scripts_)] = scripts_
+            if seq_length <= TRAIN_INPUT_PAD_LENGTH:
+                input_length[k] = seq_length
+                inputs[k, 0, :, 0:seq_length] = spect_
+            else:  # a random crop; one draw per long utterance, in batch order
+                start = np.random.randint(seq_length - TRAIN_INPUT_PAD_LENGTH)
+                input_length[k] = TRAIN_INPUT_PAD_LENGTH
+                inputs[k, 0] = spect_[:, start:start + TRAIN_INPUT_PAD_LENGTH]
+        return inputs, input_length, targets, target_lengths

@@ -26,6 +26,31 @@ def pack_bidir_layer(fwd, bwd, K, H):
     return _pack(_lib.load().ma_lstm_pack_f32, "lstm_pack", src, K, H, wih=(2, 4 * H, ceil64(K)), whh=(2 * 4 * H * H,), bias=(2, 4 * H))
 
 
+def pack_bidir_train_layer(fwd, bwd, K, H):
+    """pack_bidir_layer's operands plus what the backward pass reads: whh_bwd, W_hh in the backward step's fragment order
+    (ma_lstm_pack_bwd_f32), and wih_t (2, Kpad, 4H) bf16, the transposed copy of wih for dx = dgates . W_ih."""
+    L = pack_bidir_layer(fwd, bwd, K, H)
+    w_hh = torch.stack([fwd[1], torch.zeros_like(fwd[1]) if bwd is None else bwd[1]]).contiguous()
+    L["whh_bwd"] = torch.empty((2 * 4 * H * H,), dtype=torch.bfloat16, device=w_hh.device)
+    _lib.check(_lib.load().ma_lstm_pack_bwd_f32(w_hh.data_ptr(), H, L["whh_bwd"].data_ptr(), _host.current_stream_ptr()), "lstm_pack_bwd")
+    torch.cuda.current_stream().synchronize()  # (w_hh goes out of scope)
+    L["wih_t"] = L["wih"].transpose(1, 2).contiguous()
+    return dict(L, K=K)
+
+
+def run_train_layers(layers, xin, ws=None):
+    """The training forward of a stack of pack_bidir_train_layer's operands on a (T, B, Kpad) bf16 input, each layer reading the bf16
+    output of the one below -> (float32 (T, B, H) and bf16 output of the last layer, [the layers' tapes]).  The same calls on the same
+    operands as run_layers, so the outputs have its bits."""
+    from .. import ops
+
+    cur, tapes, of = xin, [], None
+    for L in layers:
+        of, cur, tape = ops.lstm_bidir_train(cur, L, workspace=ws)
+        tapes.append(tape)
+    return of, cur, tapes
+
+
 def pack_stack_layer(src, K, H):
     """src = [weight_ih (4H, K), weight_hh (4H, H), bias_ih (4H), bias_hh (4H)] float32 on the device -> one layer of
     ma_lstm_stack_bf16's operands {packed, bias, Kpad}."""

@@ -1124,3 +1124,107 @@ def si_snr_pit(source, estimate, lengths):
     mask = (t.arange(n, device=dev)[None, :] < lens[:, None]).to(estimate.dtype)[:, None, :]
     reordered = t.gather(estimate.to(dev), 1, perm[:, :, None].expand(b, c, n)) * mask
     return -max_snr.mean(), max_snr, reordered, perm, pair
+
+
+# ---- bidirectional LSTM layer, training (csrc/lstm.hip, csrc/lstm_train.hip) --------------------------------------------------------
+class LstmTape:
+    """What lstm_bidir_backward needs of a training forward: the layer's input x (T, B, Kpad) bf16 (kept by reference), the tape
+    buffer of ma_lstm_bidir_train_bf16 and the shape it was written for."""
+
+    def __init__(self, x, buf, T, B, H, dir_mask):
+        self.x, self.buf, self.T, self.B, self.H, self.dir_mask = x, buf, T, B, H, dir_mask
+
+    def views(self):
+        """(act (2, T, 5, B, H) float32: the activated gates i, f, g, o and c; h (2, T, B, H) bf16: the h that was fed back)."""
+        t = _host.torch()
+        T, B, H = self.T, self.B, self.H
+        off = int(_lib.load().ma_lstm_train_tape_h_offset(T, B, H))
+        act = self.buf[:2 * T * 5 * B * H * 4].view(t.float32).view(2, T, 5, B, H)
+        h = self.buf[off:off + 2 * T * B * H * 2].view(t.bfloat16).view(2, T, B, H)
+        return act, h
+
+
+def _lstm_check(x, layer):
+    t = _host.torch()
+    if not isinstance(x, t.Tensor) or x.dim() != 3 or x.dtype != t.bfloat16 or not x.is_cuda or not x.is_contiguous():
+        raise ValueError("x must be a contiguous (T, B, Kpad) bf16 tensor on the HIP device")
+    if x.shape[2] != layer["Kpad"]:
+        raise ValueError("x has %d columns, the layer was packed for %d" % (x.shape[2], layer["Kpad"]))
+    return x.shape[0], x.shape[1], layer["bias"].shape[1] // 4
+
+
+def lstm_bidir_train(x, layer, dir_mask=3, chunk=None, workspace=None, out_f32=None, out_bf16=None, tape_buf=None):
+    """The training forward of one bidirectional LSTM layer (ma_lstm_bidir_train_bf16): x (T, B, Kpad) bf16, layer = the operands of
+    models._lstm.pack_bidir_train_layer -> (out_f32 (T, B, H), out_bf16 (T, B, H), tape: LstmTape).  out_f32 / out_bf16 have the bits
+    of ma_lstm_bidir_bf16 on the same operands.
+    out_f32 / out_bf16 / tape_buf: caller-owned (T, B, H) float32, (T, B, H) bf16 and uint8 buffers to write into."""
+    t = _host.torch()
+    T, B, H = _lstm_check(x, layer)
+    _host.require_gpu()
+    lib, dev = _lib.load(), x.device
+    chunk = chunk or max(1, min(T, (1 << 26) // (B * 4 * H)))
+    nbytes, tbytes = int(lib.ma_lstm_workspace_bytes(T, B, H, chunk)), int(lib.ma_lstm_train_tape_bytes(T, B, H))
+    for v, what in ((nbytes, "lstm_workspace_bytes"), (tbytes, "lstm_train_tape_bytes")):
+        if v < 0:
+            _lib.check(v, what)
+    if workspace is None or workspace.numel() < nbytes:
+        workspace = t.empty((nbytes,), dtype=t.uint8, device=dev)
+    tape = t.empty((tbytes,), dtype=t.uint8, device=dev) if tape_buf is None else tape_buf
+    of = t.empty((T, B, H), dtype=t.float32, device=dev) if out_f32 is None else out_f32
+    ob = t.empty((T, B, H), dtype=t.bfloat16, device=dev) if out_bf16 is None else out_bf16
+    for v, dt, shape in ((tape, t.uint8, (tbytes,)), (of, t.float32, (T, B, H)), (ob, t.bfloat16, (T, B, H))):
+        if v.dtype != dt or tuple(v.shape) != shape or not v.is_contiguous() or v.device != dev:
+            raise ValueError("a caller-owned output must be contiguous, on x's device and of shape %s" % (shape,))
+    _lib.check(lib.ma_lstm_bidir_train_bf16(_host.ptr(x), T, B, layer["Kpad"], H, _host.ptr(layer["wih"]), _host.ptr(layer["whh"]),
+                                            _host.ptr(layer["bias"]), dir_mask, chunk, _host.ptr(of), _host.ptr(ob), None, _host.ptr(tape),
+                                            tbytes, _host.ptr(workspace), workspace.numel(), _host.current_stream_ptr()), "lstm_bidir_train")
+    return of, ob, LstmTape(x, tape, T, B, H, dir_mask)
+
+
+def lstm_bidir_backward(dout, tape, layer, need_dx=True, dgates=None):
+    """Backward through time of the layer whose training forward wrote `tape`: dout (T, B, H) float32 = dL/d(out_f32) ->
+      dgates (2, T, B, 4H) bf16   the gradient of the pre-activation gate sums per direction (ma_lstm_bidir_bwd_bf16)
+      dw_ih  (2, 4H, Kpad) f32    ma_gemm_tn_bf16_f32(dgates[dir], x); the columns past the layer's K are zero, as x's are
+      db     (2, 4H) f32          its column sum: the gradient of bias_ih and of bias_hh alike
+      dw_hh  (2, 4H, H) f32       the same product against the tape's h one frame earlier in the direction's walk; zero for T = 1
+      dx     (T, B, Kpad) f32     sum over the directions of dgates[dir] . W_ih[dir] (ma_gemm_bf16 on layer["wih_t"]); None
+                                  without need_dx.
+    A direction outside the forward's dir_mask has zero gradients.  dgates: a caller-owned contiguous buffer of that shape."""
+    t = _host.torch()
+    T, B, H, x = tape.T, tape.B, tape.H, tape.x
+    if not isinstance(dout, t.Tensor) or dout.dtype != t.float32 or tuple(dout.shape) != (T, B, H) or not dout.is_cuda:
+        raise ValueError("dout must be a (T, B, H) float32 tensor on the HIP device, H that of the tape")
+    dout = dout.contiguous()
+    lib, dev, Kpad, g4 = _lib.load(), dout.device, layer["Kpad"], 4 * H
+    s = _host.current_stream_ptr()
+    dg = t.empty((2, T, B, g4), dtype=t.bfloat16, device=dev) if dgates is None else dgates
+    if dg.dtype != t.bfloat16 or tuple(dg.shape) != (2, T, B, g4) or not dg.is_contiguous() or dg.device != dev:
+        raise ValueError("dgates must be a contiguous (2, T, B, 4H) bf16 tensor on dout's device")
+    wsb = int(lib.ma_lstm_bwd_workspace_bytes(B, H))
+    if wsb < 0:
+        _lib.check(wsb, "lstm_bwd_workspace_bytes")
+    ws = t.empty((wsb,), dtype=t.uint8, device=dev)
+    _lib.check(lib.ma_lstm_bidir_bwd_bf16(_host.ptr(dout), T, B, H, _host.ptr(tape.buf), tape.buf.numel(), _host.ptr(layer["whh_bwd"]),
+                                          tape.dir_mask, _host.ptr(dg), _host.ptr(ws), wsb, s), "lstm_bidir_bwd")
+    _, h = tape.views()
+    dw_ih = t.zeros((2, g4, Kpad), dtype=t.float32, device=dev)
+    dw_hh = t.zeros((2, g4, H), dtype=t.float32, device=dev)
+    db = t.zeros((2, g4), dtype=t.float32, device=dev)
+    tnb = max(int(lib.ma_gemm_tn_workspace_bytes(g4, Kpad, T * B)), int(lib.ma_gemm_tn_workspace_bytes(g4, H, max(1, (T - 1) * B))))
+    tn = t.empty((tnb + 256,), dtype=t.uint8, device=dev)
+    dirs = [d for d in (0, 1) if tape.dir_mask & (1 << d)]
+    for d in dirs:
+        _lib.check(lib.ma_gemm_tn_bf16_f32(_host.ptr(dg[d]), g4, _host.ptr(x), Kpad, _host.ptr(dw_ih[d]), Kpad, g4, Kpad, T * B, g4, 1.0, 0,
+                                           _host.ptr(db[d]), _host.ptr(tn), tnb, s), "lstm dW_ih")
+        if T > 1:  # forward: dgates[t] with h[t - 1]; reverse: dgates[t] with h[t + 1] - a shift of B rows either way
+            a, b = (dg[d, 1:], h[d, :T - 1]) if d == 0 else (dg[d, :T - 1], h[d, 1:])
+            _lib.check(lib.ma_gemm_tn_bf16_f32(_host.ptr(a), g4, _host.ptr(b), H, _host.ptr(dw_hh[d]), H, g4, H, (T - 1) * B, g4, 1.0, 0,
+                                               None, _host.ptr(tn), tnb, s), "lstm dW_hh")
+    dx = None
+    if need_dx:
+        for i, d in enumerate(dirs):
+            prev, dx = dx, t.empty((T, B, Kpad), dtype=t.float32, device=dev)
+            e = _epilogue(residual=prev.view(T * B, Kpad) if i else None, out_bf16=False)
+            _lib.check(lib.ma_gemm_bf16(_host.ptr(dg[d]), g4, _host.ptr(layer["wih_t"][d]), g4, _host.ptr(dx), Kpad, T * B, Kpad, g4,
+                                        ctypes.byref(e), s), "lstm dx")
+    return dict(dgates=dg, dw_ih=dw_ih, dw_hh=dw_hh, db=db, dx=dx)
