@@ -192,6 +192,7 @@ class SpeakerHeadTrainer:
 
         from .. import ops
         from ..train import kernels as K
+        from ..train.flat import adam_lr_t
 
         emb = emb.detach()
         on_device = isinstance(labels, torch.Tensor) and labels.is_cuda
@@ -203,8 +204,7 @@ class SpeakerHeadTrainer:
         self.flag.zero_()
         K.grad_overflow(self.grad, self.flag)
         lr = float(self.lr_list[min(self.global_step, len(self.lr_list) - 1)])
-        t = self.global_step + 1
-        lr_t = lr * math.sqrt(1.0 - self.b2 ** t) / (1.0 - self.b1 ** t)
+        lr_t = adam_lr_t(lr, self.global_step + 1, self.b1, self.b2)
         K.adam(self.weight, self.grad, self.exp_avg, self.exp_avg_sq, lr_t, self.b1, self.b2, self.adam_eps, 1.0 / self.loss_scale,
                self.flag)
         self.global_step += 1

@@ -6,8 +6,8 @@ gradient rides in its residual epilogue), ma_gemm_tn_bf16_f32 for dW = dY^T X; e
 csrc/conv_tasnet_train.hip (float32 with whole-utterance float64 sums, per-workgroup partials joined in a fixed order, no atomics).
 `operands="f32"` is the validation mode: the same kernels, every product through ma_gemm_x32 on float32 activations and weights.
 
-All parameters live in ONE flat float32 buffer (each padded to 8 elements), with the gradients, the momentum buffers and the bf16
-mirror laid out alike, so the optimizer is one launch.  The model's parameters become views of that buffer; the depthwise and the
+The parameters, the gradients, the momentum buffers and the bf16 mirror are a train.flat.FlatParams (8-element alignment), so the
+optimizer is one launch.  The model's parameters become views of its masters; the depthwise and the
 encoder weights are kept in the forward kernels' transposed order ((P, H) and (L, N)) and the model sees transposed views, so no
 layout copy runs in a step.  Moving the model to another device after the trainer has bound it is not supported.
 
@@ -19,6 +19,7 @@ import torch
 
 from .. import _host, _lib, ops
 from ..train import plans
+from ..train.flat import FlatTrainer, stored_last_first
 from .conv_tasnet import _OVERLAP, ConvTasNet, _epilogue
 
 __all__ = ["ConvTasNetTrainer"]
@@ -27,11 +28,7 @@ _TRAIN_H = (64, 128, 256, 512, 1024)  # one channel group per thread in the dept
 _OUTER_MAX = 12288                    # L * N of the basis / encoder gradient kernels
 
 
-def _pad8(n):
-    return (n + 7) // 8 * 8
-
-
-class ConvTasNetTrainer:
+class ConvTasNetTrainer(FlatTrainer):
     """ConvTasNetTrainer(model, momentum=0.0, weight_decay=0.0, operands="bf16", overlap=model.overlap).
 
     loss_and_grads(mixture (M, T), sources (M, C, T_out), lengths) -> loss (float); one float32 gradient per parameter, under the names
@@ -61,48 +58,29 @@ class ConvTasNetTrainer:
         self.model, self.momentum, self.weight_decay = model, float(momentum), float(weight_decay)
         self.operands, self.overlap, self.bf16 = operands, overlap, operands == "bf16"
         self.steps = 0
-        self._flat = None
         self._ws = {}
         self._stale = True
         model.register_load_state_dict_post_hook(lambda module, _keys: setattr(self, "_stale", True))
 
     # ---- parameters ---------------------------------------------------------------------------------------------------------------
-    def _view(self, flat, name):
-        off, n, shape, kind = self._slots[name]
-        v = flat[off:off + n]
-        if kind == "t3":  # stored (last, first), seen as (first, 1, last)
-            return v.view(shape[2], shape[0]).t().unsqueeze(1)
-        return v.view(shape)
-
     def _bind(self, dev):
         m = self.model
-        self._slots, off = {}, 0
-        for name, p in m.named_parameters():
-            kind = "t3" if name.endswith(("depthwise_conv.weight", "conv1d_U.weight")) else "plain"
-            self._slots[name] = (off, p.numel(), tuple(p.shape), kind)
-            off += _pad8(p.numel())
-        self._total = off
-        f32 = torch.float32
-        self._flat = torch.zeros(off, dtype=f32, device=dev)
-        self._grad = torch.zeros(off, dtype=f32, device=dev)
-        self._buf = torch.zeros(off, dtype=f32, device=dev) if self.momentum > 0 else None
-        self._mirror = torch.zeros(off, dtype=torch.bfloat16, device=dev) if self.bf16 else None
-        for name, p in m.named_parameters():
-            view = self._view(self._flat, name)
-            view.copy_(p.detach().to(device=dev, dtype=f32))
-            p.data = view
+        tap_major = ("depthwise_conv.weight", "conv1d_U.weight")  # kept (P, H) and (L, N), the order the forward kernels read
+        self._bind_params([(name, tuple(p.shape), stored_last_first if name.endswith(tap_major) else None) for name, p in m.named_parameters()],
+                          dev, mirror_bf16=self.bf16, moments=("momentum",) if self.momentum > 0 else ())
+        fp, f32 = self.params, torch.float32
         self._one = torch.ones(4, dtype=f32, device=dev)
         # the 1 x 1 convolutions: (out, in) views of the float32 master, the bf16 mirror and a transposed bf16 copy for dX
-        self._w1x1 = [n for n in self._slots if n.endswith(("conv1x1.weight", "pointwise_conv.weight"))]
+        self._w1x1 = [n for n in fp.index if n.endswith(("conv1x1.weight", "pointwise_conv.weight"))]
         self._wt = {}
         if self.bf16:
-            tot = sum(_pad8(self._slots[n][1]) for n in self._w1x1)
+            tot = sum((fp.index[n][2] + 7) // 8 * 8 for n in self._w1x1)
             self._wt_flat = torch.zeros(tot, dtype=torch.bfloat16, device=dev)
             o, items = 0, []
             for n in self._w1x1:
-                rows, cols = self._slots[n][2][:2]
+                rows, cols = fp.index[n][1][:2]
                 self._wt[n] = self._wt_flat[o:o + rows * cols].view(cols, rows)
-                o += _pad8(rows * cols)
+                o += (rows * cols + 7) // 8 * 8
                 w = self._w(n, bf=True)
                 items.append((_lib.TransposeItem(w.data_ptr(), self._wt[n].data_ptr(), cols, rows, rows, cols, 0, (cols + 63) // 64),
                               ((rows + 63) // 64) * ((cols + 63) // 64)))
@@ -111,46 +89,21 @@ class ConvTasNetTrainer:
         self._stale = True
 
     def _w(self, name, bf=False):
-        off, n, shape, _ = self._slots[name]
-        src = self._mirror if bf else self._flat
+        off, shape, n = self.params.index[name]
+        src = self.params.bf16 if bf else self.params.master
         return src[off:off + n].view(shape[0], shape[1])
 
     def _refresh(self, s):
         """The bf16 mirror and the transposed copies from the float32 master (after a load; a step refreshes them itself)."""
         lib = _lib.load()
         if self.bf16:
-            _lib.check(lib.ma_cast_f32_bf16(self._flat.data_ptr(), self._mirror.data_ptr(), self._total, s), "cast")
+            _lib.check(lib.ma_cast_f32_bf16(self.params.master.data_ptr(), self.params.bf16.data_ptr(), self.params.size, s), "cast")
             _lib.check(lib.ma_transpose_batch_bf16(*self._wt_plan.args, s), "transpose_batch")
         self._stale = False
-
-    def gradients(self):
-        """{state-dict name: float32 gradient} of the last loss_and_grads / step (views of the flat gradient)."""
-        return {name: self._view(self._grad, name) for name in self._slots}
 
     def activation_gradients(self):
         """The gradients of the last backward at the estimate, the mask scores, the bottleneck output and the normalised mixture_w."""
         return dict(self._act_grads)
-
-    def state_dict(self):
-        out = {k: v.detach().clone() for k, v in self.model.state_dict().items()}
-        if self._buf is not None and self._flat is not None:
-            for name in self._slots:
-                out["momentum." + name] = self._view(self._buf, name).detach().clone()
-        out["steps"] = torch.tensor(self.steps, dtype=torch.int64)
-        return out
-
-    def load_state_dict(self, state):
-        names = list(self.model.state_dict())
-        self.model.load_state_dict({k: state[k] for k in names})
-        self.steps = int(state.get("steps", 0))
-        mom = {k[len("momentum."):]: v for k, v in state.items() if k.startswith("momentum.")}
-        if mom and self.momentum > 0:
-            if self._flat is None:
-                self._pending_momentum = mom
-            else:
-                for name, v in mom.items():
-                    self._view(self._buf, name).copy_(v)
-        self._stale = True
 
     # ---- workspaces -----------------------------------------------------------------------------------------------------------------
     def _workspace(self, M, T, K, dev):
@@ -196,13 +149,13 @@ class ConvTasNetTrainer:
         offs, tot = [], 0
         for n in sizes:
             offs.append(tot)
-            tot += _pad8(n)
+            tot += (n + 7) // 8 * 8
         arena = ws["parts"] = torch.empty(tot, dtype=f32, device=dev)
         base, items = arena.data_ptr(), []
 
         def item(i, name, mn, splits):
-            off, _, _, _ = self._slots[name]
-            items.append(plans._reduce_item(base + offs[i] * 4, self._grad[off:off + mn], mn, mn, mn, splits, mn, splits >= 64, accumulate=False))
+            off = self.params.index[name][0]
+            items.append(plans._reduce_item(base + offs[i] * 4, self.params.grad[off:off + mn], mn, mn, mn, splits, mn, splits >= 64, accumulate=False))
             return base + offs[i] * 4
 
         names = self._block_names()
@@ -224,9 +177,6 @@ class ConvTasNetTrainer:
                 out.append(dict(c1=p + "conv1x1.weight", a1=p + "prelu.weight", dw=p + "dsconv.depthwise_conv.weight",
                                 a2=p + "dsconv.prelu.weight", pw=p + "dsconv.pointwise_conv.weight", d=2 ** x))
         return out
-
-    def _ptr(self, name, src=None):
-        return (self._flat if src is None else src).data_ptr() + self._slots[name][0] * 4
 
     # ---- the step -------------------------------------------------------------------------------------------------------------------
     def _check_inputs(self, mixture, sources, lengths):
@@ -250,16 +200,11 @@ class ConvTasNetTrainer:
         _host.require_gpu()
         dev = mixture.device
         with torch.no_grad():
-            if self._flat is None:
+            if self.params is None:
                 self.model.to(dev)
                 self._bind(dev)
-                mom = getattr(self, "_pending_momentum", None)
-                if mom:
-                    for name, v in mom.items():
-                        self._view(self._buf, name).copy_(v)
-                    self._pending_momentum = None
-            elif self._flat.device != dev:
-                raise ValueError("the trainer is bound to %s" % self._flat.device)
+            elif self.params.master.device != dev:
+                raise ValueError("the trainer is bound to %s" % self.params.master.device)
             ws = self._workspace(M, T, K, dev)
             x_in = mixture.to(torch.float32).contiguous()
             src = sources.to(torch.float32).contiguous()
@@ -277,13 +222,13 @@ class ConvTasNetTrainer:
 
     def step(self, mixture, sources, lengths, lr):
         loss = self.loss_and_grads(mixture, sources, lengths)
-        lib = _lib.load()
+        lib, fp = _lib.load(), self.params
         with torch.no_grad(), _host.pinned_stream():
             s = _host.current_stream_ptr()
-            _lib.check(lib.ma_sgd_momentum_f32(self._flat.data_ptr(), self._grad.data_ptr(),
-                                               self._buf.data_ptr() if self._buf is not None else None, self._total, float(lr),
+            _lib.check(lib.ma_sgd_momentum_f32(fp.master.data_ptr(), fp.grad.data_ptr(),
+                                               fp.momentum.data_ptr() if self.momentum > 0 else None, fp.size, float(lr),
                                                self.momentum, self.weight_decay, 1 if self.steps == 0 else 0,
-                                               self._mirror.data_ptr() if self.bf16 else None, s), "sgd_momentum")
+                                               fp.bf16.data_ptr() if self.bf16 else None, s), "sgd_momentum")
             if self.bf16:
                 _lib.check(lib.ma_transpose_batch_bf16(*self._wt_plan.args, s), "transpose_batch")
         self.steps += 1
@@ -291,10 +236,10 @@ class ConvTasNetTrainer:
         return loss
 
     def _gemms(self, rows, ws, s):
-        lib, ck, bf = _lib.load(), _lib.check, self.bf16
+        lib, ck, bf, ptr = _lib.load(), _lib.check, self.bf16, self.params.ptr
 
         def shape(name):
-            return self._slots[name][2][:2]  # (out, in)
+            return self.params.index[name][1][:2]  # (out, in)
 
         def fwd(a, name, out, residual=None):
             n, k = shape(name)
@@ -303,7 +248,7 @@ class ConvTasNetTrainer:
                 ck(lib.ma_gemm_bf16(a.data_ptr(), k, self._w(name, True).data_ptr(), k, out.data_ptr(), n, rows, n, k, ctypes.byref(epi), s),
                    "gemm")
             else:
-                ck(lib.ma_gemm_x32(a.data_ptr(), k, 1, self._ptr(name), k, 1, out.data_ptr(), n, rows, n, k, ctypes.byref(epi), s), "gemm_x32")
+                ck(lib.ma_gemm_x32(a.data_ptr(), k, 1, ptr(name), k, 1, out.data_ptr(), n, rows, n, k, ctypes.byref(epi), s), "gemm_x32")
 
         def dx(dy, name, out, residual=None):  # out (rows, in) = dy (rows, out) . W (+ residual)
             n, k = shape(name)
@@ -312,12 +257,12 @@ class ConvTasNetTrainer:
                 ck(lib.ma_gemm_bf16(dy.data_ptr(), n, self._wt[name].data_ptr(), n, out.data_ptr(), k, rows, k, n, ctypes.byref(epi), s),
                    "gemm dX")
             else:
-                ck(lib.ma_gemm_x32(dy.data_ptr(), n, 1, self._ptr(name), 1, k, out.data_ptr(), k, rows, k, n, ctypes.byref(epi), s),
+                ck(lib.ma_gemm_x32(dy.data_ptr(), n, 1, ptr(name), 1, k, out.data_ptr(), k, rows, k, n, ctypes.byref(epi), s),
                    "gemm_x32 dX")
 
         def dw(dy, x, name):  # grad (out, in) = dy^T . x
             n, k = shape(name)
-            g = self._ptr(name, self._grad)
+            g = ptr(name, self.params.grad)
             if bf:
                 ck(lib.ma_gemm_tn_bf16_f32(dy.data_ptr(), n, x.data_ptr(), k, g, k, n, k, rows, n, 1.0, 0, None, ws["tn_ws"].data_ptr(),
                                            ws["tn_bytes"], s), "gemm dW")
@@ -327,13 +272,13 @@ class ConvTasNetTrainer:
         return fwd, dx, dw
 
     def _forward(self, ws, x_in, M, T, K, s):
-        m, lib, ck, bf = self.model, _lib.load(), _lib.check, self.bf16
+        m, lib, ck, bf, ptr = self.model, _lib.load(), _lib.check, self.bf16, self.params.ptr
         N, L, B, H, C = m.N, m.L, m.B, m.H, m.C
         rows = M * K
         fwd, _, _ = self._gemms(rows, ws, s)
         norm = lib.ma_gln_apply_bf16 if bf else lib.ma_gln_apply_f32
         mw, pn = ws["mw"], ws["part_n"].data_ptr()
-        ck(lib.ma_tasnet_encode_f32(x_in.data_ptr(), M, T, T, self._ptr("encoder.conv1d_U.weight"), L, N, mw.data_ptr(), pn, s),
+        ck(lib.ma_tasnet_encode_f32(x_in.data_ptr(), M, T, T, ptr("encoder.conv1d_U.weight"), L, N, mw.data_ptr(), pn, s),
            "tasnet_encode")
         ck(norm(mw.data_ptr(), M, K, N, pn, ws["nb"].data_ptr(), s), "gln_apply")
         names = self._block_names()
@@ -344,8 +289,8 @@ class ConvTasNetTrainer:
                 ck(lib.ma_cast_f32_bf16(cur.data_ptr(), ws["xop"][b].data_ptr(), rows * B, s), "cast")
             y0, d0, pa, pb = ws["y0"][b], ws["d0"][b], ws["part_a"][b].data_ptr(), ws["part_b"][b].data_ptr()
             fwd(ws["xop"][b], nm["c1"], y0)
-            ck(lib.ma_prelu_gln_stats(y0.data_ptr(), M, K, H, self._ptr(nm["a1"]), ws["p1"].data_ptr(), pa, s), "prelu_gln_stats")
-            ck(lib.ma_gln_dwconv_prelu_train(ws["p1"].data_ptr(), M, K, H, pa, self._ptr(nm["dw"]), m.P, nm["d"], self._ptr(nm["a2"]),
+            ck(lib.ma_prelu_gln_stats(y0.data_ptr(), M, K, H, ptr(nm["a1"]), ws["p1"].data_ptr(), pa, s), "prelu_gln_stats")
+            ck(lib.ma_gln_dwconv_prelu_train(ws["p1"].data_ptr(), M, K, H, pa, ptr(nm["dw"]), m.P, nm["d"], ptr(nm["a2"]),
                                              d0.data_ptr(), ws["z"].data_ptr(), pb, s), "gln_dwconv_prelu_train")
             ck(norm(ws["z"].data_ptr(), M, K, H, pb, ws["hop"][b].data_ptr(), s), "gln_apply")
             nxt = ws["x"][(b + 1) % 2] if bf else ws["xop"][b + 1]
@@ -354,11 +299,11 @@ class ConvTasNetTrainer:
         if bf:
             ck(lib.ma_cast_f32_bf16(cur.data_ptr(), ws["xop"][-1].data_ptr(), rows * B, s), "cast")
         fwd(ws["xop"][-1], "separator.mask_conv1x1.weight", ws["score"])
-        ck(lib.ma_tasnet_decode_f32(ws["score"].data_ptr(), mw.data_ptr(), M, K, C, N, self._ptr("decoder.basis_signals.weight"), L,
+        ck(lib.ma_tasnet_decode_f32(ws["score"].data_ptr(), mw.data_ptr(), M, K, C, N, ptr("decoder.basis_signals.weight"), L,
                                     _OVERLAP[self.overlap], ws["out"].data_ptr(), s), "tasnet_decode")
 
     def _backward(self, ws, x_in, src, lens, perm, M, T, K, s):
-        m, lib, ck, bf = self.model, _lib.load(), _lib.check, self.bf16
+        m, lib, ck, bf, ptr = self.model, _lib.load(), _lib.check, self.bf16, self.params.ptr
         N, L, B, H, C = m.N, m.L, m.B, m.H, m.C
         rows = M * K
         _, dx, dw = self._gemms(rows, ws, s)
@@ -373,7 +318,7 @@ class ConvTasNetTrainer:
         ck(lib.ma_si_snr_grad_f32(src.data_ptr(), ws["out"].data_ptr(), lens.data_ptr(), perm.data_ptr(), M, C, src.shape[2],
                                   ws["d_est"].data_ptr(), s), "si_snr_grad")
         ck(lib.ma_tasnet_decode_bwd_f32(ws["d_est"].data_ptr(), ws["score"].data_ptr(), ws["mw"].data_ptr(), M, K, C, N,
-                                        self._ptr("decoder.basis_signals.weight"), L, _OVERLAP[self.overlap], ws["d_score"].data_ptr(),
+                                        ptr("decoder.basis_signals.weight"), L, _OVERLAP[self.overlap], ws["d_score"].data_ptr(),
                                         ws["dmw"].data_ptr(), ws["pp_basis"], s), "tasnet_decode_bwd")
         ds = operand(ws["d_score"], ws.get("d_score_op"))
         dw(ds, ws["xop"][-1], "separator.mask_conv1x1.weight")
@@ -386,11 +331,11 @@ class ConvTasNetTrainer:
             dxo = operand(cur, ws.get("dx_op"))
             dw(dxo, ws["hop"][b], nm["pw"])
             dx(dxo, nm["pw"], ws["dh"])
-            ck(lib.ma_gln_bwd_stats(ws["dh"].data_ptr(), d0, M, K, H, pb, self._ptr(nm["a2"]), ws["p2h"].data_ptr(), s), "gln_bwd_stats")
-            ck(lib.ma_gln2_bwd_dwconv(ws["dh"].data_ptr(), d0, y0, M, K, H, pa, pb, ws["p2h"].data_ptr(), self._ptr(nm["a1"]),
-                                      self._ptr(nm["a2"]), self._ptr(nm["dw"]), m.P, nm["d"], ws["du"].data_ptr(), ws["p2u"].data_ptr(),
+            ck(lib.ma_gln_bwd_stats(ws["dh"].data_ptr(), d0, M, K, H, pb, ptr(nm["a2"]), ws["p2h"].data_ptr(), s), "gln_bwd_stats")
+            ck(lib.ma_gln2_bwd_dwconv(ws["dh"].data_ptr(), d0, y0, M, K, H, pa, pb, ws["p2h"].data_ptr(), ptr(nm["a1"]),
+                                      ptr(nm["a2"]), ptr(nm["dw"]), m.P, nm["d"], ws["du"].data_ptr(), ws["p2u"].data_ptr(),
                                       pa2, pdw, s), "gln2_bwd_dwconv")
-            ck(lib.ma_gln1_bwd(ws["du"].data_ptr(), y0, M, K, H, pa, ws["p2u"].data_ptr(), self._ptr(nm["a1"]), ws["dy0"].data_ptr(),
+            ck(lib.ma_gln1_bwd(ws["du"].data_ptr(), y0, M, K, H, pa, ws["p2u"].data_ptr(), ptr(nm["a1"]), ws["dy0"].data_ptr(),
                                1 if bf else 0, pa1, s), "gln1_bwd")
             dw(ws["dy0"], ws["xop"][b], nm["c1"])
             dx(ws["dy0"], nm["c1"], nxt, residual=cur)  # d_x_in = d_x_out + d_conv1x1_out . W_c1

@@ -24,30 +24,25 @@ What the reference's script does and this keeps (each measured against a float64
 What it does not keep: the data set pads every target row to 350 entries with the blank id and passes all 350 as labels; this trainer
 takes the true lengths.  Targets longer than 223 labels are beyond ma_ctc_loss_grad_f32 and raise ValueError.
 
-All trained parameters live in ONE flat float32 buffer (each padded to 8 elements) in the reference's layouts, with the gradient and
-both moments laid out alike; the model's parameters become views of it.  Layer 0's weight_ih is kept in the reference's c * F2 + f
+The trained parameters, their gradient and both moments are a train.flat.FlatParams (8-element alignment) in the reference's layouts;
+the model's parameters become views of it.  Layer 0's weight_ih is kept in the reference's c * F2 + f
 column order; the kernels' f * 32 + c order exists only in the packed operands, and its gradient is permuted back."""
 import ctypes
-import math
 
 import numpy as np
 import torch
 
 from .. import _host, _lib, ops
 from ..train import kernels
+from ..train.flat import ADAM_BETA1, ADAM_BETA2, FlatTrainer, adam_lr_t
 from . import _lstm
 from .deepspeech2 import DeepSpeechModel, permute_wih_columns
 
 __all__ = ["DeepSpeech2Trainer", "unpermute_wih_columns", "MAX_TARGET_LENGTH"]
 
-_BETA1, _BETA2 = float(np.float32(0.9)), float(np.float32(0.999))  # nn.Adam's defaults as the float32 values the kernel works with
 _F32, _BF16 = torch.float32, torch.bfloat16
 MAX_TARGET_LENGTH = 223  # ma_ctc_loss_grad_f32: 2 L + 1 <= 448 lattice states
 _LEAVES = ("weight_ih", "weight_hh", "bias_ih", "bias_hh")
-
-
-def _pad8(n):
-    return (n + 7) // 8 * 8
 
 
 def unpermute_wih_columns(w, channels, n_freq):
@@ -56,7 +51,7 @@ def unpermute_wih_columns(w, channels, n_freq):
     return w.reshape(w.shape[0], n_freq, channels).permute(0, 2, 1).reshape(w.shape[0], channels * n_freq)
 
 
-class DeepSpeech2Trainer:
+class DeepSpeech2Trainer(FlatTrainer):
     """DeepSpeech2Trainer(model, learning_rate, eps, loss_scale=1024, optimizer_loss_scale=None, train_conv=False).
 
     loss_and_grads(x (B, 1, F, T), lengths (B), targets (B, Lmax) int32, target_lengths (B)) -> loss (float): the mean over the batch
@@ -80,8 +75,6 @@ class DeepSpeech2Trainer:
         self.blank = len(model.labels) - 1
         self.steps = 0
         self.launches = {}  # the library's launches per phase of the last step (torch's copies and fills are not counted)
-        self._flat = None
-        self._pending = None
         self.logits = None
         self.events = None  # a list: every phase boundary of a step appends (name, torch.cuda.Event) to it (tools/deepspeech2_train_bench.py)
 
@@ -100,28 +93,10 @@ class DeepSpeech2Trainer:
         return out + ["fc.module.weight"]
 
     def _bind(self, dev):
-        m = self.model
-        params = dict(m.named_parameters())
-        self._slots, off = {}, 0
-        for name in self._names():
-            p = params[name]
-            self._slots[name] = (off, p.numel(), tuple(p.shape))
-            off += _pad8(p.numel())
-        self._total = off
-        self._flat, self._grad, self._m1, self._m2 = (torch.zeros(off, dtype=_F32, device=dev) for _ in range(4))
-        for name in self._slots:
-            view = self._view(self._flat, name)
-            view.copy_(params[name].detach().to(device=dev, dtype=_F32))
-            params[name].data = view
+        shapes = {name: tuple(p.shape) for name, p in self.model.named_parameters()}
+        self._bind_params([(name, shapes[name]) for name in self._names()], dev, mirror_bf16=False, moments=("moment1", "moment2"))
         self._flag = torch.zeros(4, dtype=torch.int32, device=dev)
-        m._prepared = None
-        if self._pending:
-            self._load_moments(self._pending)
-            self._pending = None
-
-    def _view(self, flat, name):
-        off, n, shape = self._slots[name]
-        return flat[off:off + n].view(shape)
+        self.model._prepared = None
 
     def _repack(self):
         """The operands of every layer and of fc from the float32 masters: one pack per layer (csrc/lstm.hip, csrc/lstm_train.hip)."""
@@ -131,44 +106,17 @@ class DeepSpeech2Trainer:
         P, H = m._prepared, m.hidden_size
         layers = []
         for k in range(m.hidden_layers):
-            fwd, bwd = ([self._view(self._flat, "RNN.lstms.%d.%s_l0%s" % (k, leaf, d)) for leaf in _LEAVES] for d in ("", "_reverse"))
+            fwd, bwd = ([self.params.p("RNN.lstms.%d.%s_l0%s" % (k, leaf, d)) for leaf in _LEAVES] for d in ("", "_reverse"))
             if k == 0:
                 fwd[0], bwd[0] = permute_wih_columns(fwd[0], 32, m.F2), permute_wih_columns(bwd[0], 32, m.F2)
             layers.append(_lstm.pack_bidir_train_layer(fwd, bwd, m.rnn_input_size if k == 0 else H, H))
         P["layers"] = layers
-        fc = self._view(self._flat, "fc.module.weight")
+        fc = self.params.p("fc.module.weight")
         P["fc"] = fc.to(_BF16).contiguous()
         C = fc.shape[0]
         fct = torch.zeros((H, _lstm.ceil64(C)), dtype=_BF16, device=fc.device)  # dh = dlogits (rows, 64) . fc: W (N = H, K = 64)
         fct[:, :C] = P["fc"].t()
         P["fc_t"] = fct
-
-    def gradients(self):
-        """{reference name: float32 gradient of loss_scale * loss, in the reference's layout} of the last loss_and_grads / step."""
-        return {name: self._view(self._grad, name) for name in self._slots}
-
-    def state_dict(self):
-        out = {k: v.detach().clone().contiguous() for k, v in self.model.state_dict().items()}
-        if self._flat is not None:
-            for name in self._slots:
-                out["moment1." + name] = self._view(self._m1, name).detach().clone()
-                out["moment2." + name] = self._view(self._m2, name).detach().clone()
-        out["steps"] = torch.tensor(self.steps, dtype=torch.int64)
-        return out
-
-    def _load_moments(self, state):
-        for name in self._slots:
-            for prefix, buf in (("moment1.", self._m1), ("moment2.", self._m2)):
-                if prefix + name in state:
-                    self._view(buf, name).copy_(torch.as_tensor(state[prefix + name]).to(buf.device, _F32))
-
-    def load_state_dict(self, state):
-        self.model.load_state_dict({k: torch.as_tensor(state[k]) for k in self.model.state_dict()})  # (drops the packed operands)
-        self.steps = int(state.get("steps", 0))
-        if self._flat is None:
-            self._pending = dict(state)
-        else:
-            self._load_moments(state)
 
     # ---- calls ----------------------------------------------------------------------------------------------------------------------
     def _count(self, phase, n=1):
@@ -203,10 +151,10 @@ class DeepSpeech2Trainer:
         lib, ck = _lib.load(), _lib.check
         self.launches = {}
         with torch.no_grad():
-            if self._flat is None:
+            if self.params is None:
                 self._bind(dev)
-            elif self._flat.device != dev:
-                raise ValueError("the trainer is bound to %s" % self._flat.device)
+            elif self.params.master.device != dev:
+                raise ValueError("the trainer is bound to %s" % self.params.master.device)
             if m._prepared is None or "whh_bwd" not in m._prepared["layers"][0]:
                 self._repack()
             P, H, C = m._prepared, m.hidden_size, len(m.labels)
@@ -238,7 +186,7 @@ class DeepSpeech2Trainer:
             self._count("loss", 4)
             self._mark("loss")
             # ---- backward
-            self._grad.zero_()
+            self.params.grad.zero_()
             g = self.gradients()
             tnb = int(lib.ma_gemm_tn_workspace_bytes(ld, H, T1 * B))
             tn = torch.empty((tnb + 256,), dtype=torch.uint8, device=dev)
@@ -270,12 +218,12 @@ class DeepSpeech2Trainer:
 
     def step(self, x, lengths, targets, target_lengths):
         loss = self._run(x, lengths, targets, target_lengths)
-        t = self.steps + 1
-        lr_t = self.learning_rate * math.sqrt(1.0 - _BETA2 ** t) / (1.0 - _BETA1 ** t)
+        fp = self.params
+        lr_t = adam_lr_t(self.learning_rate, self.steps + 1, ADAM_BETA1, ADAM_BETA2)
         with torch.no_grad():
             self._flag.zero_()
-            kernels.grad_overflow(self._grad, self._flag)
-            kernels.adam(self._flat, self._grad, self._m1, self._m2, lr_t, _BETA1, _BETA2, self.eps,
+            kernels.grad_overflow(fp.grad, self._flag)
+            kernels.adam(fp.master, fp.grad, fp.moment1, fp.moment2, lr_t, ADAM_BETA1, ADAM_BETA2, self.eps,
                          1.0 / (self.loss_scale * self.optimizer_loss_scale), overflow=self._flag)
             self._count("update", 2)
             overflow = bool(int(self._flag[0].item()))  # the step's read-back, with the loss

@@ -17,13 +17,11 @@ One ma_reduce_splits_batch_f32 launch sums the partials of last_conv and the ini
 the same walk with float32 operand images (ma_wavegrad_pack_f32) and every product through ma_gemm_x32 / ma_colsum_x32, one call per
 tap and utterance.
 
-All parameters live in ONE flat float32 buffer (each padded to 8 elements) with the gradient and both Adam moments laid out alike, so
-the norm and the update are one launch each.  Convolution weights are kept in the operand order (N, taps, C) and the model's
-parameters become permuted views of them ((out, in, k) as the reference names them); the init convolution is kept (taps, C0), the order
-its forward kernel reads.  The bf16 operand copies (padded, and the transposed ones of the input gradients) are rewritten by one
+The parameters, the gradient and both Adam moments are a train.flat.FlatParams (8-element alignment), so the norm and the update are
+one launch each.  Convolution weights are kept in the operand order (N, taps, C) and the model's parameters become permuted views of
+them ((out, in, k) as the reference names them); the init convolution is kept (taps, C0), the order its forward kernel reads.  The bf16 operand copies (padded, and the transposed ones of the input gradients) are rewritten by one
 ma_wavegrad_weights_bf16 launch after an update.  Moving the model to another device after the trainer has bound it is not supported."""
 import ctypes
-import math
 
 import numpy as np
 import torch
@@ -31,19 +29,14 @@ import torch.nn as nn
 
 from .. import _host, _lib
 from ..train import plans
-from ..train.engine import DynamicLossScale
+from ..train.flat import (ADAM_BETA1, ADAM_BETA2, DynamicLossScale, FlatTrainer, adam_lr_t, stored_last_first,
+                          stored_taps_inner)
 from .wavegrad import WaveGrad, _pad64, positional_table
 
 __all__ = ["WaveGradTrainer"]
 
-# nn.Adam's defaults (train.py:130 passes only the learning rate) as the float32 values the kernel works with: the host's bias
-# correction must use the same ones (1 - 0.999f is 4.7e-5 above 0.001, which would be 2.3e-5 of every step)
-_BETA1, _BETA2, _EPS = float(np.float32(0.9)), float(np.float32(0.999)), 1e-8
+_EPS = 1e-8  # nn.Adam's default (train.py:130 passes only the learning rate)
 _F32, _BF16 = torch.float32, torch.bfloat16
-
-
-def _pad8(n):
-    return (n + 7) // 8 * 8
 
 
 def _epilogue(alpha=1.0, bias=None, residual=None, ldr=0):
@@ -130,7 +123,7 @@ class _Step:
     """Everything of one (B, frames) shape: the op list, the activation and gradient arenas, the item table of the partial sums."""
 
 
-class WaveGradTrainer:
+class WaveGradTrainer(FlatTrainer):
     """WaveGradTrainer(model, learning_rate, max_grad_norm=1.0, loss_scale=2**12, scale_factor=2, scale_window=1000, operands="bf16").
 
     loss_and_grads(noisy_audio (B, T), noise_scale (B,) or (1,), noise (B, T), spectrogram (B, n_mels, T / hop)) -> loss (float), the
@@ -138,7 +131,7 @@ class WaveGradTrainer:
         (out, in, k); activation_gradients()["pred"] the same for the network's output.
     step(noisy_audio, noise_scale, noise, spectrogram, lr=None) -> (loss, overflow, loss_scale): the same, then the gradient is
         unscaled, clipped by its global norm to max_grad_norm and applied by nn.Adam; a non-finite norm skips the update and halves
-        the loss scale (train.engine.DynamicLossScale).  `lr` defaults to learning_rate.
+        the loss scale (train.flat.DynamicLossScale).  `lr` defaults to learning_rate.
     state_dict() / load_state_dict(): the model's entries plus "moment1.<name>", "moment2.<name>", "steps" and "loss_scale".
 
     ValueError before any device call for CPU tensors, wrong ranks, T != hop * frames or a `noise` of another shape."""
@@ -156,10 +149,8 @@ class WaveGradTrainer:
         self.steps = 0
         self.last_norm = None
         self.launches = {}
-        self._flat = None
         self._steps = {}
         self._stale = True
-        self._pending = None
         self._act_grads = {}
         model.register_load_state_dict_post_hook(lambda module, _keys: setattr(self, "_stale", True))
 
@@ -168,35 +159,18 @@ class WaveGradTrainer:
         """[(module name, Conv1d)] in state_dict order."""
         return [(name, m) for name, m in self.model.named_modules() if isinstance(m, nn.Conv1d)]
 
-    def _view(self, flat, name):
-        """The (out, in, k) / (out,) view of a slot of `flat` (the masters, the gradient or a moment)."""
-        off, n, shape, kind = self._slots[name]
-        v = flat[off:off + n]
-        if kind == "bias":
-            return v
-        if kind == "init":  # stored (taps, C0), seen as (C0, 1, taps)
-            return v.view(shape[2], shape[0]).t().unsqueeze(1)
-        return v.view(shape[0], shape[2], shape[1]).permute(0, 2, 1)  # stored (N, taps, C)
-
     def _bind(self, dev):
         m = self.model
         init, last = m.DBlock[0], m.last_conv
         padded_bias = {id(blk.residual_dense) for blk in list(m.DBlock)[1:]}  # its bf16 output is an operand: 64-column rows
-        self._slots, off = {}, 0
+        entries = []
         for name, conv in self._convs():
             w, b = conv.weight, conv.bias
-            self._slots[name + ".weight"] = (off, w.numel(), tuple(w.shape), "init" if conv is init else "conv")
-            off += _pad8(w.numel())
-            self._slots[name + ".bias"] = (off, b.numel(), tuple(b.shape), "bias")
-            off += _pad8(_pad64(b.numel()) if id(conv) in padded_bias else b.numel())
-        self._total = off
-        self._flat, self._grad = torch.zeros(off, dtype=_F32, device=dev), torch.zeros(off, dtype=_F32, device=dev)
-        self._m1, self._m2 = torch.zeros(off, dtype=_F32, device=dev), torch.zeros(off, dtype=_F32, device=dev)
-        for name, p in m.named_parameters():
-            view = self._view(self._flat, name)
-            view.copy_(p.detach().to(device=dev, dtype=_F32))
-            p.data = view
-        self._norm_parts = int(_lib.load().ma_wavegrad_sumsq_parts(off))
+            entries.append((name + ".weight", tuple(w.shape), stored_last_first if conv is init else stored_taps_inner))
+            entries.append((name + ".bias", tuple(b.shape), None, _pad64(b.numel()) if id(conv) in padded_bias else b.numel()))
+        self._bind_params(entries, dev, mirror_bf16=False, moments=("moment1", "moment2"))
+        fp = self.params
+        self._norm_parts = int(_lib.load().ma_wavegrad_sumsq_parts(fp.size))
         self._norm_part = torch.zeros(self._norm_parts, dtype=torch.float64, device=dev)
         self._flag = torch.zeros(4, dtype=torch.int32, device=dev)
         self._norm = torch.zeros(4, dtype=_F32, device=dev)
@@ -213,36 +187,33 @@ class WaveGradTrainer:
             self._mirror = torch.zeros(sum(a + b for a, b in sizes), dtype=_BF16, device=dev)
         for i, (name, conv) in enumerate(mfma):
             n, c, k = conv.weight.shape
-            woff, boff = self._slots[name + ".weight"][0], self._slots[name + ".bias"][0]
+            woff, boff = fp.index[name + ".weight"][0], fp.index[name + ".bias"][0]
             rows = _pad64(n) if (self.bf16 and id(conv) in padded_bias) else n
-            bias = self._flat[boff:boff + rows]
+            bias = fp.master[boff:boff + rows]
             if self.bf16:
                 fsz, rsz = sizes[i]
                 fwd = self._mirror[mo:mo + fsz].view(rows, k, _pad64(c))
                 rev = self._mirror[mo + fsz:mo + fsz + rsz]
                 mo += fsz + rsz
                 mode = 1 if id(conv) in downs else 0
-                item = _lib.WaveGradWeightItem(self._flat.data_ptr() + woff * 4, fwd.data_ptr(), rev.data_ptr(), n, k, c, _pad64(c), _pad64(n),
+                item = _lib.WaveGradWeightItem(fp.ptr(name + ".weight"), fwd.data_ptr(), rev.data_ptr(), n, k, c, _pad64(c), _pad64(n),
                                                rows, mode, 0)
                 items.append((item, (_pad64(n) * k * _pad64(c) + 255) // 256))
                 self._rev[name] = rev
             else:
-                fwd = self._flat[woff:woff + n * k * c].view(n, k, c)
+                fwd = fp.master[woff:woff + n * k * c].view(n, k, c)
             self._P[id(conv)] = (fwd, bias)
             self._by_ptr[fwd.data_ptr()] = (name, n, c, k)
         for key, conv in (("init", init), ("last", last)):
             name = [nm for nm, cv in self._convs() if cv is conv][0]
-            woff, boff = self._slots[name + ".weight"][0], self._slots[name + ".bias"][0]
+            woff, boff = fp.index[name + ".weight"][0], fp.index[name + ".bias"][0]
             n, c, k = conv.weight.shape
-            w = self._flat[woff:woff + n * c * k].view(k, max(n, c))  # (taps, C0) and (taps, C)
-            self._P[key] = (w, self._flat[boff:boff + n])
+            w = fp.master[woff:woff + n * c * k].view(k, max(n, c))  # (taps, C0) and (taps, C)
+            self._P[key] = (w, fp.master[boff:boff + n])
             self._by_ptr[w.data_ptr()] = (name, n, c, k)
         self._weights_plan = plans.ItemTable(items, dev) if self.bf16 else None
         m._drop()
         self._stale = True
-        if self._pending:
-            self._load_moments(self._pending)
-            self._pending = None
 
     def _refresh(self, s):
         """The bf16 operand copies from the float32 masters: one launch."""
@@ -250,40 +221,15 @@ class WaveGradTrainer:
             _lib.check(_lib.load().ma_wavegrad_weights_bf16(*self._weights_plan.args, s), "wavegrad_weights")
         self._stale = False
 
-    def gradients(self):
-        """{state-dict name: float32 gradient of loss_scale * loss, (out, in, k)} of the last loss_and_grads / step (views)."""
-        return {name: self._view(self._grad, name) for name in self._slots}
-
     def activation_gradients(self):
         return dict(self._act_grads)
 
-    def state_dict(self):
-        out = {k: v.detach().clone().contiguous() for k, v in self.model.state_dict().items()}
-        if self._flat is not None:
-            for name in self._slots:
-                out["moment1." + name] = self._view(self._m1, name).detach().clone().contiguous()
-                out["moment2." + name] = self._view(self._m2, name).detach().clone().contiguous()
-        out["steps"] = torch.tensor(self.steps, dtype=torch.int64)
-        out["loss_scale"] = torch.tensor(self.scaler.scale, dtype=torch.float64)
-        return out
+    def _extra_state(self):
+        return {"loss_scale": torch.tensor(self.scaler.scale, dtype=torch.float64)}
 
-    def _load_moments(self, state):
-        for name in self._slots:
-            for prefix, buf in (("moment1.", self._m1), ("moment2.", self._m2)):
-                if prefix + name in state:
-                    self._view(buf, name).copy_(torch.as_tensor(state[prefix + name]).to(buf.device, _F32))
-
-    def load_state_dict(self, state):
-        names = list(self.model.state_dict())
-        self.model.load_state_dict({k: torch.as_tensor(state[k]) for k in names})
-        self.steps = int(state.get("steps", 0))
+    def _loaded(self, state):
         if "loss_scale" in state:
             self.scaler.scale = float(state["loss_scale"])
-        if self._flat is None:
-            self._pending = dict(state)
-        else:
-            self._load_moments(state)
-        self._stale = True
 
     # ---- the plan -----------------------------------------------------------------------------------------------------------------
     def _plan(self, B, frames, dev):
@@ -376,19 +322,19 @@ class WaveGradTrainer:
         # partials of last_conv and of the init convolution, and the one launch that sums them
         last, init = ops[-1], ops[0]
         lp, ip = int(lib.ma_wavegrad_last_bwd_parts(B, T)), int(lib.ma_wavegrad_init_bwd_parts(B, T))
-        st.last_stride = _pad8(last["taps"] * last["C"] + 1)
+        st.last_stride = (last["taps"] * last["C"] + 1 + 7) // 8 * 8
         st.last_part = torch.zeros(lp * st.last_stride, dtype=_F32, device=dev)
         st.loss_part = torch.zeros(lp, dtype=torch.float64, device=dev)
         istride = (init["taps"] + 1) * init["N"]
         st.init_part = torch.zeros(ip * istride, dtype=_F32, device=dev)
-        items = []
+        items, fp = [], self.params
         for part, stride, splits, op, nw, nb in ((st.last_part, st.last_stride, lp, last, last["taps"] * last["C"], 1),
                                                  (st.init_part, istride, ip, init, init["taps"] * init["N"], init["N"])):
             name = self._by_ptr[op["w"].data_ptr()][0]
-            woff, boff = self._slots[name + ".weight"][0], self._slots[name + ".bias"][0]
-            items.append(plans._reduce_item(part.data_ptr(), self._grad[woff:woff + nw], nw, nw, nw, splits, stride, splits >= 64,
+            woff, boff = fp.index[name + ".weight"][0], fp.index[name + ".bias"][0]
+            items.append(plans._reduce_item(part.data_ptr(), fp.grad[woff:woff + nw], nw, nw, nw, splits, stride, splits >= 64,
                                             accumulate=False))
-            items.append(plans._reduce_item(part.data_ptr() + nw * 4, self._grad[boff:boff + nb], nb, nb, nb, splits, stride, splits >= 64,
+            items.append(plans._reduce_item(part.data_ptr() + nw * 4, fp.grad[boff:boff + nb], nb, nb, nb, splits, stride, splits >= 64,
                                             accumulate=False))
         st.reduce = plans.ItemTable(items, dev)
         self._steps[key] = st
@@ -418,11 +364,11 @@ class WaveGradTrainer:
         _host.require_gpu()
         dev = noisy_audio.device
         with torch.no_grad():
-            if self._flat is None:
+            if self.params is None:
                 self.model.to(dev)
                 self._bind(dev)
-            elif self._flat.device != dev:
-                raise ValueError("the trainer is bound to %s" % self._flat.device)
+            elif self.params.master.device != dev:
+                raise ValueError("the trainer is bound to %s" % self.params.master.device)
             st = self._plan(B, frames, dev)
             st.enc = torch.from_numpy(positional_table(levels, self.model.enc_dims)).to(dev)
             st.ld_enc = st.enc.shape[1] if levels.size > 1 else 0
@@ -435,23 +381,22 @@ class WaveGradTrainer:
                 if self._stale:
                     self._refresh(s)
                 self._forward(st, s)
-                self._grad.zero_()  # (the bias gradients are column sums that add to what is there)
+                self.params.grad.zero_()  # (the bias gradients are column sums that add to what is there)
                 self._count("backward")
                 self._backward(st, s)
         return st
 
     def step(self, noisy_audio, noise_scale, noise, spectrogram, lr=None):
         st = self._run(noisy_audio, noise_scale, noise, spectrogram)
-        lib, scale = _lib.load(), self.scaler.scale
+        lib, scale, fp = _lib.load(), self.scaler.scale, self.params
         lr = self.learning_rate if lr is None else float(lr)
-        t = self.steps + 1
-        lr_t = lr * math.sqrt(1.0 - _BETA2 ** t) / (1.0 - _BETA1 ** t)
+        lr_t = adam_lr_t(lr, self.steps + 1, ADAM_BETA1, ADAM_BETA2)
         with torch.no_grad(), _host.pinned_stream():
             s = _host.current_stream_ptr()
-            _lib.check(lib.ma_wavegrad_sumsq_f64(self._grad.data_ptr(), self._total, self._norm_part.data_ptr(), s), "wavegrad_sumsq")
-            _lib.check(lib.ma_wavegrad_clip_adam_f32(self._flat.data_ptr(), self._grad.data_ptr(), self._m1.data_ptr(), self._m2.data_ptr(),
-                                                     self._total, self._norm_part.data_ptr(), self._norm_parts, scale, self.max_grad_norm,
-                                                     lr_t, _BETA1, _BETA2, _EPS, self._flag.data_ptr(), self._norm.data_ptr(), s),
+            _lib.check(lib.ma_wavegrad_sumsq_f64(fp.grad.data_ptr(), fp.size, self._norm_part.data_ptr(), s), "wavegrad_sumsq")
+            _lib.check(lib.ma_wavegrad_clip_adam_f32(fp.master.data_ptr(), fp.grad.data_ptr(), fp.moment1.data_ptr(), fp.moment2.data_ptr(),
+                                                     fp.size, self._norm_part.data_ptr(), self._norm_parts, scale, self.max_grad_norm,
+                                                     lr_t, ADAM_BETA1, ADAM_BETA2, _EPS, self._flag.data_ptr(), self._norm.data_ptr(), s),
                        "wavegrad_clip_adam")
             self._count("update", 2)
             if self.bf16:
@@ -531,7 +476,7 @@ class WaveGradTrainer:
             return _pad64(c) if bf else c
 
         def gslot(name, leaf):
-            return self._grad.data_ptr() + self._slots[name + leaf][0] * 4
+            return self.params.ptr(name + leaf, self.params.grad)
 
         def grad_image(op, halo):
             """The operand image of the gradient of op's output (slope 1, mul = alpha): one image serves dX and dW."""

@@ -2,9 +2,10 @@
 DynamicLossScaleUpdateCell)` does in the reference (mindaudio/utils/train_one_step.py:13-48,
 examples/conformer/train.py:104-141, examples/conformer/asr_model.py:75-153), with a hand-written backward pass.
 
-* All parameters live in ONE flat float32 buffer (masters), with a bf16 mirror at the same offsets (refreshed by one
-  cast kernel per step) and bf16 transposed copies of the matmul weights (the dX GEMMs read those).  Gradients, Adam
-  moments: flat buffers of the same layout -> one overflow check, one Adam launch, bucketed all-reduce on slices.
+* The parameters are a train.flat.FlatParams (64-element alignment): flat float32 masters with a bf16 mirror at the same
+  offsets (refreshed by one cast kernel per step), and bf16 transposed copies of the matmul weights (the dX GEMMs read
+  those).  Gradients, Adam moments: flat buffers of the same layout -> one overflow check, one Adam launch, bucketed
+  all-reduce on slices.
 * Forward keeps what the backward needs on an explicit tape (no autograd graph); dropout masks are regenerated from
   (seed, site, index).  Matmuls are bf16 MFMA with float32 accumulation; residual stream, LayerNorm/BatchNorm
   statistics, softmax, CTC lattice, gradients of parameters and the optimizer are float32.
@@ -21,62 +22,8 @@ from . import kernels as K
 from . import kernels_x32 as X32
 from . import plans
 from .block_table import RECORD, REPLAY, BlockTables
+from .flat import DynamicLossScale, FlatParams, adam_lr_t  # noqa: F401  (both classes are part of this module's interface)
 from .grad_schedule import Buckets, GradSchedule, half_of
-
-_PAD = 64  # every entry of the flat buffers starts on a 64-element boundary (16-byte aligned in bf16 and f32)
-
-
-class FlatParams:
-    """Name -> (offset, shape) views into flat float32 / bf16 buffers."""
-
-    def __init__(self, entries, device, mirror_bf16=True):
-        self.index = {}
-        off = 0
-        for name, shape in entries:
-            n = 1
-            for s in shape:
-                n *= s
-            self.index[name] = (off, tuple(shape), n)
-            off += (n + _PAD - 1) // _PAD * _PAD
-        self.size = off
-        self.master = torch.zeros(off, dtype=torch.float32, device=device)
-        # (one allocation: the flat gradient and, behind it, the step's overflow flag - one fill zeroes both)
-        self._grad_alloc = torch.zeros(off + 64, dtype=torch.float32, device=device)
-        self.grad = self._grad_alloc[:off]
-        self.flag = self._grad_alloc[off:off + 1].view(torch.int32)
-        self.exp_avg = torch.zeros(off, dtype=torch.float32, device=device)
-        self.exp_avg_sq = torch.zeros(off, dtype=torch.float32, device=device)
-        # matmul-operand copy of the masters: bf16 (throughput mode) or the masters themselves (float32 validation mode)
-        self.bf16 = torch.zeros(off, dtype=torch.bfloat16, device=device) if mirror_bf16 else self.master
-        self._pc, self._gc, self._wc = {}, {}, {}
-
-    def _view(self, buf, name):
-        off, shape, n = self.index[name]
-        return buf[off:off + n].view(shape)
-
-    # (the views are cached: the flat buffers never move, and a step asks for ~600 of them)
-    def p(self, name):
-        v = self._pc.get(name)
-        if v is None:
-            v = self._pc[name] = self._view(self.master, name)
-        return v
-
-    def g(self, name):
-        v = self._gc.get(name)
-        if v is None:
-            v = self._gc[name] = self._view(self.grad, name)
-        return v
-
-    def w(self, name):
-        v = self._wc.get(name)
-        if v is None:
-            v = self._wc[name] = self._view(self.bf16, name)
-        return v
-
-    def span(self, names):
-        lo = min(self.index[n][0] for n in names)
-        hi = max(self.index[n][0] + (self.index[n][2] + _PAD - 1) // _PAD * _PAD for n in names)
-        return lo, hi
 
 
 def asr_warmup_lr(step, base_lr=1e-3, warmup_steps=25000, start_steps=0):
@@ -85,24 +32,6 @@ def asr_warmup_lr(step, base_lr=1e-3, warmup_steps=25000, start_steps=0):
     if s <= 0.0:
         return 0.0
     return base_lr * warmup_steps ** 0.5 * min(s ** -0.5, s * warmup_steps ** -1.5)
-
-
-class DynamicLossScale:
-    """DynamicLossScaleUpdateCell(loss_scale_value, scale_factor, scale_window) (train.py:126-129): halve (min 1) on
-    overflow, double after `scale_window` consecutive clean steps."""
-
-    def __init__(self, init=1024.0, factor=2.0, window=1000):
-        self.scale, self.factor, self.window, self.good = float(init), float(factor), int(window), 0
-
-    def update(self, overflow):
-        if overflow:
-            self.scale = max(self.scale / self.factor, 1.0)
-            self.good = 0
-        else:
-            self.good += 1
-            if self.good >= self.window:
-                self.scale *= self.factor
-                self.good = 0
 
 
 class BucketedAllReduce:
@@ -1560,7 +1489,7 @@ class ConformerCTCTrainStep:
         two = self.lr_step_rule == "mindspore23"
         lr_opt = self.lr_at(self.global_step + 1) if two else lr
         tstep = self.applied_steps + 1
-        lr_t = lr_opt * math.sqrt(1.0 - self.b2 ** tstep) / (1.0 - self.b1 ** tstep)
+        lr_t = adam_lr_t(lr_opt, tstep, self.b1, self.b2)
         mirrored = K.adam(self.fp.master, self.fp.grad, self.fp.exp_avg, self.fp.exp_avg_sq, lr_t, self.b1, self.b2, self.eps,
                           1.0 / (scale * self.world), self.flag, **({} if self.x32 else {"mirror": self.fp.bf16}))
         self.refresh_weights(cast=not mirrored)  # (the bf16 mirror of the masters left with the update)

@@ -202,8 +202,8 @@ def test_three_steps_against_float64_adam():
     u, inv = 2.0 ** -24, 1.0 / (LOSS_SCALE * LOSS_SCALE)
     single_division_differs = False
     for t in (1, 2, 3):
-        names = list(tr._slots) if tr._flat is not None else None
-        before = None if names is None else {n: [tr._view(b, n).double().cpu().numpy() for b in (tr._flat, tr._m1, tr._m2)] for n in names}
+        names = list(tr.params.index) if tr.params is not None else None
+        before = None if names is None else {n: [tr.params._view(b, n).double().cpu().numpy() for b in (tr.params.master, tr.params.moment1, tr.params.moment2)] for n in names}
         if before is None:  # the first step binds the parameters: they are the model's, the moments zero
             before = {n: [np.asarray(state[n], np.float64), 0.0, 0.0] for n in [k for k in state if not k.startswith("conv.")]}
         loss, overflow = tr.step(x, LENGTHS, ys, ylens)
@@ -211,7 +211,7 @@ def test_three_steps_against_float64_adam():
         for n, (p0, m0, v0) in before.items():
             g = tr.gradients()[n].double().cpu().numpy()
             p1, m1, v1, delta, lr_t = _adam_f64(p0, m0, v0, g, t, LR, eps, inv)
-            got_p, got_m, got_v = (tr._view(b, n).double().cpu().numpy() for b in (tr._flat, tr._m1, tr._m2))
+            got_p, got_m, got_v = (tr.params._view(b, n).double().cpu().numpy() for b in (tr.params.master, tr.params.moment1, tr.params.moment2))
             b1 = float(np.float32(0.9))
             tiny = 2.0 ** -126  # a float32 result below the smallest normal number may be flushed to zero
             err_m = 4 * u * (np.abs(b1 * m0) + np.abs((1 - b1) * g * inv)) + tiny
@@ -231,12 +231,12 @@ def test_non_finite_input_sets_overflow_and_keeps_every_bit():
     cfg, state, x, model, tr = _trainer()
     ys, ylens = _targets()
     tr.step(x, LENGTHS, ys, ylens)
-    keep = [b.clone() for b in (tr._flat, tr._m1, tr._m2)]
+    keep = [b.clone() for b in (tr.params.master, tr.params.moment1, tr.params.moment2)]
     bad = x.copy()
     bad[1, 0, 3, 5] = np.nan  # (an infinite sample would only saturate the frozen front end's tanh: NaN goes through)
     _, overflow = tr.step(bad, LENGTHS, ys, ylens)
     assert overflow and tr.steps == 1
-    for a, b in zip(keep, (tr._flat, tr._m1, tr._m2)):
+    for a, b in zip(keep, (tr.params.master, tr.params.moment1, tr.params.moment2)):
         assert torch.equal(a.view(torch.int32), b.view(torch.int32))
     loss, overflow = tr.step(x, LENGTHS, ys, ylens)  # and the next clean step goes through
     assert np.isfinite(loss) and not overflow and tr.steps == 2
@@ -256,7 +256,7 @@ def test_state_dict_round_trip_and_the_next_step_is_bit_equal():
     other.load_state_dict(sd)
     a, b = tr.step(x, LENGTHS, ys, ylens), other.step(x, LENGTHS, ys, ylens)
     assert a == b and other.steps == 2
-    for u, v in zip((tr._flat, tr._m1, tr._m2), (other._flat, other._m1, other._m2)):
+    for u, v in zip((tr.params.master, tr.params.moment1, tr.params.moment2), (other.params.master, other.params.moment1, other.params.moment2)):
         assert torch.equal(u.view(torch.int32), v.view(torch.int32))
 
 

@@ -208,7 +208,7 @@ def test_trainer_refusals_come_before_the_device():
         tr.loss_and_grads(torch.zeros(2, 61), level, torch.zeros(2, 61), spec)  # T != hop * frames
     with pytest.raises(ValueError):
         tr.step(audio, level, audio, torch.zeros(2, 7, 2))  # n_mels
-    assert tr._flat is None and tr.steps == 0  # nothing was bound
+    assert tr.params is None and tr.steps == 0  # nothing was bound
 
 
 def test_noise_of_another_shape_is_refused_before_the_device(monkeypatch):
@@ -226,7 +226,7 @@ def test_noise_of_another_shape_is_refused_before_the_device(monkeypatch):
         tr.loss_and_grads(audio, level, torch.zeros(2, 60), spec)
     with pytest.raises(ValueError, match="noise must be a"):
         tr.step(audio, level, None, spec)
-    assert tr._flat is None
+    assert tr.params is None
 
 
 def test_script_refusals():
@@ -290,6 +290,7 @@ def test_trainer_binds_views_and_keeps_reference_names():
     """Binding needs no device: the model's parameters become (out, in, k) views of the flat masters kept in operand order, and
     state_dict() returns the values that went in."""
     from mindaudio_amd.models import WaveGrad, WaveGradTrainer
+    from mindaudio_amd.train.flat import stored_last_first
 
     c = T.case("tiny_b2")
     model = WaveGrad(c["hps"])
@@ -299,12 +300,12 @@ def test_trainer_binds_views_and_keeps_reference_names():
     sd = tr.state_dict()
     shapes = W.param_shapes(c["hps"])
     assert all(torch.equal(sd[k], c["state"][k]) and tuple(sd["moment1." + k].shape) == tuple(shapes[k]) for k in shapes)
-    off, n, shape, kind = tr._slots["UBlock.0.block2_a.weight"]
+    off, shape, n = tr.params.index["UBlock.0.block2_a.weight"]
     w = c["state"]["UBlock.0.block2_a.weight"]
-    assert torch.equal(tr._flat[off:off + n].view(shape[0], shape[2], shape[1]), w.permute(0, 2, 1))  # (N, taps, C)
-    off, n, shape, kind = tr._slots["DBlock.0.weight"]
-    assert kind == "init" and torch.equal(tr._flat[off:off + n].view(shape[2], shape[0]), c["state"]["DBlock.0.weight"][:, 0, :].t())
+    assert torch.equal(tr.params.master[off:off + n].view(shape[0], shape[2], shape[1]), w.permute(0, 2, 1))  # (N, taps, C)
+    off, shape, n = tr.params.index["DBlock.0.weight"]
+    assert tr.params._layout["DBlock.0.weight"] is stored_last_first and torch.equal(tr.params.master[off:off + n].view(shape[2], shape[0]), c["state"]["DBlock.0.weight"][:, 0, :].t())
     model.last_conv.weight.data.mul_(2.0)  # the parameter IS the master
-    off, n, _, _ = tr._slots["last_conv.weight"]
-    assert torch.equal(tr._flat[off:off + n].view(3, -1), 2.0 * c["state"]["last_conv.weight"][0].t())
-    assert tr._total % 8 == 0 and all(s[0] % 8 == 0 for s in tr._slots.values())
+    off, _, n = tr.params.index["last_conv.weight"]
+    assert torch.equal(tr.params.master[off:off + n].view(3, -1), 2.0 * c["state"]["last_conv.weight"][0].t())
+    assert tr.params.size % 8 == 0 and all(s[0] % 8 == 0 for s in tr.params.index.values())

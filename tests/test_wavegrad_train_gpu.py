@@ -558,7 +558,7 @@ def test_same_bits_from_run_to_run(torch, operands):
     c2, model2, tr2, _ = _trainer("tiny_b3", operands)
     assert tr2.loss_and_grads(*batch) == l1 and all(torch.equal(g1[k], v) for k, v in tr2.gradients().items())
     s1, s2 = tr.step(*batch), tr2.step(*batch)
-    assert s1 == s2 and torch.equal(tr._flat, tr2._flat) and torch.equal(tr._m2, tr2._m2)
+    assert s1 == s2 and torch.equal(tr.params.master, tr2.params.master) and torch.equal(tr.params.moment2, tr2.params.moment2)
 
 
 def test_utterances_do_not_see_each_other(torch):
@@ -613,7 +613,7 @@ def test_state_dict_round_trip(torch):
     c2, model2, tr2, _ = _trainer("tiny_b2", "bf16")
     tr2.load_state_dict({k: v.cpu() for k, v in sd.items()})
     a, b = tr.step(*batch), tr2.step(*batch)
-    assert a == b and torch.equal(tr._flat, tr2._flat)
+    assert a == b and torch.equal(tr.params.master, tr2.params.master)
 
 
 def test_train_script_checkpoint_resume(torch, tmp_path):

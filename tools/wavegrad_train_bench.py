@@ -47,7 +47,7 @@ def ours(a, torch):
     out["launches"] = dict(tr.launches)
     st = tr._steps[(a.batch, a.frames)]
     out["workspace_mb"] = round((st.ws.numel() + st.gws.numel() + st.gimg.numel()) / 2 ** 20, 1)
-    out["params"] = tr._total
+    out["params"] = tr.params.size
 
     def phase(fn):
         def run():
@@ -56,15 +56,15 @@ def ours(a, torch):
         return WB.timed(torch, run, 1, a.repeats)
 
     def backward(s):
-        tr._grad.zero_()
+        tr.params.grad.zero_()
         tr._backward(st, s)
 
     def update(s):  # (loss scale 2^30: the norm is tiny, the factor 1, the step a real one on whatever the gradient buffer holds)
         from mindaudio_amd import _lib
 
-        lib = _lib.load()
-        _lib.check(lib.ma_wavegrad_sumsq_f64(tr._grad.data_ptr(), tr._total, tr._norm_part.data_ptr(), s), "sumsq")
-        _lib.check(lib.ma_wavegrad_clip_adam_f32(tr._flat.data_ptr(), tr._grad.data_ptr(), tr._m1.data_ptr(), tr._m2.data_ptr(), tr._total,
+        lib, fp = _lib.load(), tr.params
+        _lib.check(lib.ma_wavegrad_sumsq_f64(fp.grad.data_ptr(), fp.size, tr._norm_part.data_ptr(), s), "sumsq")
+        _lib.check(lib.ma_wavegrad_clip_adam_f32(fp.master.data_ptr(), fp.grad.data_ptr(), fp.moment1.data_ptr(), fp.moment2.data_ptr(), fp.size,
                                                  tr._norm_part.data_ptr(), tr._norm_parts, tr.scaler.scale, 1.0, 2e-4, 0.9, 0.999, 1e-8,
                                                  tr._flag.data_ptr(), tr._norm.data_ptr(), s), "clip_adam")
         tr._refresh(s)
