@@ -1731,6 +1731,45 @@ int ma_ds2_conv1_bf16(const float* x, int64_t B, int32_t F, int64_t T, const flo
                       int32_t Fpad, void* out, ma_stream_t stream);
 int ma_ds2_softmax_f32(const float* logits, int64_t ld, int64_t T, int64_t B, int32_t C, float* probs, ma_stream_t stream);
 
+/* ---- DeepSpeech2's convolution front end in TRAINING mode (csrc/deepspeech2_train.hip): conv1, conv2 and both BatchNorm2d trained ----
+ * Channel-last everywhere, 32 channels, channel = column mod 32.  Every statistic is summed in double per thread, per workgroup and
+ * over the workgroups' partials ((a | b) of 64 doubles each), always in a fixed order; no atomics: the same bits run to run.
+ * ma_ds2_conv1_raw_f32: ma_ds2_conv1_bf16's convolution without its epilogue: y1 (T1, B, F1, 32) float32, the accumulators themselves,
+ *   and ma_ds2_conv1_raw_parts(B, T) partials (sum | sum of squares).
+ * ma_ds2_bn_stats_f32: the same partials, ma_ds2_stats_parts(n) of them, of n float32 values (n % 32 == 0, 16-byte aligned).
+ * ma_ds2_bn_finalize_f32: stats (96) = mean | 1 / sqrt(biased variance + eps) | biased variance over `count` values per channel;
+ *   mean_out / var_out (both or neither) = (1 - momentum) * mean_in / var_in + momentum * (mean, variance * count / (count - 1)):
+ *   the moving statistics are never updated in place.
+ * ma_ds2_bn_tanh_fwd_bf16: out[r * ldo + c] = bf16(tanh(fma(gamma, (y[r, c] - mean) * rstd, beta))) for y (rows, cols) contiguous,
+ *   cols % 32 == 0, ldo % 4 == 0; nothing else of `out` is touched.
+ * ma_ds2_bn_tanh_bwd_f32: the backward of that stage from the raw y and dout (rows, row stride ldd) float32 in three launches:
+ *   dn = dout (1 - a^2) with a recomputed as above and its partials (sum dn | sum dn xhat); their join bsum (128) = d_beta | d_gamma |
+ *   mean dn | mean dn xhat, also stored to d_gamma / d_beta (32 each, optional); dz = gamma rstd (dn - mean dn - xhat mean dn xhat)
+ *   to out[r * ldo + c], bf16 (out_bf16 != 0) or float32.  workspace >= ma_ds2_bn_tanh_bwd_workspace_bytes(rows, cols), 8-byte aligned.
+ * ma_ds2_conv1_dw_f32: dw (32, 451) = sum over (b, f1, t1) of dz1[t1, b, f1, c] * x[b, 2 f1 + kf - 20, 2 t1 + kt - 5] (zero outside x),
+ *   dz1 (T1, B, F1, 32) float32.  A workgroup walks frames_per_wg frames (0: ceil(B T1 / 1024)) with float32 fused multiply-adds, a
+ *   chain of frames_per_wg * F1 per output; the ma_ds2_conv1_dw_parts partials are added in double in partial order.
+ *   workspace >= parts * 451 * 32 * 4 bytes, 16-byte aligned.
+ * ma_ds2_commit_f32: dst[i] = src[i], i < n, unless overflow[0] != 0 (the moving statistics of a step that is not skipped).
+ * Shapes as ma_ds2_conv1_bf16: F <= 256, B <= 65535. */
+int32_t ma_ds2_conv1_raw_parts(int64_t B, int64_t T);
+int ma_ds2_conv1_raw_f32(const float* x, int64_t B, int32_t F, int64_t T, const float* wt, float* y1, double* partials,
+                         ma_stream_t stream);
+int32_t ma_ds2_stats_parts(int64_t n);
+int ma_ds2_bn_stats_f32(const float* y, int64_t n, double* partials, ma_stream_t stream);
+int ma_ds2_bn_finalize_f32(const double* partials, int32_t nparts, int64_t count, float eps, float momentum, const float* mean_in,
+                           const float* var_in, float* mean_out, float* var_out, float* stats, ma_stream_t stream);
+int ma_ds2_bn_tanh_fwd_bf16(const float* y, int64_t rows, int32_t cols, const float* stats, const float* gamma, const float* beta,
+                            void* out, int64_t ldo, ma_stream_t stream);
+int64_t ma_ds2_bn_tanh_bwd_workspace_bytes(int64_t rows, int32_t cols);
+int ma_ds2_bn_tanh_bwd_f32(const float* y, const float* dout, int64_t ldd, int64_t rows, int32_t cols, const float* stats,
+                           const float* gamma, const float* beta, void* out, int64_t ldo, int32_t out_bf16, float* bsum, float* d_gamma,
+                           float* d_beta, void* workspace, int64_t workspace_bytes, ma_stream_t stream);
+int32_t ma_ds2_conv1_dw_parts(int64_t B, int64_t T, int32_t frames_per_wg);
+int ma_ds2_conv1_dw_f32(const float* x, int64_t B, int32_t F, int64_t T, const float* dz1, int32_t frames_per_wg, float* dw,
+                        void* workspace, int64_t workspace_bytes, ma_stream_t stream);
+int ma_ds2_commit_f32(float* dst, const float* src, int32_t n, const int32_t* overflow, ma_stream_t stream);
+
 /* ---- Layer-pipelined unidirectional LSTM stack, inference (mindaudio/models/tasnet.py:106-108: nn.LSTM(N, hidden_size, num_layers,
  * bidirectional=False)) -----------------------------------------------------------------------------------------------------------------
  * The cell and its gate order are those of the block above; h_0 = c_0 = 0 in every layer; layer l >= 1 reads layer l - 1's h.

@@ -475,6 +475,18 @@ PROTOTYPES = {
     "ma_lstm_bidir_bwd_bf16": (ctypes.c_int, [vp, i64, i64, i32, vp, i64, vp, i32, vp, vp, i64, vp]),
     "ma_ds2_conv1_bf16": (ctypes.c_int, [vp, i64, i32, i64, vp, vp, vp, i32, vp, vp]),
     "ma_ds2_softmax_f32": (ctypes.c_int, [vp, i64, i64, i64, i32, vp, vp]),
+    # ---- DeepSpeech2's front end in training mode ----
+    "ma_ds2_conv1_raw_parts": (i32, [i64, i64]),
+    "ma_ds2_conv1_raw_f32": (ctypes.c_int, [vp, i64, i32, i64, vp, vp, vp, vp]),
+    "ma_ds2_stats_parts": (i32, [i64]),
+    "ma_ds2_bn_stats_f32": (ctypes.c_int, [vp, i64, vp, vp]),
+    "ma_ds2_bn_finalize_f32": (ctypes.c_int, [vp, i32, i64, f32, f32, vp, vp, vp, vp, vp, vp]),
+    "ma_ds2_bn_tanh_fwd_bf16": (ctypes.c_int, [vp, i64, i32, vp, vp, vp, vp, i64, vp]),
+    "ma_ds2_bn_tanh_bwd_workspace_bytes": (i64, [i64, i32]),
+    "ma_ds2_bn_tanh_bwd_f32": (ctypes.c_int, [vp, vp, i64, i64, i32, vp, vp, vp, vp, i64, i32, vp, vp, vp, vp, i64, vp]),
+    "ma_ds2_conv1_dw_parts": (i32, [i64, i64, i32]),
+    "ma_ds2_conv1_dw_f32": (ctypes.c_int, [vp, i64, i32, i64, vp, i32, vp, vp, i64, vp]),
+    "ma_ds2_commit_f32": (ctypes.c_int, [vp, vp, i32, vp, vp]),
     # ---- layer-pipelined LSTM stack, TasNet ----
     "ma_lstm_stack_workspace_bytes": (i64, [i64, i64, i32, i32]),
     "ma_lstm_stack_pack_f32": (ctypes.c_int, [vp, vp, vp, vp, i32, i32, i32, vp, vp, vp]),

@@ -11,7 +11,9 @@ newest keep_checkpoint_max of them stay.  A checkpoint holds the model's paramet
 What the reference's script does and this keeps (models.DeepSpeech2Trainer has the details): the loss scale is the constant 1024,
 Adam divides the unscaled gradient by OptimConfig.loss_scale a second time, step_lr is computed and never used - the rate is constant -
 and OptimConfig's weight_decay, momentum, eps, betas and learning_anneal are never read (epsilon is Adam's eps).
-The convolution front end is frozen.  `--is_distributed` raises NotImplementedError."""
+The convolution front end is frozen unless `--frontend trained` is given (train(config, frontend="trained")): conv1, conv2 and both
+BatchNorm2d are then trained as the reference trains them, and a checkpoint also holds `moment1.conv.*` / `moment2.conv.*`, which a
+later `--frontend trained` run restores.  `--is_distributed` raises NotImplementedError."""
 import argparse
 import os
 import time
@@ -74,8 +76,9 @@ def restore(trainer, path):
         trainer.load_state_dict(dict(trainer.model.state_dict(), steps=steps, **moments))
 
 
-def train(config, is_distributed=False, log=print, max_steps=None):
-    """train.py:26-96 on a config mapping; returns the list of per-step losses."""
+def train(config, is_distributed=False, log=print, max_steps=None, frontend="frozen", save_checkpoint_steps=SAVE_CHECKPOINT_STEPS):
+    """train.py:26-96 on a config mapping; returns the list of per-step losses.  frontend: models.DeepSpeech2Trainer's;
+    save_checkpoint_steps: the reference's constant 5 unless a caller (a short run, a test) asks for another interval."""
     if is_distributed:
         raise NotImplementedError("--is_distributed: multi-GPU DeepSpeech2 training is not built")
     s = settings(config)
@@ -88,11 +91,12 @@ def train(config, is_distributed=False, log=print, max_steps=None):
                               batch_size=s["batch_size"], log=log)
     model = DeepSpeechModel(batch_size=s["batch_size"], rnn_hidden_size=s["hidden_size"], nb_layers=s["hidden_layers"], labels=s["labels"],
                             rnn_type=s["rnn_type"], audio_conf=s["spect"], bidirectional=True).cuda()
-    trainer = DeepSpeech2Trainer(model, s["learning_rate"], s["epsilon"], loss_scale=LOSS_SCALE, optimizer_loss_scale=s["optimizer_loss_scale"])
+    trainer = DeepSpeech2Trainer(model, s["learning_rate"], s["epsilon"], loss_scale=LOSS_SCALE, optimizer_loss_scale=s["optimizer_loss_scale"],
+                                 frontend=frontend)
     if s["pretrained"]:
         restore(trainer, s["pretrained"])
         log("Successfully loading the pre-trained model")
-    saver = Checkpoints(trainer, s["ckpt_path"], s["prefix"], s["keep_checkpoint_max"])
+    saver = Checkpoints(trainer, s["ckpt_path"], s["prefix"], s["keep_checkpoint_max"], every=save_checkpoint_steps)
     losses, global_step = [], 0
     for epoch in range(1, s["epochs"] + 1):
         for i in range(len(dataset)):
@@ -116,8 +120,9 @@ def main(argv=None):
     ap.add_argument("--config_path", required=True)
     ap.add_argument("--Pretrained_model")
     ap.add_argument("--is_distributed", action="store_true")
+    ap.add_argument("--frontend", choices=("frozen", "trained"), default="frozen", help="train the convolution front end as well")
     a = ap.parse_args(argv)
-    return train(load_config(a.config_path, {"Pretrained_model": a.Pretrained_model}), is_distributed=a.is_distributed)
+    return train(load_config(a.config_path, {"Pretrained_model": a.Pretrained_model}), is_distributed=a.is_distributed, frontend=a.frontend)
 
 
 if __name__ == "__main__":

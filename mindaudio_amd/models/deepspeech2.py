@@ -147,19 +147,10 @@ class DeepSpeechModel(nn.Module):
 
     @torch.no_grad()
     def prepare(self):
-        dev = self.fc.module.weight.device
         f32, bf = torch.float32, torch.bfloat16
         self._ws = {}
-        c = self.conv
         P = {"layers": []}
-        P["w1t"] = c.conv1.weight.detach().to(f32).reshape(32, 41 * 11).t().contiguous()  # (451, 32)
-        for i, bn in ((1, c.bn1), (2, c.bn2)):
-            sc, sh = fold_batchnorm(*(p.detach().cpu().numpy() for p in (bn.gamma, bn.beta, bn.moving_mean, bn.moving_variance)))
-            P["scale%d" % i], P["shift%d" % i] = torch.from_numpy(sc).to(dev), torch.from_numpy(sh).to(dev)
-        # conv2 as 11 taps over time x (22 frequency rows x 32 channels): W[n, j, df * 32 + c] = w2[n, c, df, j], row 21 zero
-        w2 = torch.zeros((32, 11, 22, 32), dtype=f32, device=dev)
-        w2[:, :, :21, :] = c.conv2.weight.detach().to(f32).permute(0, 3, 2, 1)
-        P["w2"] = w2.reshape(32, 11 * 704).to(bf).contiguous()
+        self._fold_frontend(P)
         for k, cell in enumerate(self.RNN.lstms):
             fwd, bwd = ([getattr(cell, n + "_l0" + d).detach().to(f32) for n in ("weight_ih", "weight_hh", "bias_ih", "bias_hh")]
                         for d in ("", "_reverse"))
@@ -169,6 +160,23 @@ class DeepSpeechModel(nn.Module):
         P["fc"] = self.fc.module.weight.detach().to(bf).contiguous()
         self._prepared = P
         return self
+
+    @torch.no_grad()
+    def _fold_frontend(self, P):
+        """MaskConv's inference operands into P: conv1 tap-major, both BatchNorms folded, conv2 as 11 taps over time.  A trainer that has
+        changed the convolutions or the moving statistics sets P["frontend_stale"]; frontend() then comes back here."""
+        dev = self.fc.module.weight.device
+        f32, bf = torch.float32, torch.bfloat16
+        c = self.conv
+        P.pop("frontend_stale", None)
+        P["w1t"] = c.conv1.weight.detach().to(f32).reshape(32, 41 * 11).t().contiguous()  # (451, 32)
+        for i, bn in ((1, c.bn1), (2, c.bn2)):
+            sc, sh = fold_batchnorm(*(p.detach().cpu().numpy() for p in (bn.gamma, bn.beta, bn.moving_mean, bn.moving_variance)))
+            P["scale%d" % i], P["shift%d" % i] = torch.from_numpy(sc).to(dev), torch.from_numpy(sh).to(dev)
+        # conv2 as 11 taps over time x (22 frequency rows x 32 channels): W[n, j, df * 32 + c] = w2[n, c, df, j], row 21 zero
+        w2 = torch.zeros((32, 11, 22, 32), dtype=f32, device=dev)
+        w2[:, :, :21, :] = c.conv2.weight.detach().to(f32).permute(0, 3, 2, 1)
+        P["w2"] = w2.reshape(32, 11 * 704).to(bf).contiguous()
 
     def _workspace(self, B, F, T, dev):
         key = (B, F, T, str(dev), int(torch.cuda.current_stream().cuda_stream))
@@ -201,6 +209,8 @@ class DeepSpeechModel(nn.Module):
         if self._prepared is None or self._prepared["fc"].device != dev:
             self.prepare()
         P, lib, ck = self._prepared, _lib.load(), _lib.check
+        if P.get("frontend_stale"):
+            self._fold_frontend(P)
         B, _, F, T = x.shape
         ws = self._workspace(B, F, T, dev)
         T1, Fpad, act1, xin = ws["T1"], ws["Fpad"], ws["act1"], ws["xin"]

@@ -2,6 +2,8 @@
 Tensors are torch HIP tensors used as device buffers; all arithmetic happens in the HIP kernels."""
 import ctypes
 
+import numpy as np
+
 from . import _host, _lib
 
 
@@ -1228,3 +1230,205 @@ def lstm_bidir_backward(dout, tape, layer, need_dx=True, dgates=None):
             _lib.check(lib.ma_gemm_bf16(_host.ptr(dg[d]), g4, _host.ptr(layer["wih_t"][d]), g4, _host.ptr(dx), Kpad, T * B, Kpad, g4,
                                         ctypes.byref(e), s), "lstm dx")
     return dict(dgates=dg, dw_ih=dw_ih, dw_hh=dw_hh, db=db, dx=dx)
+
+
+# ---- DeepSpeech2's convolution front end in training mode (csrc/deepspeech2_train.hip) ---------------------------------------------------
+DS2_BN_EPS = 1e-5
+DS2_BN_MOMENTUM = 0.1  # moving = 0.9 * moving + 0.1 * batch: MindSpore's BatchNorm2d(momentum=0.9)
+DS2_DZ2_ROWS_BEFORE, DS2_DZ2_ROWS_EXTRA = 5, 11  # zero frequency rows of the dz2 image in front of row 0, and in all
+
+
+def ds2_frontend_operands(model):
+    """The training operands of MaskConv from the model's float32 parameters:
+      w1t  (451, 32) float32         conv1's weight, tap-major (ma_ds2_conv1_bf16's wt)
+      w2   (32, 11 * 704) bf16       conv2 as 11 time taps over 22 frequency rows x 32 channels, W[co, j, df * 32 + ci], row 21 zero
+      w2t  (2, 32, 11 * 384) bf16    its transpose for the input gradient, one image per parity p of the padded input row:
+                                     W_p[ci, j', k * 32 + co] = w2[co, ci, p + 2 (10 - k), 10 - j'], zero where that tap does not exist
+                                     (k = 11 always, k = 0 for p = 1): 12 consecutive output rows of the dz2 image, time taps reversed."""
+    t = _host.torch()
+    c = model.conv
+    w1, w2 = c.conv1.weight.detach().to(t.float32), c.conv2.weight.detach().to(t.float32)
+    dev = w2.device
+    fwd = t.zeros((32, 11, 22, 32), dtype=t.float32, device=dev)
+    fwd[:, :, :21, :] = w2.permute(0, 3, 2, 1)
+    rev = w2.flip(3)  # [co, ci, df, j'] with j = 10 - j'
+    wt = t.zeros((2, 32, 11, 12, 32), dtype=t.float32, device=dev)
+    wt[0, :, :, 0:11, :] = rev[:, :, [20 - 2 * k for k in range(11)], :].permute(1, 3, 2, 0)
+    wt[1, :, :, 1:11, :] = rev[:, :, [21 - 2 * k for k in range(1, 11)], :].permute(1, 3, 2, 0)
+    return dict(w1t=w1.reshape(32, 451).t().contiguous(), w2=fwd.reshape(32, 11 * 704).to(t.bfloat16).contiguous(),
+                w2t=wt.reshape(2, 32, 11 * 384).to(t.bfloat16).contiguous())
+
+
+class Ds2FrontendTape:
+    """What ds2_frontend_backward needs of ds2_frontend_train: the input x (B, 1, F, T), the raw float32 convolution outputs y1 (T1, B,
+    F1, 32) and y2 (T1 * B, F2 * 32), stats1 / stats2 (96: mean | rstd | biased variance), the operands, the BatchNorm parameters and,
+    by REFERENCE, the model's act1 and xin workspaces (an inference forward of the same shape in between overwrites them).
+    moving (128) = the updated moving_mean | moving_variance of bn1, then of bn2; the model's own are not touched."""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+
+def ds2_frontend_train(model, x, operands=None, mark=None):
+    """Train-mode MaskConv on x (B, 1, F, T): conv1 raw -> batch statistics -> tanh(BatchNorm) as the bf16 act1 image; conv2 per output
+    frequency raw -> batch statistics -> tanh(BatchNorm) as the bf16 LSTM input.  Nothing is masked.  -> (xin (T1, B, Kpad) bf16, tape).
+    Launches: 4 + (F2 + 3)."""
+    t = _host.require_gpu()
+    lib, ck = _lib.load(), _lib.check
+    dev = model.fc.module.weight.device
+    if dev.type != "cuda":
+        raise ValueError("the model's parameters must be on the HIP device (there is no CPU path)")
+    if not isinstance(x, t.Tensor):
+        x = t.from_numpy(np.ascontiguousarray(np.asarray(x, np.float32)))
+    if x.dim() != 4 or x.shape[1] != 1 or x.shape[2] != model.n_freq:
+        raise ValueError("x must be (B, 1, %d, T)" % model.n_freq)
+    x = x.to(dev, t.float32).contiguous()
+    P = operands if operands is not None else ds2_frontend_operands(model)
+    B, _, F, T = x.shape
+    ws = model._workspace(B, F, T, dev)
+    T1, Fpad, act1, xin = ws["T1"], ws["Fpad"], ws["act1"], ws["xin"]
+    F1, F2, lda, Kpad, rows = model.F1, model.F2, Fpad * 32, xin.shape[2], T1 * B
+    bn1, bn2 = model.conv.bn1, model.conv.bn2
+    f32 = t.float32
+    y1 = t.empty((T1, B, F1, 32), dtype=f32, device=dev)
+    y2 = t.empty((rows, F2 * 32), dtype=f32, device=dev)
+    np1, np2 = int(lib.ma_ds2_conv1_raw_parts(B, T)), int(lib.ma_ds2_stats_parts(rows * F2 * 32))
+    part = t.empty((max(np1, np2) * 64,), dtype=t.float64, device=dev)
+    stats1, stats2 = t.empty((96,), dtype=f32, device=dev), t.empty((96,), dtype=f32, device=dev)
+    moving = t.empty((128,), dtype=f32, device=dev)
+    e = _epilogue(out_bf16=False)
+    p = _host.ptr
+    with _host.pinned_stream():
+        s = _host.current_stream_ptr()
+        ck(lib.ma_ds2_conv1_raw_f32(p(x), B, F, T, p(P["w1t"]), p(y1), p(part), s), "ds2_conv1_raw")
+        ck(lib.ma_ds2_bn_finalize_f32(p(part), np1, rows * F1, DS2_BN_EPS, DS2_BN_MOMENTUM, p(bn1.moving_mean), p(bn1.moving_variance),
+                                      p(moving[0:32]), p(moving[32:64]), p(stats1), s), "ds2_bn_finalize")
+        ck(lib.ma_ds2_bn_tanh_fwd_bf16(p(y1), rows, F1 * 32, p(stats1), p(bn1.gamma), p(bn1.beta),
+                                       act1.data_ptr() + (5 * B * lda + 10 * 32) * 2, lda, s), "ds2_bn_tanh_fwd")
+        if mark:
+            mark("fe_stage1")
+        first = act1.data_ptr() + 5 * B * lda * 2
+        for fo in range(F2):
+            ck(lib.ma_conv1d_taps_bf16(first + 2 * fo * 32 * 2, lda, rows, 704, 11, B, p(P["w2"]), y2.data_ptr() + fo * 32 * 4, F2 * 32, 32,
+                                       ctypes.byref(e), s), "ds2_conv2")
+        ck(lib.ma_ds2_bn_stats_f32(p(y2), rows * F2 * 32, p(part), s), "ds2_bn_stats")
+        ck(lib.ma_ds2_bn_finalize_f32(p(part), np2, rows * F2, DS2_BN_EPS, DS2_BN_MOMENTUM, p(bn2.moving_mean), p(bn2.moving_variance),
+                                      p(moving[64:96]), p(moving[96:128]), p(stats2), s), "ds2_bn_finalize")
+        ck(lib.ma_ds2_bn_tanh_fwd_bf16(p(y2), rows, F2 * 32, p(stats2), p(bn2.gamma), p(bn2.beta), p(xin), Kpad, s), "ds2_bn_tanh_fwd")
+        if mark:
+            mark("fe_stage2")
+    tape = Ds2FrontendTape(x=x, y1=y1, y2=y2, stats1=stats1, stats2=stats2, moving=moving, act1=act1, xin=xin, operands=P, ws=ws,
+                           gamma1=bn1.gamma, beta1=bn1.beta, gamma2=bn2.gamma, beta2=bn2.beta, B=B, F=F, T=T, T1=T1, F1=F1, F2=F2,
+                           Fpad=Fpad, Kpad=Kpad)
+    return xin, tape
+
+
+def ds2_bn_tanh_backward(y, dout, stats, gamma, beta, out, out_ld=None):
+    """The BatchNorm + tanh backward of one stage (ma_ds2_bn_tanh_bwd_f32): y (rows, cols) float32 contiguous, the raw convolution
+    output; dout (rows, >= cols) float32 with its row stride; out: a float32 or bf16 tensor whose first element receives dz[0, 0], row
+    stride out_ld (default: cols).  -> bsum (128) = d_beta | d_gamma | mean dn | mean dn xhat."""
+    t = _host.torch()
+    lib = _lib.load()
+    rows, cols = y.shape
+    nbytes = int(lib.ma_ds2_bn_tanh_bwd_workspace_bytes(rows, cols))
+    if nbytes < 0:
+        _lib.check(nbytes, "ds2_bn_tanh_bwd_workspace_bytes")
+    work = t.empty((nbytes,), dtype=t.uint8, device=y.device)
+    bsum = t.empty((128,), dtype=t.float32, device=y.device)
+    _lib.check(lib.ma_ds2_bn_tanh_bwd_f32(_host.ptr(y), _host.ptr(dout), dout.stride(0), rows, cols, _host.ptr(stats), _host.ptr(gamma),
+                                          _host.ptr(beta), _host.ptr(out), cols if out_ld is None else out_ld,
+                                          1 if out.dtype == t.bfloat16 else 0, _host.ptr(bsum), None, None, _host.ptr(work), nbytes,
+                                          _host.current_stream_ptr()), "ds2_bn_tanh_bwd")
+    return bsum
+
+
+def ds2_conv1_dw(x, dz1, frames_per_wg=0):
+    """conv1's weight gradient (ma_ds2_conv1_dw_f32): x (B, 1, F, T) float32, dz1 (T1, B, F1, 32) float32 -> (32, 1, 41, 11) float32."""
+    t = _host.torch()
+    lib = _lib.load()
+    B, _, F, T = x.shape
+    parts = int(lib.ma_ds2_conv1_dw_parts(B, T, frames_per_wg))
+    if parts < 0:
+        _lib.check(parts, "ds2_conv1_dw_parts")
+    work = t.empty((parts * 451 * 32,), dtype=t.float32, device=x.device)
+    dw = t.empty((32, 1, 41, 11), dtype=t.float32, device=x.device)
+    _lib.check(lib.ma_ds2_conv1_dw_f32(_host.ptr(x), B, F, T, _host.ptr(dz1), frames_per_wg, _host.ptr(dw), _host.ptr(work),
+                                       work.numel() * 4, _host.current_stream_ptr()), "ds2_conv1_dw")
+    return dw
+
+
+def ds2_frontend_backward(dxin, tape, mark=None, keep=False):
+    """The backward of ds2_frontend_train from dxin (T1, B, Kpad) float32 = d loss / d xin (feature f * 32 + c; the bf16 rounding of
+    xin is passed straight through).  -> {"conv.conv1.weight" (32, 1, 41, 11), "conv.conv2.weight" (32, 32, 21, 11), "conv.bn{1,2}.gamma",
+    "conv.bn{1,2}.beta" (32): float32 gradients; "stats1", "stats2": the batch statistics of the forward; "launches": per piece}.
+    keep: also "dz1" (T1, B, F1, 32) float32, "dz2_image" (T1 + 10, B, (F2 + 11) * 32) bf16 and "dact1" (T1 * B, F1 * 32) float32.
+      BatchNorm  one ma_ds2_bn_tanh_bwd_f32 per stage; stage 2 writes dz2 as the bf16 operand image of the two products below, with 5
+                 zero frames around it and 5 / 6 zero frequency rows in front of / behind its F2 rows
+      conv2 dW   per (time tap j, output frequency fo) one ma_gemm_tn_bf16_f32: dz2's 32 columns of fo against act1 shifted by j - 5
+                 frames at columns 2 fo * 32 .. + 703, accumulated over fo into (11, 32, 704); row 21 of the 22 is padding and dropped
+      conv2 dX   per input frequency one ma_conv1d_taps_bf16 over 12 frequency rows of the dz2 image on the transposed weights of the
+                 row's parity (ds2_frontend_operands)
+      conv1 dW   ma_ds2_conv1_dw_f32 on the float32 dz1."""
+    t = _host.torch()
+    lib, ck, p = _lib.load(), _lib.check, _host.ptr
+    tp = tape
+    B, T1, F1, F2, Fpad, Kpad = tp.B, tp.T1, tp.F1, tp.F2, tp.Fpad, tp.Kpad
+    rows, dev, f32 = T1 * B, tp.y1.device, t.float32
+    if not isinstance(dxin, t.Tensor) or dxin.dtype != f32 or tuple(dxin.shape) != (T1, B, Kpad) or dxin.device != dev:
+        raise ValueError("dxin must be a (T1, B, Kpad) float32 tensor on the tape's device")
+    dxin = dxin.contiguous()
+    F2p = F2 + DS2_DZ2_ROWS_EXTRA
+    ldz, lda = F2p * 32, Fpad * 32
+    img = tp.ws.get("dz2_image")
+    if img is None:
+        img = tp.ws["dz2_image"] = t.zeros((T1 + 10, B, ldz), dtype=t.bfloat16, device=dev)  # only the interior is ever written
+    interior = img.view(-1)[(5 * B * F2p + DS2_DZ2_ROWS_BEFORE) * 32:]
+    out, launches = {}, {}
+    with _host.pinned_stream():
+        s = _host.current_stream_ptr()
+        bs2 = ds2_bn_tanh_backward(tp.y2, dxin.view(rows, Kpad), tp.stats2, tp.gamma2, tp.beta2, interior, ldz)
+        launches["batchnorm"] = 3
+        if mark:
+            mark("fe_bn2_bwd")
+        # conv2 dW
+        acc = t.empty((11, 32, 704), dtype=f32, device=dev)
+        tnb = int(lib.ma_gemm_tn_workspace_bytes(32, 704, rows))
+        tn = t.empty((tnb + 256,), dtype=t.uint8, device=dev)
+        a0 = interior.data_ptr()
+        for j in range(11):
+            b0 = tp.act1.data_ptr() + j * B * lda * 2
+            for fo in range(F2):
+                ck(lib.ma_gemm_tn_bf16_f32(a0 + fo * 32 * 2, ldz, b0 + 2 * fo * 32 * 2, lda, acc.data_ptr() + j * 32 * 704 * 4, 704, 32, 704,
+                                           rows, 32, 1.0, 1 if fo else 0, None, p(tn), tnb, s), "ds2 conv2 dW")
+        launches["conv2_dw"] = 2 * 11 * F2  # (a product and the sum of its splits each)
+        out["conv.conv2.weight"] = acc.view(11, 32, 22, 32)[:, :, :21, :].permute(1, 3, 2, 0).contiguous()
+        if mark:
+            mark("fe_conv2_dw")
+        # conv2 dX
+        dact1 = t.empty((rows, F1 * 32), dtype=f32, device=dev)
+        e = _epilogue(out_bf16=False)
+        frame0 = img.data_ptr() + 5 * B * ldz * 2
+        for fi in range(F1):
+            r = fi + 10
+            par = r & 1
+            q0 = (r - par) // 2 - 10 + DS2_DZ2_ROWS_BEFORE
+            ck(lib.ma_conv1d_taps_bf16(frame0 + q0 * 32 * 2, ldz, rows, 384, 11, B, p(tp.operands["w2t"][par]),
+                                       dact1.data_ptr() + fi * 32 * 4, F1 * 32, 32, ctypes.byref(e), s), "ds2 conv2 dX")
+        launches["conv2_dx"] = F1
+        if mark:
+            mark("fe_conv2_dx")
+        dz1 = t.empty((T1, B, F1, 32), dtype=f32, device=dev)
+        bs1 = ds2_bn_tanh_backward(tp.y1.view(rows, F1 * 32), dact1, tp.stats1, tp.gamma1, tp.beta1, dz1)
+        launches["batchnorm"] += 3
+        if mark:
+            mark("fe_bn1_bwd")
+        out["conv.conv1.weight"] = ds2_conv1_dw(tp.x, dz1)
+        launches["conv1_dw"] = 2
+        if mark:
+            mark("fe_conv1_dw")
+    for i, bs in ((1, bs1), (2, bs2)):
+        out["conv.bn%d.beta" % i], out["conv.bn%d.gamma" % i] = bs[0:32], bs[32:64]
+    out.update(stats1=tp.stats1, stats2=tp.stats2, launches=launches)
+    if keep:
+        out.update(dz1=dz1, dz2_image=img, dact1=dact1)
+    return out

@@ -2,7 +2,8 @@
 """DeepSpeech2 training step at the example's training shape: examples/deepspeech2/deepspeech2.yaml (hidden_size 1024,
 hidden_layers 5, 161 frequency bins), 64 utterances padded to 1250 frames (T1 = 625 LSTM steps per layer), 100 labels each.
 
---part ours        models.DeepSpeech2Trainer.step (frozen front end).  One JSON line with
+--frontend frozen | trained   models.DeepSpeech2Trainer's option of that name (default frozen), for both parts.
+--part ours        models.DeepSpeech2Trainer.step.  One JSON line with
     step / forward / loss / backward / update   median_ms and min_ms of --repeats steps, the phases from device events at the
                    trainer's phase boundaries (forward includes the front end; backward the fc products and every layer)
     loss_value / overflow   what the last step returned;  launches   the trainer's launch counts per phase of one step
@@ -11,8 +12,12 @@ hidden_layers 5, 161 frequency bins), 64 utterances padded to 1250 frames (T1 = 
     fwd_step_us / bwd_step_us   those two divided by T1: microseconds per step launch, forward beside backward
     bwd_products   the four products that follow the backward steps of that layer (dW_ih + db, dW_hh, dx), per layer
     tape_mb        ma_lstm_train_tape_bytes per layer;  peak_mem_mb   torch.cuda.max_memory_allocated over the steps
+    --frontend trained adds, from device events inside the same steps: frontend_forward (conv1, conv2, both BatchNorms), and the
+                   front end's backward split into frontend_batchnorm (both stages' launches), frontend_conv2_dw, frontend_conv2_dx
+                   and frontend_conv1_dw; their launch counts are in `launches`
 --part eager       the same recurrent stack, fc, CTC loss and Adam step in PyTorch-ROCm eager (torch.nn.LSTM autograd, float32) on the
     output of an untimed front end: median_ms, or {"error": ...} if a library refuses the shape (reported, not worked round).
+    With --frontend trained the front end is part of the timed graph: conv2d + batch_norm(training=True) + tanh twice, in float32.
 The reference runs on MindSpore, which is not installed here: nothing is said about its speed.  No threshold: the figures are
 measurements."""
 import argparse
@@ -62,12 +67,17 @@ def ours(a, torch):
     _host.require_gpu()
     lib = _lib.load()
     model = DeepSpeechModel(a.batch, ["x"] * LABELS, a.hidden, a.layers, dict(sample_rate=16000, window_size=0.02)).cuda().eval()
-    trainer = DeepSpeech2Trainer(model, 3e-4, 1e-5, loss_scale=1024)
+    trainer = DeepSpeech2Trainer(model, 3e-4, 1e-5, loss_scale=1024, frontend=a.frontend)
     x, lengths, targets, target_lengths = _batch(a, torch)
     torch.cuda.reset_peak_memory_stats()
     for _ in range(a.warmup):
         trainer.step(x, lengths, targets, target_lengths)
     phases = {k: [] for k in ("step", "forward", "loss", "backward", "update")}
+    # (name of a piece of the trained front end: the event pairs whose spans add up to it)
+    pieces = {"frontend_forward": [("start", "fe_stage2")], "frontend_batchnorm": [("lstm_backward", "fe_bn2_bwd"), ("fe_conv2_dx", "fe_bn1_bwd")],
+              "frontend_conv2_dw": [("fe_bn2_bwd", "fe_conv2_dw")], "frontend_conv2_dx": [("fe_conv2_dw", "fe_conv2_dx")],
+              "frontend_conv1_dw": [("fe_bn1_bwd", "fe_conv1_dw")]} if a.frontend == "trained" else {}
+    phases.update({k: [] for k in pieces})
     for _ in range(a.repeats):
         torch.cuda.synchronize()
         trainer.events = []
@@ -78,6 +88,8 @@ def ours(a, torch):
         for prev, name in zip(order, order[1:]):
             phases[name].append(ev[prev].elapsed_time(ev[name]))
         phases["step"].append(ev["start"].elapsed_time(ev["update"]))
+        for name, spans in pieces.items():
+            phases[name].append(sum(ev[lo].elapsed_time(ev[hi]) for lo, hi in spans))
     trainer.events = None
     out = {k: _stat(v) for k, v in phases.items()}
     out.update(loss_value=round(float(loss), 4), overflow=bool(overflow), launches=dict(trainer.launches),
@@ -117,15 +129,24 @@ def eager(a, torch):
     x, lengths, targets, target_lengths = _batch(a, torch)
     xin = model.frontend(x)[:, :, :model.rnn_input_size].float()  # the frozen front end, untimed
     T1 = xin.shape[0]
+    trained = a.frontend == "trained"
+    convs = [torch.nn.Conv2d(1, 32, (41, 11), stride=(2, 2), padding=(20, 5), bias=False).cuda(),
+             torch.nn.Conv2d(32, 32, (21, 11), stride=(2, 1), padding=(10, 5), bias=False).cuda()] if trained else []
+    norms = [torch.nn.BatchNorm2d(32, momentum=0.1).cuda().train() for _ in convs]
     lstms = [torch.nn.LSTM(model.rnn_input_size if k == 0 else a.hidden, a.hidden, bidirectional=True).cuda() for k in range(a.layers)]
     fc = torch.nn.Linear(a.hidden, LABELS, bias=False).cuda()
-    params = [p for m in lstms + [fc] for p in m.parameters()]
+    params = [p for m in lstms + [fc] + convs + norms for p in m.parameters()]
     opt = torch.optim.Adam(params, lr=3e-4, eps=1e-5)
     ys, ylens = torch.from_numpy(targets).long().cuda(), torch.from_numpy(target_lengths).long().cuda()
     hlens = torch.full((a.batch,), T1, dtype=torch.long, device="cuda")
 
     def step():
         h = xin
+        if trained:  # (B, 1, F, T) -> (B, 32, F2, T1) -> (T1, B, 32 F2)
+            h = x
+            for conv, norm in zip(convs, norms):
+                h = torch.tanh(norm(conv(h)))
+            h = h.reshape(a.batch, -1, T1).permute(2, 0, 1)
         for lstm in lstms:
             h, _ = lstm(h)
             h = h.reshape(T1, a.batch, 2, -1).sum(2)
@@ -135,7 +156,10 @@ def eager(a, torch):
         opt.step()
 
     try:
-        return timed(torch, step, a.warmup, a.repeats)
+        torch.cuda.reset_peak_memory_stats()
+        out = timed(torch, step, a.warmup, a.repeats)
+        out["peak_mem_mb"] = round(torch.cuda.max_memory_allocated() / 2 ** 20, 1)
+        return out
     except RuntimeError as err:  # e.g. MIOpen refusing the shape: reported as it is
         return {"error": str(err).split("\n")[0][:300]}
 
@@ -143,6 +167,7 @@ def eager(a, torch):
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--part", choices=("ours", "eager"), default="ours")
+    ap.add_argument("--frontend", choices=("frozen", "trained"), default="frozen")
     ap.add_argument("--batch", type=int, default=64)
     ap.add_argument("--frames", type=int, default=1250)
     ap.add_argument("--hidden", type=int, default=1024)
@@ -157,7 +182,7 @@ def main(argv=None):
     if not torch.cuda.is_available():
         raise SystemExit("deepspeech2_train_bench needs a HIP device: nothing is measured without one")
     torch.manual_seed(0)
-    result = {"part": a.part, "batch": a.batch, "frames": a.frames, "hidden": a.hidden, "layers": a.layers, "labels": a.labels,
+    result = {"part": a.part, "frontend": a.frontend, "batch": a.batch, "frames": a.frames, "hidden": a.hidden, "layers": a.layers, "labels": a.labels,
               "repeats": a.repeats, "device": torch.cuda.get_device_name(0)}
     result.update(ours(a, torch) if a.part == "ours" else {"eager": eager(a, torch)})
     print(json.dumps(result))
