@@ -88,6 +88,14 @@ class _Embed(nn.Module):
         self.out = nn.Linear(odim * (((idim - 1) // 2 - 1) // 2), odim)
 
 
+def fold_batchnorm(cm):
+    """The affine form the eval kernels read: BatchNorm1d (running statistics) of depthwise(.) + its bias = depthwise_nobias(.) *
+    scale + shift, scale = gamma / sqrt(var + eps), shift = beta + (dw_bias - mean) * scale  -> (scale, shift) in the module's dtype."""
+    bn = cm.norm
+    scale = bn.weight.detach() / torch.sqrt(bn.running_var + bn.eps)
+    return scale, bn.bias.detach() + (cm.depthwise_conv.bias.detach() - bn.running_mean) * scale
+
+
 class ConformerEncoder(nn.Module):
     """Same constructor arguments as the reference (models/conformer.py:293-313).  `global_cmvn` is a
     (mean, istd) pair of arrays (layers/cmvn.py); `compute_type` is accepted for signature parity — matmul
@@ -157,9 +165,7 @@ class ConformerEncoder(nn.Module):
         }
         for l in self.encoders:
             a, cm = l.self_attn, l.conv_module
-            bn = cm.norm
-            scale = bn.weight.detach() / torch.sqrt(bn.running_var + bn.eps)
-            shift = bn.bias.detach() + (cm.depthwise_conv.bias.detach() - bn.running_mean) * scale
+            scale, shift = fold_batchnorm(cm)
             prep["layers"].append({
                 "ffm_w1": l.feed_forward_macaron.w_1.weight.detach().to(bf).contiguous(),
                 "ffm_b1": l.feed_forward_macaron.w_1.bias.detach().float().contiguous(),
@@ -373,10 +379,9 @@ class ConformerEncoder(nn.Module):
     def _refresh_bn(self, P):
         """Re-fold BatchNorm (running statistics) + depthwise bias into the affine form the eval kernels read."""
         for l, W in zip(self.encoders, P["layers"]):
-            cm, bn = l.conv_module, l.conv_module.norm
-            scale = bn.weight.detach() / torch.sqrt(bn.running_var + bn.eps)
+            scale, shift = fold_batchnorm(l.conv_module)
             W["bn_scale"].copy_(scale.float())
-            W["bn_shift"].copy_((bn.bias.detach() + (cm.depthwise_conv.bias.detach() - bn.running_mean) * scale).float())
+            W["bn_shift"].copy_(shift.float())
         self._bn_dirty = False
 
     @staticmethod

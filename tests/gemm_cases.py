@@ -259,9 +259,10 @@ LD_KINDS = ("a8", "a8o4", "a4", "odd")
 def ld_off(N, kind):
     """(leading dimension, column offset of the window) of layout `kind`: a8 = ld % 8 == 0 and a 16-byte aligned base, a8o4 = the
     window 4 elements further right, a4 = ld % 4 == 0 only, odd = an odd ld, tight = ld == N (guard rows only, for the entry points
-    without a leading dimension).  Offsets are multiples of 4 elements."""
+    without a leading dimension), pad8 = the window at column 0 of rows of N + 8 elements (convmodule_cases).  Offsets are multiples of
+    4 elements."""
     ld8 = (N + 16 + 7) // 8 * 8
-    return {"a8": (ld8, 8), "a8o4": (ld8, 4), "a4": (ld8 + 4, 4), "odd": (ld8 + 3, 4), "tight": (N, 0)}[kind]
+    return {"a8": (ld8, 8), "a8o4": (ld8, 4), "a4": (ld8 + 4, 4), "odd": (ld8 + 3, 4), "tight": (N, 0), "pad8": (N + 8, 0)}[kind]
 
 
 def _bits(x):
